@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s and Mrays/s of the hot path on N MI355X (one process per GPU).
 
-A "step" is one pass of the hot path over one batch of synthetic input: one sample per pixel.  The default run (N = 1)
-times the FOUR GPU configurations of BASELINE.json and prints ONE SMALL JSON line (<= 6 KB: the contract's fields for the headline,
-`configs`: one compact object per other configuration); the full records -- per-kernel tables, counter calibration, yard-sticks, API
-legs, per-rank statistics -- go to bench_detail.json beside this file (and to stderr behind "bench_detail: ").
+A "step" is one pass of the hot path over one batch of synthetic input: one sample per pixel.  A plain run times the headline
+configuration only -- set-up, W warm-up steps, the K timed steps, --dump-outputs if asked -- and prints ONE SMALL JSON line (<= 6 KB).
+`--full` adds everything else: the other GPU configurations of BASELINE.json (`configs`: one compact object each), the roofline and its
+counters, the CPU baseline, the API and tolerance legs, at N > 1 the fixed-work and group legs; their full records -- per-kernel tables,
+counter calibration, yard-sticks, API legs, per-rank statistics -- go to bench_detail.json beside this file (and to stderr behind
+"bench_detail: ").
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes the headline's accumulator (what a caller of the timed path receives) to
+                       DIR/accum.npy, float32 (a seeded sample of its pixels above 64 MB: dump_outputs).  Inputs are generated from
+                       fixed pass indices, so the same arguments give the same inputs on every run.
 
   headline     BASELINE configs[1]: data/cornell.tin 1024x1024 maxDepth 4 (spp 256 <=> --steps 256).  The scene (2.6 KB) lives in
                LDS: the path is bound by VALU issue, and `roofline` says so (bound "valu": wave-instructions issued per second
@@ -21,11 +27,12 @@ Scenes come from scene packs written by the reference's own loader (tests/golden
 everything downstream are generated on the GPU, so inputs are resident in HBM when a timed region starts, and the
 accumulation buffer stays in HBM (`api_msamples_s` reports the API's per-call D2H patterns separately).
 
-Timing: W untimed warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize()
-on both sides, repeated until >= 0.5 s have been timed; `ms_per_step` is the MEDIAN block / K, `value` the samples of
-one block / that median (max over ranks for N > 1).
+Timing: W untimed warm-up steps (repeated from the same pass index until the device has run them for 0.5 s: clocks settle), then
+ONE block of EXACTLY K steps, bracketed by barrier + torch.cuda.synchronize() on both sides; `ms_per_step` is that block / K, `value`
+the samples of the block / its time (max over ranks for N > 1).  Choose K so that the block lasts long enough to measure.  `--full`
+takes the kernels' own times in one more block of K steps after the timed one.
 
-Counters: `roofline.traffic` (HBM bytes per launch of the dominant kernel) and the VALU instruction count behind
+Counters (--full): `roofline.traffic` (HBM bytes per launch of the dominant kernel) and the VALU instruction count behind
 `roofline.achieved` are measured IN THIS RUN, on this box, by re-running the same workload under
 `rocprofv3 --pmc` (separate passes for FETCH_SIZE, WRITE_SIZE, the SQ counters and TCC hits / misses).  What one count of
 FETCH_SIZE / WRITE_SIZE stands for is CALIBRATED in the same passes on kernels with a known byte count
@@ -35,9 +42,9 @@ chases through a 1 GiB table, beyond the Infinity Cache, for the walking kernels
 
 N > 1 (launched by torch.distributed.run; the ranks meet at once, under a 90 s watchdog): `value` is WEAK scaling -- every rank
 traces its interleaved pixel tiles for K*N passes (same paths per GPU as N = 1), then ONE RCCL sum-reduce of the float4 accumulator
-to rank 0 inside the timed region (tinsel_amd.distributed.reduce_accum).  `strong_msamples_s` is the FIXED-WORK leg beside it: the
+to rank 0 inside the timed region (tinsel_amd.distributed.reduce_accum).  `strong_msamples_s` (--full) is the FIXED-WORK leg beside it: the
 same K full-frame passes as N = 1 split over the ranks' tiles + the reduce (north_star's 8-GPU configuration, veach 4K at 4096
-spp, is a fixed job); veach 4K gets both legs too (`configs`).  AFTER the ranks' timed regions rank 0 times the SAME N devices
+spp, is a fixed job); veach 4K gets both legs too (`configs`).  With --full, AFTER the ranks' timed regions rank 0 times the SAME N devices
 through the library's own multi-GPU path (`--group`: tinsel_hip_group, what the reference's single-process C++ caller gets through
 the shim) in child processes limited to 60 s each: `group`, `group_cfg5`.
 """
@@ -65,6 +72,7 @@ SIMDS = 256*4                   # 256 CUs x 4 SIMDs
 CLOCK_HZ = 2.4e9                # max clock, same guide
 VALU_PEAK = SIMDS*CLOCK_HZ/2    # a wave64 VALU instruction issues over 2 cycles on a SIMD-32 (same guide; scratch/ubench/valu_bench.hip: 2.6)
 MIN_TIMED_S = 0.5
+MIN_WARMUP_S = 0.5
 GROUP_LEG_LIMIT_S = 60            # each tinsel_hip_group leg of an N-rank run (child process of rank 0, after the ranks' timed regions)
 LARGE = "large/ajax_standin"
 REAL_MESH = "large/ajax_aphrodite"   # config 3 once more: ajax.tin with the reference's own Aphrodite scan, 1 -> 4 subdivided (427,384 triangles, an irregular tree)
@@ -98,8 +106,16 @@ def parse():
     ap.add_argument("--no-group-leg", action="store_true", help="N > 1: do not time the tinsel_hip_group path from rank 0 before the ranks meet")
     ap.add_argument("--tuning", default="", help='A/B: a tinsel_hip_tuning as JSON, e.g. \'{"walk_refill_min": 16}\' (tinsel_amd.abi.Tuning; the default run sets nothing)')
     ap.add_argument("--force-comm", action="store_true", help="N = 1 validation: make the library's RCCL communicator of ONE rank and put its ncclReduce inside the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel roofline and counters, CPU baseline, API legs, tolerance arm, "
+                         "the other BASELINE configs, N > 1 fixed-work and group legs, bench_detail.json (the --no-* switches act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's accumulator (what the timed path returns to its caller) to DIR/*.npy")
     ap.add_argument("--inner-pmc", action="store_true", help=argparse.SUPPRESS)      # the child process the PMC passes profile
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -288,10 +304,33 @@ def yard_sticks():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returns to its caller, so that two builds can be compared output for output
 
-def run_config(args, scene_name, width, height, maxdepth, rank, world, local, dist, backend, torch, with_extras, cfg_spp=256):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, accum):
+    """The accumulator [H, W, 4] float32 after the timed steps (per pixel: the filter-weighted radiance sums and the weight, over every
+    pass since the timed region began) as accum.npy.  Above DUMP_LIMIT_BYTES: a fixed seeded sample of its pixels instead, accum_sample.npy
+    [n, 4], with their flat pixel indices in accum_sample_index.npy (float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.ascontiguousarray(accum, dtype=np.float32)
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "accum.npy"), a)
+        return
+    flat = a.reshape(-1, a.shape[-1])
+    n = DUMP_LIMIT_BYTES//2//flat.strides[0]
+    idx = np.sort(np.random.default_rng(20261015).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "accum_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "accum_sample_index.npy"), idx.astype(np.float64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+
+def run_config(args, scene_name, width, height, maxdepth, rank, world, local, dist, backend, torch, with_extras, cfg_spp=256, dump_dir=None):
     """Times one configuration per the contract; returns the dict bench_detail.json keeps for it (rank 0; None elsewhere).
-    `cfg_spp`: the samples per pixel BASELINE.json quotes the configuration at (the tolerance arm's L2 is taken at that spp)."""
+    `cfg_spp`: the samples per pixel BASELINE.json quotes the configuration at (the tolerance arm's L2 is taken at that spp).
+    `dump_dir`: where rank 0 writes the accumulator after the timed steps (dump_outputs)."""
     import tinsel_amd
     from tinsel_amd import abi
 
@@ -349,73 +388,60 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- algorithmic-bytes constants of this workload (device counters, untimed) --------------
-    r.set_detail_counters(True)
-    r.reset_stats()
-    r.render_async(cam, opt, passes=passes_per_step, stream=stream)
-    torch.cuda.synchronize()
-    c = r.stats()
-    r.set_detail_counters(False)
-    # (the counted pass may run another pipeline -- the paired one counts nothing -- and so give the path buffers back: reserve again, outside
-    # every timed region)
-    r.reserve(max(args.steps, args.warmup, 1)*world, opt.max_depth)
-    rays_c = max(1, c["rays"])
-    I_bar, T_bar, P_bar = c["internal_visits"]/rays_c, c["tri_tests"]/rays_c, c["prim_tests"]/rays_c
-    B_ray = 48.0 + 64.0*I_bar + 48.0*T_bar + 84.0*P_bar
-    fw = opt.filter.width
-    # pixels AddSample touches per sample (render.cpp:426-429: [int(x - fw), int(x + fw)] per axis, x uniform in the pixel):
-    # 2 fw + 1 per axis on average away from the frame edge -- 6.25 for the default 0.75 (4..9)
-    K_fp = (2.0*fw + 1.0)**2
-    B_fb = 32.0*K_fp
-
-    # ---- warmup --------------------------------------------------------------------------------
+    # ---- warmup: W steps.  Before them the same W steps, from the same pass index, are repeated on this rank alone until the device has run
+    # them for MIN_WARMUP_S (clocks settle: 256 cornell steps timed right after 8 warm-up steps ran 5 % slow); the timed steps see the same
+    # inputs however often they were repeated ---------------------------------------------------------------------------------------------
     if args.warmup > 0:
+        p0 = r.get_pass_index()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < MIN_WARMUP_S:
+            r.render_async(cam, opt, passes=args.warmup*passes_per_step, stream=stream)
+            torch.cuda.synchronize()
+            r.set_pass_index(p0)
         run(args.warmup)
     sync()
 
-    # ---- timed blocks of exactly K steps, repeated until MIN_TIMED_S ----------------------------
-    first_timed_pass = None
-    blocks, stats_blocks, ktimes = [], None, {}
-    total = 0.0
-    # The kernels' HIP events (two records per launch, on the launch stream) ride in ONE timed block, the LAST: every record is a barrier
-    # packet of a few microseconds, which a small batch (cfg1: 0.32 ms of kernels) feels in every block -- and the first block after the
-    # warm-up runs 10-15 % below the others (clocks), which made its kernel times disagree with rocprofv3's averages of the same command.
-    while True:
-        last = total >= MIN_TIMED_S or len(blocks) >= 1000          # (the block after the time is up: the one with the events)
+    # ---- the timed region: ONE block of exactly K steps --------------------------------------------
+    accum.zero_()
+    r.reset_stats()
+    sync()
+    checked = (r.get_pass_index(), args.steps*passes_per_step)     # (first pass, passes) of the render the validation below re-renders
+    t0 = time.perf_counter()
+    run(args.steps)
+    sync()
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        small_dev = "cuda" if backend == "nccl" else "cpu"
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=small_dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    blocks = [elapsed]
+    st = r.stats()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, reduced[0].cpu().numpy())
+
+    # ---- --full: the kernels' HIP events in a block of their own, after the timed one: every record is a barrier packet of a few
+    # microseconds, which a small batch (cfg1: 0.32 ms of kernels) feels -- the timed region carries none
+    ktimes = {}
+    if args.full:
         accum.zero_()
-        r.reset_stats()
-        r.enable_kernel_timing(last)
+        r.enable_kernel_timing(True)
         sync()
-        if first_timed_pass is None:
-            first_timed_pass = r.get_pass_index()
-        t0 = time.perf_counter()
+        checked = (r.get_pass_index(), args.steps*passes_per_step)
         run(args.steps)
         sync()
-        elapsed = time.perf_counter() - t0
-        if world > 1:
-            small_dev = "cuda" if backend == "nccl" else "cpu"
-            tt = torch.tensor([elapsed], dtype=torch.float64, device=small_dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            elapsed = float(tt.item())
-        blocks.append(elapsed)
-        total += elapsed
-        if stats_blocks is None:
-            stats_blocks = r.stats()
-        if last:
-            ktimes = r.kernel_times()           # of the last timed block's render call
-            break
-    r.enable_kernel_timing(False)
-    elapsed = statistics.median(blocks)
-    st = stats_blocks
+        ktimes = r.kernel_times()
+        r.enable_kernel_timing(False)
 
     # ---- N > 1: the FIXED-WORK leg (north_star's 8-GPU configuration is a fixed job: veach 4K at 4096 spp).  The same K full-frame
     # passes as N = 1, split over the ranks' pixel tiles (K passes over 1/N of the pixels each) + the one reduce; same bracketing.
     strong = None
-    if world > 1:
+    if world > 1 and args.full:
         sblocks, stotal = [], 0.0
         while stotal < MIN_TIMED_S/2 and len(sblocks) < 1000:
             accum.zero_()
             sync()
+            checked = (r.get_pass_index(), args.steps)
             t0 = time.perf_counter()
             run(args.steps, per_step=1)
             sync()
@@ -438,7 +464,7 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
 
     # per-rank view of the run (load balance of the pixel tiles): every rank's samples, rays, kernel time and median block
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = {"rank": rank, "samples": int(st["samples"]), "rays": int(st["rays"]), "kernel_ms": round(sum(v[2] for v in ktimes.values()), 3),
                 "median_block_ms": round(statistics.median(blocks)*1e3, 3), "device": int(local)}
         gathered = [None]*world
@@ -452,8 +478,7 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
     # validation mode only: the reduced image of the N-rank run must equal an unsharded render of the same passes
     if os.environ.get("TINSEL_BENCH_ONE_DEVICE") and world > 1:
         torch.cuda.synchronize()
-        last_passes = args.steps            # (the last render was the fixed-work leg's: K passes)
-        last_first = r.get_pass_index() - last_passes
+        last_first, last_passes = checked   # (the last reduced render: the timed block, the kernel-timing block or a fixed-work block)
         chk = tinsel_amd.create_gpu_renderer(scene, local)
         chk.init(opt.width, opt.height)
         chk.set_pass_index(last_first)
@@ -476,7 +501,7 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
 
     # ---- the API's own call pattern, N = 1 only -------------------------------------------------
     pcie = api_1pass = api_1pass_plain = api_1pass_pinned = None
-    if world == 1 and with_extras and not args.no_api:
+    if world == 1 and with_extras and args.full and not args.no_api:
         # a renderer of its own, with a library-owned accumulator like the C++ shim's (the timed one renders into a torch tensor)
         ra = tinsel_amd.create_gpu_renderer(scene, local)
         ra.init(opt.width, opt.height)
@@ -515,7 +540,7 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
 
     # ---- the opt-in tolerance-arithmetic arm (tinsel_hip_set_arithmetic): rate and distance, N = 1 only ---------
     fast = None
-    if world == 1 and not args.no_fast and args.arith == "exact":
+    if world == 1 and args.full and not args.no_fast and args.arith == "exact":
         try:
             spp = cfg_spp           # the configuration's own spp (north_star's tolerance is quoted per configuration)
             # the distance is per pixel at that spp: where the whole frame at that spp is more than ~4 G samples per arm (veach 4K x 4096) it is
@@ -559,167 +584,185 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
         except Exception as e:
             fast = {"msamples_s": None, "error": str(e)}
 
-    # ---- roofline: every kernel of the block, the dominant one (by time, over ALL kernels) in the headline fields ------------
-    # a kernel's time: (launches, sum of the launches' durations, union of their intervals).  Where a call's two chunks run on two streams
-    # (tinsel_hip.hip render_impl) launches of one kernel overlap: RATES divide by the union ("busy"); the average launch duration is the
-    # sum over the launches, which is what rocprofv3 --stats reports, and `concurrent_launches` = sum / union says how many ran at once
-    gpu_ms = sum(v[2] for v in ktimes.values())
-    dom = max(ktimes.items(), key=lambda kv: kv[1][2], default=(None, (0, 0.0, 0.0)))
-    dom_name, (dom_launches, dom_ms, dom_busy) = dom
-    avg_launch_s = dom_ms*1e-3/max(1, dom_launches)
-    dom_concurrency = (dom_ms/dom_busy) if dom_busy > 0 else 1.0
-    rays = st["rays"]
-    # algorithmic bytes by kernel (SURVEY.md 8d's B_ray split over the kernels that do the work): the mesh walk (Node64 visits + triangle
-    # tests) belongs to k_walk when it runs, the primitive tests and ray/hit records to the scan kernels; path-state streaming (k_shade,
-    # k_lights, k_generate, k_seg) and the framebuffer gather have no algorithmic figure in that model (8d: "an implementation artefact")
-    alg = {"k_bounce": rays*B_ray, "k_mega": rays*B_ray}
-    if "k_walk" in ktimes:
-        alg["k_walk"] = rays*(64.0*I_bar + 48.0*T_bar)
-        alg["k_extend"] = (rays - st["shadow_rays"])*(48.0 + 84.0*P_bar)
-        alg["k_shadow"] = st["shadow_rays"]*(48.0 + 84.0*P_bar)
-    else:
-        alg["k_extend"] = (rays - st["shadow_rays"])*B_ray
-        alg["k_shadow"] = st["shadow_rays"]*B_ray
-    alg["k_accumulate"] = st["samples"]*B_fb
-    job_bytes = rays*B_ray + st["samples"]*B_fb
-    # what a wavefront path tracer with the scene on chip MUST move through HBM: ray in / hit out per ray, the footprint's RMW per sample
-    job_compulsory = rays*48.0 + st["samples"]*B_fb
+    fw = opt.filter.width
+    roofline = None
+    if args.full:
+        # ---- algorithmic-bytes constants of this workload (device counters, untimed; after every render the validation re-renders) ---
+        r.set_detail_counters(True)
+        r.reset_stats()
+        r.render_async(cam, opt, passes=passes_per_step, stream=stream)
+        torch.cuda.synchronize()
+        c = r.stats()
+        r.set_detail_counters(False)
+        rays_c = max(1, c["rays"])
+        I_bar, T_bar, P_bar = c["internal_visits"]/rays_c, c["tri_tests"]/rays_c, c["prim_tests"]/rays_c
+        B_ray = 48.0 + 64.0*I_bar + 48.0*T_bar + 84.0*P_bar
+        # pixels AddSample touches per sample (render.cpp:426-429: [int(x - fw), int(x + fw)] per axis, x uniform in the pixel):
+        # 2 fw + 1 per axis on average away from the frame edge -- 6.25 for the default 0.75 (4..9)
+        K_fp = (2.0*fw + 1.0)**2
+        B_fb = 32.0*K_fp
 
-    pmc = {"sq": None, "fetch": None, "write": None, "tcc": None}
-    if world == 1 and not args.no_pmc and dom_name:
-        for key in ("sq", "fetch", "write", "tcc"):
-            pmc[key] = pmc_pass(args, scene_name, width, height, opt.max_depth, args.steps, PMC_SETS[key])
-    cal = calibrate(pmc)
-    # what a count stands for: calibrated on this run's yard-stick kernels; without them the guide's figures (x2 for wide
-    # coalesced streaming reads, MI355X_MICROARCH.md HBM section; everything else taken at face value) -- and the line says which
-    f_stream = cal["stream_bytes_per_fetch_count"] or 2.0
-    f_gather = cal["gather_bytes_per_fetch_count"] or 1.0
-    f_write = cal["bytes_per_write_count"] or 1.0
+        # ---- roofline: every kernel of the block, the dominant one (by time, over ALL kernels) in the headline fields ------------
+        # a kernel's time: (launches, sum of the launches' durations, union of their intervals).  Where a call's two chunks run on two streams
+        # (tinsel_hip.hip render_impl) launches of one kernel overlap: RATES divide by the union ("busy"); the average launch duration is the
+        # sum over the launches, which is what rocprofv3 --stats reports, and `concurrent_launches` = sum / union says how many ran at once
+        gpu_ms = sum(v[2] for v in ktimes.values())
+        dom = max(ktimes.items(), key=lambda kv: kv[1][2], default=(None, (0, 0.0, 0.0)))
+        dom_name, (dom_launches, dom_ms, dom_busy) = dom
+        avg_launch_s = dom_ms*1e-3/max(1, dom_launches)
+        dom_concurrency = (dom_ms/dom_busy) if dom_busy > 0 else 1.0
+        rays = st["rays"]
+        # algorithmic bytes by kernel (SURVEY.md 8d's B_ray split over the kernels that do the work): the mesh walk (Node64 visits + triangle
+        # tests) belongs to k_walk when it runs, the primitive tests and ray/hit records to the scan kernels; path-state streaming (k_shade,
+        # k_lights, k_generate, k_seg) and the framebuffer gather have no algorithmic figure in that model (8d: "an implementation artefact")
+        alg = {"k_bounce": rays*B_ray, "k_mega": rays*B_ray}
+        if "k_walk" in ktimes:
+            alg["k_walk"] = rays*(64.0*I_bar + 48.0*T_bar)
+            alg["k_extend"] = (rays - st["shadow_rays"])*(48.0 + 84.0*P_bar)
+            alg["k_shadow"] = st["shadow_rays"]*(48.0 + 84.0*P_bar)
+        else:
+            alg["k_extend"] = (rays - st["shadow_rays"])*B_ray
+            alg["k_shadow"] = st["shadow_rays"]*B_ray
+        alg["k_accumulate"] = st["samples"]*B_fb
+        job_bytes = rays*B_ray + st["samples"]*B_fb
+        # what a wavefront path tracer with the scene on chip MUST move through HBM: ray in / hit out per ray, the footprint's RMW per sample
+        job_compulsory = rays*48.0 + st["samples"]*B_fb
 
-    def kernel_traffic(name):
-        """counter bytes per launch of one kernel: FETCH_SIZE / WRITE_SIZE (KB) x the calibrated bytes per count of its access shape"""
-        if not (pmc["fetch"] and pmc["write"] and name in pmc["fetch"] and name in pmc["write"]):
-            return None
-        f, w = pmc["fetch"][name], pmc["write"][name]
-        ff = f_gather if name in GATHER_KERNELS else f_stream
-        return (ff*f["FETCH_SIZE"]/f["launches"] + f_write*w["WRITE_SIZE"]/w["launches"])*1024.0
+        pmc = {"sq": None, "fetch": None, "write": None, "tcc": None}
+        if world == 1 and not args.no_pmc and dom_name:
+            for key in ("sq", "fetch", "write", "tcc"):
+                pmc[key] = pmc_pass(args, scene_name, width, height, opt.max_depth, args.steps, PMC_SETS[key])
+        cal = calibrate(pmc)
+        # what a count stands for: calibrated on this run's yard-stick kernels; without them the guide's figures (x2 for wide
+        # coalesced streaming reads, MI355X_MICROARCH.md HBM section; everything else taken at face value) -- and the line says which
+        f_stream = cal["stream_bytes_per_fetch_count"] or 2.0
+        f_gather = cal["gather_bytes_per_fetch_count"] or 1.0
+        f_write = cal["bytes_per_write_count"] or 1.0
 
-    copy_gbs = YARD[0].get("stream_copy_GBs") if YARD[0] else None
+        def kernel_traffic(name):
+            """counter bytes per launch of one kernel: FETCH_SIZE / WRITE_SIZE (KB) x the calibrated bytes per count of its access shape"""
+            if not (pmc["fetch"] and pmc["write"] and name in pmc["fetch"] and name in pmc["write"]):
+                return None
+            f, w = pmc["fetch"][name], pmc["write"][name]
+            ff = f_gather if name in GATHER_KERNELS else f_stream
+            return (ff*f["FETCH_SIZE"]/f["launches"] + f_write*w["WRITE_SIZE"]/w["launches"])*1024.0
 
-    def kernel_row(name):
-        """one row of roofline.kernels[]: time from the library's HIP events (this block), counters from this run's rocprofv3 passes"""
-        launches, sum_ms, ms = ktimes[name]           # (every rate below is over `ms`, the kernel's busy time)
-        row = {"kernel": name, "launches": launches, "ms": round(ms, 4), "sum_of_launch_ms": round(sum_ms, 4), "share_of_gpu_time": (ms/gpu_ms) if gpu_ms > 0 else None,
-               "frac_model": None, "frac": None, "counter_GB": None, "counter_GBs": None, "frac_hbm_counter": None, "frac_of_stream_copy": None,
-               "algorithmic_GBs": None, "valu_frac_of_issue_peak": None, "valu_lanes_active": None, "wave_cycles_waiting": None, "waves_per_simd": None, "l2_hit_rate": None}
-        t = kernel_traffic(name)
-        if t and ms > 0:
-            row["counter_GB"] = t*launches/1e9
-            row["counter_GBs"] = t*launches/(ms*1e-3)/1e9
-            row["frac_hbm_counter"] = row["counter_GBs"]/HBM_PEAK_GBS
-            if copy_gbs:
-                row["frac_of_stream_copy"] = row["counter_GBs"]/copy_gbs
-        if name in alg and ms > 0:
-            row["algorithmic_GBs"] = alg[name]/(ms*1e-3)/1e9
-        if pmc["sq"] and name in pmc["sq"]:
-            q = pmc["sq"][name]
-            iv = q.get("SQ_INSTS_VALU", 0.0)
-            if iv and ms > 0:
-                # (the profiled pass launches what the timed block launches: per-launch counts x this block's launches / this block's time)
-                row["valu_frac_of_issue_peak"] = iv/q["launches"]*launches/(ms*1e-3)/VALU_PEAK
-                row["valu_lanes_active"] = q.get("SQ_THREAD_CYCLES_VALU", 0.0)/(64.0*iv)
-            if q.get("SQ_WAVE_CYCLES"):
-                row["wave_cycles_waiting"] = q.get("SQ_WAIT_ANY", 0.0)/q["SQ_WAVE_CYCLES"]
-                if q.get("GRBM_GUI_ACTIVE"):
-                    row["waves_per_simd"] = 4.0*q["SQ_WAVE_CYCLES"]/(q["GRBM_GUI_ACTIVE"]/8.0*SIMDS)
-        if pmc["tcc"] and name in pmc["tcc"]:
-            q = pmc["tcc"][name]
-            if q.get("TCC_HIT_sum", 0.0) + q.get("TCC_MISS_sum", 0.0) > 0:
-                row["l2_hit_rate"] = q["TCC_HIT_sum"]/(q["TCC_HIT_sum"] + q["TCC_MISS_sum"])
-        # which model the kernel's `frac` comes from: instruction issue where the scene never leaves the CU, else HBM bytes (counter
-        # bytes when this run measured them, the algorithmic figure otherwise)
-        if name in LDS_SCENE_KERNELS:
-            row["frac_model"], row["frac"] = "valu_issue", row["valu_frac_of_issue_peak"]
-        elif row["frac_hbm_counter"] is not None:
-            row["frac_model"], row["frac"] = "hbm_counter", row["frac_hbm_counter"]
-        elif row["algorithmic_GBs"] is not None:
-            row["frac_model"], row["frac"] = "hbm_algorithmic", row["algorithmic_GBs"]/HBM_PEAK_GBS
-        return row
+        copy_gbs = YARD[0].get("stream_copy_GBs") if YARD[0] else None
 
-    kernels = sorted((kernel_row(k) for k in ktimes), key=lambda r: -r["ms"])
-    drow = kernels[0] if kernels else {}
-    traffic = kernel_traffic(dom_name) if dom_name else None
-    alg_gbs = drow.get("algorithmic_GBs") or 0.0
-    valu_per_launch = None
-    if pmc["sq"] and dom_name in pmc["sq"] and pmc["sq"][dom_name].get("SQ_INSTS_VALU"):
-        valu_per_launch = pmc["sq"][dom_name]["SQ_INSTS_VALU"]/pmc["sq"][dom_name]["launches"]
-    counter_job = sum(r["counter_GB"] for r in kernels if r["counter_GB"]) if any(r["counter_GB"] for r in kernels) else None
+        def kernel_row(name):
+            """one row of roofline.kernels[]: time from the library's HIP events (this block), counters from this run's rocprofv3 passes"""
+            launches, sum_ms, ms = ktimes[name]           # (every rate below is over `ms`, the kernel's busy time)
+            row = {"kernel": name, "launches": launches, "ms": round(ms, 4), "sum_of_launch_ms": round(sum_ms, 4), "share_of_gpu_time": (ms/gpu_ms) if gpu_ms > 0 else None,
+                   "frac_model": None, "frac": None, "counter_GB": None, "counter_GBs": None, "frac_hbm_counter": None, "frac_of_stream_copy": None,
+                   "algorithmic_GBs": None, "valu_frac_of_issue_peak": None, "valu_lanes_active": None, "wave_cycles_waiting": None, "waves_per_simd": None, "l2_hit_rate": None}
+            t = kernel_traffic(name)
+            if t and ms > 0:
+                row["counter_GB"] = t*launches/1e9
+                row["counter_GBs"] = t*launches/(ms*1e-3)/1e9
+                row["frac_hbm_counter"] = row["counter_GBs"]/HBM_PEAK_GBS
+                if copy_gbs:
+                    row["frac_of_stream_copy"] = row["counter_GBs"]/copy_gbs
+            if name in alg and ms > 0:
+                row["algorithmic_GBs"] = alg[name]/(ms*1e-3)/1e9
+            if pmc["sq"] and name in pmc["sq"]:
+                q = pmc["sq"][name]
+                iv = q.get("SQ_INSTS_VALU", 0.0)
+                if iv and ms > 0:
+                    # (the profiled pass launches what the timed block launches: per-launch counts x this block's launches / this block's time)
+                    row["valu_frac_of_issue_peak"] = iv/q["launches"]*launches/(ms*1e-3)/VALU_PEAK
+                    row["valu_lanes_active"] = q.get("SQ_THREAD_CYCLES_VALU", 0.0)/(64.0*iv)
+                if q.get("SQ_WAVE_CYCLES"):
+                    row["wave_cycles_waiting"] = q.get("SQ_WAIT_ANY", 0.0)/q["SQ_WAVE_CYCLES"]
+                    if q.get("GRBM_GUI_ACTIVE"):
+                        row["waves_per_simd"] = 4.0*q["SQ_WAVE_CYCLES"]/(q["GRBM_GUI_ACTIVE"]/8.0*SIMDS)
+            if pmc["tcc"] and name in pmc["tcc"]:
+                q = pmc["tcc"][name]
+                if q.get("TCC_HIT_sum", 0.0) + q.get("TCC_MISS_sum", 0.0) > 0:
+                    row["l2_hit_rate"] = q["TCC_HIT_sum"]/(q["TCC_HIT_sum"] + q["TCC_MISS_sum"])
+            # which model the kernel's `frac` comes from: instruction issue where the scene never leaves the CU, else HBM bytes (counter
+            # bytes when this run measured them, the algorithmic figure otherwise)
+            if name in LDS_SCENE_KERNELS:
+                row["frac_model"], row["frac"] = "valu_issue", row["valu_frac_of_issue_peak"]
+            elif row["frac_hbm_counter"] is not None:
+                row["frac_model"], row["frac"] = "hbm_counter", row["frac_hbm_counter"]
+            elif row["algorithmic_GBs"] is not None:
+                row["frac_model"], row["frac"] = "hbm_algorithmic", row["algorithmic_GBs"]/HBM_PEAK_GBS
+            return row
 
-    common = {
-        "kernel": dom_name, "launches": dom_launches, "avg_launch_ms": avg_launch_s*1e3, "concurrent_launches": dom_concurrency, "traffic": traffic,
-        "frac_model": drow.get("frac_model"),
-        "algorithmic_GBs": drow.get("algorithmic_GBs"), "frac_hbm_algorithmic": (alg_gbs/HBM_PEAK_GBS) if alg_gbs else None,
-        # SURVEY.md 8(d)'s own number, as written there: (rays x B_ray + samples x B_fb) / seconds / 8e12 over the TIMED step (the driver's
-        # clock, not the kernel's).  Above 1 wherever the scene is on chip: the model bills every node / primitive fetch to HBM (DESIGN.md 7)
-        "frac_survey_8d": job_bytes/elapsed/(HBM_PEAK_GBS*1e9) if elapsed > 0 else None,
-        # what the job MUST move through HBM with the scene on chip (48 B per ray + the footprint's RMW per sample) over the same seconds
-        "frac_hbm_compulsory": job_compulsory/elapsed/(HBM_PEAK_GBS*1e9) if elapsed > 0 else None,
-        # issue utilisation x lanes active: the share of the chip's peak LANE-operations per second the dominant kernel's instructions use
-        # (every issued instruction still counts as useful: the parity arm's IEEE divide / sqrt expansions are in it)
-        "useful_frac": (drow.get("valu_frac_of_issue_peak")*drow.get("valu_lanes_active")) if (drow.get("valu_frac_of_issue_peak") and drow.get("valu_lanes_active")) else None,
-        "valu_frac_of_issue_peak": drow.get("valu_frac_of_issue_peak"),
-        "counter_GBs": drow.get("counter_GBs"), "frac_hbm_counter": drow.get("frac_hbm_counter"),
-        "l2_hit_rate": drow.get("l2_hit_rate"),
-        "valu_wave_insts_per_launch": valu_per_launch, "valu_lanes_active": drow.get("valu_lanes_active"), "wave_cycles_waiting": drow.get("wave_cycles_waiting"),
-        "waves_per_simd": drow.get("waves_per_simd"),
-        "B_ray": B_ray, "I": I_bar, "T": T_bar, "P": P_bar, "B_fb": B_fb, "K_fp": K_fp,
-        "job_algorithmic_GBs": job_bytes/(gpu_ms*1e-3)/1e9 if gpu_ms > 0 else 0.0,
-        # the job as a whole: HBM bytes the counters saw over what it must move with the scene on chip (48 B per ray + the footprint per sample)
-        "job_counter_GB": counter_job, "job_compulsory_GB": job_compulsory/1e9,
-        "job_counter_over_compulsory": (counter_job*1e9/job_compulsory) if (counter_job and job_compulsory > 0) else None,
-        "kernels": kernels,
-        "kernel_ms": {k: round(v[2], 3) for k, v in ktimes.items()},
-        "kernel_traffic_GB": {r["kernel"]: (round(r["counter_GB"], 3) if r["counter_GB"] else None) for r in kernels} if any(pmc.values()) else None,
-        "counter_calibration": dict(cal, source=("k_ub_copy / k_ub_gather<0> in the same rocprofv3 passes" if any(cal.values()) else
-                                                 "none measured: FETCH_SIZE x2 on streaming kernels (the guide), x1 elsewhere"),
-                                    gather_kernels=list(GATHER_KERNELS)),
-        "counters": "rocprofv3 --pmc passes of this run (same workload, same passes per launch)" if any(pmc.values()) else None,
-    }
-    if copy_gbs:
-        common["stream_copy_GBs"] = copy_gbs
-        common["frac_of_stream_copy"] = drow.get("frac_of_stream_copy")
-    # (only where k_walk is the dominant kernel: there it does ALL the mesh visits the device counters I, T count -- config 3; in a scene
-    # that also walks small meshes inline, glass, the per-ray constants are not k_walk's alone)
-    wrow = next((r for r in kernels if r["kernel"] == "k_walk"), None) if dom_name == "k_walk" else None
-    if wrow and wrow["ms"] > 0:
-        # what the walk is made of: Node64 visits (and triangle tests) per second, next to the record-chase rates this GPU
-        # sustains on a table of the tree's size and on one that fits an XCD's L2 (tinsel_hip_ubench, this run)
-        walk = {"node_visits_G_s": rays*I_bar/(wrow["ms"]*1e-3)/1e9, "triangle_tests_G_s": rays*T_bar/(wrow["ms"]*1e-3)/1e9}
-        if YARD[0]:
-            walk["record_chase_ceilings_G_s"] = {k: YARD[0].get(k) for k in ("gather_beyond_cache_Grecords_s", "gather_tree_sized_Grecords_s", "gather_l2_resident_Grecords_s")}
-            # records per second (a 48-B triangle = 0.75 of a 64-B record) against the two ceilings: above the first (the tree top in
-            # LDS and the L2 serve most visits), below the second (what a CU's vector-memory front end retires from L2)
-            recs = walk["node_visits_G_s"] + 0.75*walk["triangle_tests_G_s"]
-            if YARD[0].get("gather_tree_sized_Grecords_s"):
-                walk["frac_of_tree_sized_chase"] = recs/YARD[0]["gather_tree_sized_Grecords_s"]
-            if YARD[0].get("gather_l2_resident_Grecords_s"):
-                walk["frac_of_l2_resident_chase"] = recs/YARD[0]["gather_l2_resident_Grecords_s"]
-        common.update(walk)         # (flat, as before) ...
-        common["k_walk"] = walk     # ... and under the kernel's name, whichever kernel is the dominant one
-    if drow.get("frac_model") == "valu_issue":
-        # the scene never leaves the CU: the HBM model counts bytes that are LDS reads.  What binds is instruction issue.
-        # (per-launch instructions / average launch duration x the launches that ran at once = all of them / the kernel's busy time)
-        ach = (valu_per_launch*dom_concurrency/avg_launch_s/1e9) if (valu_per_launch and avg_launch_s > 0) else None
-        roofline = dict({"bound": "valu", "achieved": ach, "peak": VALU_PEAK/1e9, "unit": "G wave-instructions/s",
-                         "frac": (ach/(VALU_PEAK/1e9)) if ach else None}, **common)
-    else:
-        # counter bytes when this run measured them, else the algorithmic figure (never a stored constant)
-        ach = common["counter_GBs"] if common["counter_GBs"] else alg_gbs
-        roofline = dict({"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (ach/HBM_PEAK_GBS) if ach else None,
-                         "achieved_is": "counter bytes (calibrated)" if common["counter_GBs"] else "algorithmic bytes"}, **common)
+        kernels = sorted((kernel_row(k) for k in ktimes), key=lambda r: -r["ms"])
+        drow = kernels[0] if kernels else {}
+        traffic = kernel_traffic(dom_name) if dom_name else None
+        alg_gbs = drow.get("algorithmic_GBs") or 0.0
+        valu_per_launch = None
+        if pmc["sq"] and dom_name in pmc["sq"] and pmc["sq"][dom_name].get("SQ_INSTS_VALU"):
+            valu_per_launch = pmc["sq"][dom_name]["SQ_INSTS_VALU"]/pmc["sq"][dom_name]["launches"]
+        counter_job = sum(r["counter_GB"] for r in kernels if r["counter_GB"]) if any(r["counter_GB"] for r in kernels) else None
+
+        common = {
+            "kernel": dom_name, "launches": dom_launches, "avg_launch_ms": avg_launch_s*1e3, "concurrent_launches": dom_concurrency, "traffic": traffic,
+            "frac_model": drow.get("frac_model"),
+            "algorithmic_GBs": drow.get("algorithmic_GBs"), "frac_hbm_algorithmic": (alg_gbs/HBM_PEAK_GBS) if alg_gbs else None,
+            # SURVEY.md 8(d)'s own number, as written there: (rays x B_ray + samples x B_fb) / seconds / 8e12 over the TIMED step (the driver's
+            # clock, not the kernel's).  Above 1 wherever the scene is on chip: the model bills every node / primitive fetch to HBM (DESIGN.md 7)
+            "frac_survey_8d": job_bytes/elapsed/(HBM_PEAK_GBS*1e9) if elapsed > 0 else None,
+            # what the job MUST move through HBM with the scene on chip (48 B per ray + the footprint's RMW per sample) over the same seconds
+            "frac_hbm_compulsory": job_compulsory/elapsed/(HBM_PEAK_GBS*1e9) if elapsed > 0 else None,
+            # issue utilisation x lanes active: the share of the chip's peak LANE-operations per second the dominant kernel's instructions use
+            # (every issued instruction still counts as useful: the parity arm's IEEE divide / sqrt expansions are in it)
+            "useful_frac": (drow.get("valu_frac_of_issue_peak")*drow.get("valu_lanes_active")) if (drow.get("valu_frac_of_issue_peak") and drow.get("valu_lanes_active")) else None,
+            "valu_frac_of_issue_peak": drow.get("valu_frac_of_issue_peak"),
+            "counter_GBs": drow.get("counter_GBs"), "frac_hbm_counter": drow.get("frac_hbm_counter"),
+            "l2_hit_rate": drow.get("l2_hit_rate"),
+            "valu_wave_insts_per_launch": valu_per_launch, "valu_lanes_active": drow.get("valu_lanes_active"), "wave_cycles_waiting": drow.get("wave_cycles_waiting"),
+            "waves_per_simd": drow.get("waves_per_simd"),
+            "B_ray": B_ray, "I": I_bar, "T": T_bar, "P": P_bar, "B_fb": B_fb, "K_fp": K_fp,
+            "job_algorithmic_GBs": job_bytes/(gpu_ms*1e-3)/1e9 if gpu_ms > 0 else 0.0,
+            # the job as a whole: HBM bytes the counters saw over what it must move with the scene on chip (48 B per ray + the footprint per sample)
+            "job_counter_GB": counter_job, "job_compulsory_GB": job_compulsory/1e9,
+            "job_counter_over_compulsory": (counter_job*1e9/job_compulsory) if (counter_job and job_compulsory > 0) else None,
+            "kernels": kernels,
+            "kernel_ms": {k: round(v[2], 3) for k, v in ktimes.items()},
+            "kernel_traffic_GB": {r["kernel"]: (round(r["counter_GB"], 3) if r["counter_GB"] else None) for r in kernels} if any(pmc.values()) else None,
+            "counter_calibration": dict(cal, source=("k_ub_copy / k_ub_gather<0> in the same rocprofv3 passes" if any(cal.values()) else
+                                                     "none measured: FETCH_SIZE x2 on streaming kernels (the guide), x1 elsewhere"),
+                                        gather_kernels=list(GATHER_KERNELS)),
+            "counters": "rocprofv3 --pmc passes of this run (same workload, same passes per launch)" if any(pmc.values()) else None,
+        }
+        if copy_gbs:
+            common["stream_copy_GBs"] = copy_gbs
+            common["frac_of_stream_copy"] = drow.get("frac_of_stream_copy")
+        # (only where k_walk is the dominant kernel: there it does ALL the mesh visits the device counters I, T count -- config 3; in a scene
+        # that also walks small meshes inline, glass, the per-ray constants are not k_walk's alone)
+        wrow = next((r for r in kernels if r["kernel"] == "k_walk"), None) if dom_name == "k_walk" else None
+        if wrow and wrow["ms"] > 0:
+            # what the walk is made of: Node64 visits (and triangle tests) per second, next to the record-chase rates this GPU
+            # sustains on a table of the tree's size and on one that fits an XCD's L2 (tinsel_hip_ubench, this run)
+            walk = {"node_visits_G_s": rays*I_bar/(wrow["ms"]*1e-3)/1e9, "triangle_tests_G_s": rays*T_bar/(wrow["ms"]*1e-3)/1e9}
+            if YARD[0]:
+                walk["record_chase_ceilings_G_s"] = {k: YARD[0].get(k) for k in ("gather_beyond_cache_Grecords_s", "gather_tree_sized_Grecords_s", "gather_l2_resident_Grecords_s")}
+                # records per second (a 48-B triangle = 0.75 of a 64-B record) against the two ceilings: above the first (the tree top in
+                # LDS and the L2 serve most visits), below the second (what a CU's vector-memory front end retires from L2)
+                recs = walk["node_visits_G_s"] + 0.75*walk["triangle_tests_G_s"]
+                if YARD[0].get("gather_tree_sized_Grecords_s"):
+                    walk["frac_of_tree_sized_chase"] = recs/YARD[0]["gather_tree_sized_Grecords_s"]
+                if YARD[0].get("gather_l2_resident_Grecords_s"):
+                    walk["frac_of_l2_resident_chase"] = recs/YARD[0]["gather_l2_resident_Grecords_s"]
+            common.update(walk)         # (flat, as before) ...
+            common["k_walk"] = walk     # ... and under the kernel's name, whichever kernel is the dominant one
+        if drow.get("frac_model") == "valu_issue":
+            # the scene never leaves the CU: the HBM model counts bytes that are LDS reads.  What binds is instruction issue.
+            # (per-launch instructions / average launch duration x the launches that ran at once = all of them / the kernel's busy time)
+            ach = (valu_per_launch*dom_concurrency/avg_launch_s/1e9) if (valu_per_launch and avg_launch_s > 0) else None
+            roofline = dict({"bound": "valu", "achieved": ach, "peak": VALU_PEAK/1e9, "unit": "G wave-instructions/s",
+                             "frac": (ach/(VALU_PEAK/1e9)) if ach else None}, **common)
+        else:
+            # counter bytes when this run measured them, else the algorithmic figure (never a stored constant)
+            ach = common["counter_GBs"] if common["counter_GBs"] else alg_gbs
+            roofline = dict({"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (ach/HBM_PEAK_GBS) if ach else None,
+                             "achieved_is": "counter bytes (calibrated)" if common["counter_GBs"] else "algorithmic bytes"}, **common)
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:        # the CPU leg is timed at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:        # the CPU leg is timed at N = 1 only
         try:
             cpu = cpu_baseline(scene_name, cam, opt, args.cpu_seconds)
         except Exception as e:      # a checker built for another box must not kill the bench line
@@ -730,16 +773,16 @@ def run_config(args, scene_name, width, height, maxdepth, rank, world, local, di
         "metric": "Msamples/s (%s.tin %dx%d maxDepth=%d spp=%d, wavefront path; Mrays/s alongside)" % (
             scene_name, opt.width, opt.height, opt.max_depth, args.steps*passes_per_step),
         "value": msamples, "unit": "Msamples/s", "ms_per_step": elapsed*1e3/args.steps,
-        "timed_blocks": len(blocks), "timed_seconds": total, "block_ms_min_median_max": [min(blocks)*1e3, elapsed*1e3, max(blocks)*1e3],
+        "timed_blocks": len(blocks), "timed_seconds": elapsed, "block_ms_min_median_max": [min(blocks)*1e3, elapsed*1e3, max(blocks)*1e3],
         "config": {"workload": "%s.tin %dx%d maxDepth=%d, %d pass(es) per step, pipeline=%s" % (
             scene_name, opt.width, opt.height, opt.max_depth, passes_per_step,
-            args.pipeline if args.pipeline != "auto" else "auto->" + ("wavefront(fused)" if "k_bounce" in ktimes else "wavefront(%s%s)" % ("paired" if "k_step" in ktimes else "split", "+k_walk" if "k_walk" in ktimes else ""))),
+            args.pipeline if args.pipeline != "auto" or not ktimes else "auto->" + ("wavefront(fused)" if "k_bounce" in ktimes else "wavefront(%s%s)" % ("paired" if "k_step" in ktimes else "split", "+k_walk" if "k_walk" in ktimes else ""))),
             "scene_pack": os.path.relpath(pack, ROOT), "parallelism": "pixel-tile shard x%d + RCCL reduce" % world if world > 1 else "1 GPU",
             "filter": "gaussian w=%.2f" % fw, "rays_per_sample": tot_rays/max(1.0, tot_samples),
             "mesh_bvh": args.bvh, "mesh_bvh_build_ms": bvh_build_ms, "russian_roulette_from_bounce": args.roulette},
         "mrays_per_s": tot_rays/elapsed/1e6,
         "shadow_ray_fraction": tot_shadow/max(1.0, tot_rays),
-        "gpu_kernel_ms_total": gpu_ms,
+        "gpu_kernel_ms_total": sum(v[2] for v in ktimes.values()) if ktimes else None,
         "pcie_inclusive_msamples_s": pcie,
         "api_1pass_msamples_s": api_1pass,
         "api_1pass_plain_msamples_s": api_1pass_plain,
@@ -1016,7 +1059,7 @@ def main():
         local = 0
     torch.cuda.set_device(local)
     default_headline = (args.scene, args.width, args.height) == ("cornell", 1024, 1024)
-    if world == 1 and not args.no_ubench:
+    if world == 1 and args.full and not args.no_ubench:
         YARD[0] = yard_sticks()
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -1038,7 +1081,7 @@ def main():
             raise SystemExit("bench.py: the first all-reduce over %d ranks summed to %d" % (world, int(hello.item())))
 
     head = run_config(args, args.scene, args.width, args.height, args.maxdepth, rank, world, local, dist, backend, torch, with_extras=True,
-                      cfg_spp=CONFIG_SPP.get(args.scene, 256))
+                      cfg_spp=CONFIG_SPP.get(args.scene, 256), dump_dir=args.dump_outputs)
     if head is not None:
         head["baseline_config"] = BASELINE_INDEX.get(args.scene) if default_headline else None
 
@@ -1055,7 +1098,7 @@ def main():
                 raise           # (a rank that leaves a collective sequence would hang the others: fail the run loudly instead)
             more.append({"config": {"workload": what}, "unavailable": "failed: %s" % e})
 
-    if world == 1 and default_headline and not args.no_second_config:
+    if world == 1 and args.full and default_headline and not args.no_second_config:
         # BASELINE configs[2]: the scene that lives in HBM
         what = "ajax stand-in (524,288 triangles) 1920x1080 maxDepth=4"
         if os.path.exists(os.path.join(ROOT, "tests", "golden", LARGE + ".pack")):
@@ -1066,7 +1109,7 @@ def main():
         # ... and with a REAL scanned mesh in the stand-in's place (SURVEY.md 0.1's other option): an irregular SAH tree
         if os.path.exists(os.path.join(ROOT, "tests", "golden", REAL_MESH + ".pack")):
             another(REAL_MESH, 1920, 1080, 4, "ajax.tin + Aphrodite scan (427,384 triangles) 1920x1080 maxDepth=4")
-    if default_headline and not args.no_more_configs:
+    if args.full and default_headline and not args.no_more_configs:
         if world == 1:
             another("glass", 1920, 1080, 12, "glass.tin 1920x1080 maxDepth=12")     # BASELINE configs[3]
         # BASELINE configs[4], north_star's multi-GPU configuration: at N > 1 the ranks' pixel tiles of the 4K frame, weak and fixed-work
@@ -1081,14 +1124,15 @@ def main():
     # N > 1, rank 0, AFTER the ranks' timed regions (the other ranks have left): the same N devices through the library's own multi-GPU
     # path (tinsel_hip_group: thread per device, one ncclReduce per read-back) in child processes with a 60 s limit each
     group = group5 = None
-    if world > 1 and not args.no_group_leg:
+    if world > 1 and args.full and not args.no_group_leg:
         group = group_leg(args, world)
         if default_headline and not args.no_more_configs:
             group5 = group_leg(args, world, "veach", 3840, 2160, 0)
 
-    detail = dict(head, n_gpus=world, steps=args.steps, warmup=args.warmup, yard_sticks=YARD[0], group=group, group_cfg5=group5, configs=more)
     line = contract_line(args, world, head, more, group, group5, detail_file=None)
-    line["detail"] = write_detail(detail)
+    if args.full:
+        detail = dict(head, n_gpus=world, steps=args.steps, warmup=args.warmup, yard_sticks=YARD[0], group=group, group_cfg5=group5, configs=more)
+        line["detail"] = write_detail(detail)
     print(json.dumps(line), flush=True)
 
 

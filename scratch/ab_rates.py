@@ -43,7 +43,7 @@ def one(lib, work, steps):
             path = part
     lib = path
     env = dict(os.environ, TINSEL_HIP_LIB=lib) if lib else dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "5", "--no-pmc", "--no-fast", "--no-api", "--no-ubench",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "5", "--full", "--no-pmc", "--no-fast", "--no-api", "--no-ubench",
            "--no-cpu-baseline", "--no-second-config", "--no-more-configs"] + WORK[work] + (["--tuning", tuning] if tuning else []) + extra
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     if p.returncode != 0:

@@ -3,7 +3,7 @@
 # per-kernel counters of every configuration, k_walk's section profile, the animation's per-frame cost, the spread over fresh processes
 O=gpurun_out/r6z6; mkdir -p $O
 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -4 $O/pytest_gpu.log
-( time python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; cp bench_detail.json $O/bench_detail.json
+( time python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; cp bench_detail.json $O/bench_detail.json
 python scratch/roofline_table.py $O/bench_detail.json > $O/roofline_inputs.md
 ( cd /tmp; export TMPDIR=/tmp; timeout 400 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/stats -o s -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-fast --no-api --no-ubench > $GRAFT_REPO_ROOT/$O/bench_under_stats.json 2> /dev/null )
 DB=$(find $O/stats -name "*.db" | head -1); [ -n "$DB" ] && python scratch/rocprof_summary.py $DB > $O/kernel_stats.md; rm -rf $O/stats

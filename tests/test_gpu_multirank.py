@@ -18,7 +18,7 @@ def test_two_ranks_on_one_device():
     env = dict(os.environ, TINSEL_BENCH_BACKEND="gloo", TINSEL_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "8", "--warmup", "1", "--width", "512", "--height", "384"],
+                        "--gpus", "2", "--steps", "8", "--warmup", "1", "--width", "512", "--height", "384", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert "validation: 2-rank reduced image vs unsharded render" in p.stderr and ": ok" in p.stderr, p.stderr[-2000:]
@@ -52,7 +52,7 @@ def test_plain_launch_starts_the_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TINSEL_BENCH_BACKEND="gloo", TINSEL_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--width", "256", "--height", "256",
-                        "--no-group-leg"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--no-group-leg", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert "starting 2 ranks" in p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
