@@ -75,17 +75,8 @@ TN_D void pool_load(const uint32_t* pool, uint32_t e, PathRegs& p, uint32_t& slo
 #define TN_PROF_FLUSH if (lane_id() == 0) { for (int k = 0; k < 6; ++k) atomicAdd(q.stats + (size_t)(blockIdx.x % kStatShards)*kStatWords + 2 + k, (unsigned long long)prof[k]); } if (true) return;
 #else
 #define TN_TICK(k)
-#ifdef TN_PROFILE_TRACE
-#define TN_PROF_DECL TraceCounters ctrN = { 0, 0, 0 };
-#define TN_CTR_NEE ctrN
-#define TN_PROF_FLUSH if (lane_id() == 0) { for (int k = 0; k < 6; ++k) atomicAdd(q.stats + (size_t)(blockIdx.x % kStatShards)*kStatWords + 2 + k, (unsigned long long)(TN_PROFILE_TRACE == 2 ? ctrN.cyc[k] : ctr.cyc[k])); } if (true) return;
-#else
 #define TN_PROF_DECL
 #define TN_PROF_FLUSH
-#endif
-#endif
-#ifndef TN_CTR_NEE
-#define TN_CTR_NEE ctr
 #endif
 
 // The launch covers the bounces [bounceBegin, bounceEnd).  A path never leaves its region and a region belongs to one wave (one
@@ -99,7 +90,7 @@ TN_D void pool_load(const uint32_t* pool, uint32_t e, PathRegs& p, uint32_t& slo
 // dozen instructions at each end of a round).  As plain arguments they sat in SGPRs -- or in the VGPR lanes SGPRs spill to, and the
 // VGPRs those displace in scratch -- through every bounce: 340 -> 131 v_readlane, scratch 268 -> 216 B in cornell's variant; cornell
 // 4297 -> 4404 Msamples/s at 20 passes, veach 4K 2813 -> 2902, gloss 11 062 -> 11 838, env_loft 5537 -> 5753, a 1 M-path batch 2782 -> 2881
-// (profiles/r04_r_ab_late_kernargs.md; -DTN_LATE_CAMERA=0 -DTN_LATE_SKY=0 -DTN_LATE_STATE=0: the plain arm)
+// (profiles/r04_r_ab_late_kernargs.md)
 // k_bounce's kernel arguments: ONE struct, passed by value as the kernel's only parameter -- so the kernel-argument segment IS this struct
 // and the offsetof() of the late reads below cannot drift from what the launch lays out (the struct used to mirror a parameter
 // list by hand).
@@ -341,7 +332,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                             TN_TICK(2)
                             float ts;
                             V3 nn;
-                            const int hp = trace<SceneT<LDS, false, DEFER ? 1 : 0>, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, TN_CTR_NEE);
+                            const int hp = trace<SceneT<LDS, false, DEFER ? 1 : 0>, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, ctr);
                             TN_TICK(3)
                             rays++;
                             shadowRays++;
@@ -391,7 +382,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
 
     wave_add_stat(q.stats, 0, rays);
     wave_add_stat(q.stats, 1, samples);
-#if !defined(TN_PROFILE_SECTIONS) && !defined(TN_PROFILE_TRACE)
+#ifndef TN_PROFILE_SECTIONS
     wave_add_stat(q.stats, 5, shadowRays);
 #endif
     TN_PROF_FLUSH

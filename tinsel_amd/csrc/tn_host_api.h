@@ -1064,7 +1064,7 @@ int tinsel_hip_selftest_arith(int device_index, int op, int variant, unsigned lo
     if (!out_counts || !out_first_bad || op < 0 || op > 2)
         return fail("selftest_arith: bad arguments");
     if (variant < 0)
-        variant = op == 0 ? TN_RCP_VARIANT : op == 1 ? TN_SQRT_VARIANT : TN_RSQRT_VARIANT;      // what this library is built with
+        variant = op == 0 ? kRcpVariant : op == 1 ? kSqrtVariant : kRsqrtVariant;      // what this library is built with
     HIP_TRY(hipSetDevice(device_index));
     unsigned long long* counts = nullptr;
     uint32_t* first = nullptr;

@@ -150,7 +150,6 @@ TN_D void primitive_sample(const SC& sc, int index, float time, V3& pos, V3& nor
         const float* nr;
         int tri;
         float r = rng.randf();
-#if TN_QUAD_RECORD
         if (p.flags & kPrimQuadArena)
         {
             // a quad in the arena (tn_isect.h): its arrays through the offsets in the record; LowerBound over two entries written down
@@ -164,7 +163,6 @@ TN_D void primitive_sample(const SC& sc, int index, float time, V3& pos, V3& nor
             nr = reinterpret_cast<const float*>(base + q.normals);
         }
         else
-#endif
         {
         const DevMesh m = sc.meshes[p.mesh];
         const float* mcdf = mesh_cdf(sc, m);
@@ -306,38 +304,18 @@ TN_D V3 nee_contrib_probe(const Mat& surf, const HitCtx& h, V3 wi, V3 skyColor, 
     return L;
 }
 
-// One fetch per light in the light loops (LightRec, tn_scene.h) -- the parity arm only: cornell +0.3-0.8 % there, while the tolerance arm's k_bounce
-// loses its register allocation to it (56 VGPRs spilled: cornell 7147 -> 5812 Msamples/s, profiles/r06_2t_ab_fast_arm.md)
-#ifndef TN_LIGHT_RECS
-#ifdef TN_FAST
-#define TN_LIGHT_RECS 0
-#else
-#define TN_LIGHT_RECS 1
-#endif
-#endif
+// The light loops read a light's primitive from sc.lights and its sample count and 1/count from that primitive's material, in both arithmetic
+// arms.  Reading all three from the one 16-B LightRec measured cornell +0.3-0.8 % in the parity arm but spills 56 VGPRs in the tolerance arm's
+// k_bounce (cornell 7147 -> 5812 Msamples/s, profiles/r06_2t_ab_fast_arm.md); neither shipped build compiled that form.
 // Which light does NEE ray k belong to?  Rays arrive in order (probe first, then lights x samples): the cursor walks along.
 struct LightCursor
 {
     int li = 0, sInLight = 0;
     TN_D int next(const DevScene& sc)
     {
-#if TN_LIGHT_RECS
-        for (;;)
-        {
-            const int4 e = *reinterpret_cast<const int4*>(sc.lights + li);      // {primitive, lightSamples, ..}: one fetch
-            if (sInLight < e.y)
-            {
-                ++sInLight;
-                return e.x;
-            }
-            ++li;
-            sInLight = 0;
-        }
-#else
         while (sInLight >= sc.mats[sc.lights[li].prim].lightSamples) { ++li; sInLight = 0; }
         ++sInLight;
         return sc.lights[li].prim;
-#endif
     }
 };
 
@@ -355,21 +333,11 @@ TN_D V3 nee_sum(const DevScene& sc, Contrib contrib)
     }
     for (int li = 0; li < sc.numLights; ++li)
     {
-#if TN_LIGHT_RECS
-        const int4 e = *reinterpret_cast<const int4*>(sc.lights + li);
-        const int numSamples = e.y;
-        const float rcpSamples = __int_as_float(e.z);
-#else
         const int numSamples = sc.mats[sc.lights[li].prim].lightSamples;
-#endif
         V3 L(0.0f);
         for (int s = 0; s < numSamples; ++s)
             L = L + contrib(k++);
-#if TN_LIGHT_RECS
-        sum = sum + L*rcpSamples;                                       // L*(1.0f/numSamples), render.cpp:223: divided on the host
-#else
-        sum = sum + L*sc.mats[sc.lights[li].prim].rcpLightSamples;
-#endif
+        sum = sum + L*sc.mats[sc.lights[li].prim].rcpLightSamples;     // L*(1.0f/numSamples), render.cpp:223: divided on the host
     }
     return sum;
 }

@@ -11,17 +11,6 @@
 
 namespace tn {
 
-// A/B arms of the flat scan's fetch order (trace_flat, prim_intersect below); every setting gives the same results
-#ifndef TN_SCAN_MASK
-#define TN_SCAN_MASK 1
-#endif
-#ifndef TN_QUAD_RECORD
-#define TN_QUAD_RECORD 1
-#endif
-#ifndef TN_SCAN_AHEAD
-#define TN_SCAN_AHEAD 1
-#endif
-
 // Per-lane traversal stack living in LDS as stack[entry][lane] (conflict-free: consecutive
 // lanes hit consecutive banks).  `base` already points at this lane's column.
 template <int STRIDE>
@@ -37,19 +26,7 @@ struct TraceCounters
     uint32_t internal;      // Node64 records visited (= internal BVH nodes, both levels)
     uint32_t tris;          // triangle tests
     uint32_t prims;         // PrimitiveIntersect calls
-#ifdef TN_PROFILE_TRACE
-    uint32_t cyc[6];        // dev-only: s_memtime deltas of trace_flat by section (boxes, plane, sphere, mesh, finish, fallback walk)
-    long long tp;
-#endif
 };
-
-#ifdef TN_PROFILE_TRACE
-#define TN_TTICK0(c) { __builtin_amdgcn_sched_barrier(0); (c).tp = clock64(); __builtin_amdgcn_sched_barrier(0); }
-#define TN_TTICK(c, k) { __builtin_amdgcn_sched_barrier(0); const long long _t = clock64(); (c).cyc[k] += (uint32_t)(_t - (c).tp); (c).tp = _t; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define TN_TTICK0(c)
-#define TN_TTICK(c, k)
-#endif
 
 #if TN_FAST
 TN_D float minf_ref(float a, float b) { return fminf(a, b); }       // tolerance arm: v_min_f32 / v_max_f32
@@ -82,10 +59,6 @@ TN_D bool ray_aabb(V3 pos, V3 rcp, float minx, float miny, float minz, float max
         t = lmin;
     return hit;
 }
-
-#ifndef TN_FLAT_MINMAX
-#define TN_FLAT_MINMAX 1
-#endif
 
 // IntersectRayAABBFast (intersection.h:373-397) with hardware min/max.  Only for rays whose 1/d is finite in
 // all three components: then every product below is finite or +-inf, never NaN, and v_min/v_max return what the
@@ -444,7 +417,6 @@ TN_D bool prim_intersect(const SC& sc, int index, Stack& st, int sp, V3 o, V3 d,
     MeshHit h;
     const Tri48* mtris;
     const float* nr;
-#if TN_QUAD_RECORD
     if (!(SC::kWalkedOnly && !SC::kQuadsInline) && (p.flags & kPrimQuadArena))
     {
         // a quad in the arena: node, triangles and normals at the offsets its primitive record carries (no mesh-table record in between)
@@ -456,7 +428,6 @@ TN_D bool prim_intersect(const SC& sc, int index, Stack& st, int sp, V3 o, V3 d,
             return false;
     }
     else
-#endif
     {
     const DevMesh m = sc.meshes[p.mesh];
     mtris = mesh_tris(sc, m);
@@ -556,10 +527,9 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
     // 1295 -> 1377 Msamples/s; with ONE mesh there is nothing to merge and the second loop only costs: cornell -3.5 %).
     unsigned long long meshes = 0;
     // leaf-box tests with hardware min / max when no 0*inf can occur in the wave (every lane's origin and 1/d finite: k_walk's rule,
-    // ray_aabb_minmax above) -- 12 instructions per box instead of 24; build with -DTN_FLAT_MINMAX=0 to keep the ternaries (A/B)
-    const bool finiteAll = TN_FLAT_MINMAX && __all(finite_bits(rcp.x) && finite_bits(rcp.y) && finite_bits(rcp.z) &&
-                                                  finite_bits(o.x) && finite_bits(o.y) && finite_bits(o.z));
-    TN_TTICK0(ctr)
+    // ray_aabb_minmax above) -- 12 instructions per box instead of 24
+    const bool finiteAll = __all(finite_bits(rcp.x) && finite_bits(rcp.y) && finite_bits(rcp.z) &&
+                                 finite_bits(o.x) && finite_bits(o.y) && finite_bits(o.z));
     // The scene's always-hit planes FOUR AT A TIME, ahead of the loop (DevScene::planeEq: the same equations, padded with planes no ray
     // meets; their boxes say 2 and the loop below passes them by).  Every lane is at the same primitive in this scan, so one
     // IntersectRayPlane after the other is one IEEE division's dependent chain after the other; four in one block are four independent
@@ -603,19 +573,12 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
         }
     }
     // The primitives that are not in the plane table (DevScene::scanMask), as a scalar bit loop: the loop over all primitives fetched a table
-    // plane's leaf box only to read "pass by" (-DTN_SCAN_MASK=0: the A/B arm).  And a visited primitive's RECORD is requested together with its
-    // box, one scalar round trip instead of two dependent ones (-DTN_SCAN_AHEAD=0: fetched behind the box test).
-#if TN_SCAN_MASK
+    // plane's leaf box only to read "pass by".  And a visited primitive's RECORD is requested together with its box, one scalar round trip
+    // instead of two dependent ones ("What the scan waits for").
     for (unsigned long long todo = wave_uniform64(sc.scanMask); todo != 0ull; todo &= todo - 1ull)
     {
         const int i = (int)__builtin_ctzll(todo);
-#else
-    for (int i = 0; i < sc.numPrims; ++i)
-    {
-#endif
-        TN_TTICK(ctr, 4)
         ConstF4V b0 = sc.kBoxes[i*2], b1 = sc.kBoxes[i*2 + 1];
-#if TN_SCAN_AHEAD
         ConstF4V ra = sc.kPrims[i*4], rb = sc.kPrims[i*4 + 1], rc = sc.kPrims[i*4 + 2], rd = sc.kPrims[i*4 + 3];
         asm volatile("" : "+s"(b0), "+s"(b1), "+s"(ra), "+s"(rb), "+s"(rc), "+s"(rd));        // (all six in flight before the first is used)
         Prim64 rec;
@@ -624,37 +587,20 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
         rec.g0 = rc.x; rec.g1 = rc.y; rec.g2 = rc.z; rec.g3 = rc.w;
         rec.type = __float_as_uint(rd.x); rec.flags = __float_as_uint(rd.y);
         rec.mesh = __float_as_uint(rd.z); rec.moving = __float_as_uint(rd.w);
-#endif
-#if !TN_SCAN_MASK
-        if (__float_as_uint(b1.z) == 2u)
-            continue;
-#endif
         if (__float_as_uint(b1.z) == 0u)
         {
             float tb;
             if (!(finiteAll ? ray_aabb_minmax(o, rcp, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, tb) : ray_aabb(o, rcp, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, tb)))
                 continue;
         }
-        TN_TTICK(ctr, 0)
-#if TN_SCAN_AHEAD
         if (SC::kDefer != 0 && (SC::kDefer == 1 || sc.deferMeshes) && rec.type == (uint32_t)kPrimMesh)
-#else
-        if (SC::kDefer != 0 && (SC::kDefer == 1 || sc.deferMeshes) && __float_as_uint(sc.kPrims[i*4 + 3].x) == (uint32_t)kPrimMesh)
-#endif
         {
             meshes |= 1ull << i;
             continue;
         }
         float t;
         V3 n;
-#if TN_SCAN_AHEAD
         const bool primHit = prim_intersect<SC, Stack, COUNT, ANYHIT, true>(sc, i, st, 0, o, d, time, t, n, ctr, tStop, rcp, true, &rec);
-#else
-        const bool primHit = prim_intersect<SC, Stack, COUNT, ANYHIT, true>(sc, i, st, 0, o, d, time, t, n, ctr, tStop, rcp, true);
-#endif
-#ifdef TN_PROFILE_TRACE
-        { const uint32_t ty = __builtin_amdgcn_readfirstlane(__float_as_uint(reinterpret_cast<const float4*>(sc.prims + i)[3].x)); TN_TTICK(ctr, ty == kPrimPlane ? 1 : ty == kPrimSphere ? 2 : 3) }
-#endif
         if (primHit)
             accept(i, t, n);
         if (ANYHIT && minT < tStop)
@@ -676,7 +622,6 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
             if (ANYHIT && minT < tStop)
                 break;
         }
-        TN_TTICK(ctr, 3)
     }
 
     outT = minT;
@@ -744,7 +689,6 @@ TN_D int trace(const SC& sc, Stack& st, V3 o, V3 d, float time, float& outT, V3&
         if (sane && !tie)
             return prim;
     }
-    TN_TTICK0(ctr)
 
     int sp = 0;
     st.set(sp++, sc.root);
@@ -794,7 +738,6 @@ TN_D int trace(const SC& sc, Stack& st, V3 o, V3 d, float time, float& outT, V3&
 
     outT = minT;
     outN = face_forward(cn, -d);
-    TN_TTICK(ctr, 5)
     return closest;
 }
 

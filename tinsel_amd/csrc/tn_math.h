@@ -59,16 +59,11 @@ TN_HD V3 divs(V3 a, float s) { float r = rcpf_cr(s); return V3(a.x*r, a.y*r, a.z
 //   sqrt 11  the same behind a branch (2^-96 <= x < inf, else sqrtf): exact; +0.7 % (the branch splits the scheduler's blocks)
 //   rcp 11   v_rcp + two Newton steps behind a branch (normal x, |x| < 2^126, else 1.0f/x): exact on all 2^32 but 4-5 % SLOWER --
 //            a straight-line form needs the quotient rounded once into the denormal range, which is what v_div_fmas is for: the
-//            compiler's expansion stays (variant 0); one guard per direction triple (TN_RCP3_GROUP) measured +-1 %: off
-#ifndef TN_RCP_VARIANT
-#define TN_RCP_VARIANT 0
-#endif
-#ifndef TN_RCP3_GROUP
-#define TN_RCP3_GROUP 0
-#endif
-#ifndef TN_SQRT_VARIANT
-#define TN_SQRT_VARIANT 21
-#endif
+//            compiler's expansion stays (variant 0); one guard per direction triple measured +-1 %: not kept
+// The variants the library is built with (rcpf_cr / sqrtf_cr / rsqrtf_cr below; tinsel_hip_selftest_arith's "as built")
+constexpr int kRcpVariant = 0;
+constexpr int kSqrtVariant = 21;
+constexpr int kRsqrtVariant = 3;
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // v_rcp_f32 + two Newton steps (the second one is Markstein's correction of the quotient q = r)
@@ -131,7 +126,7 @@ template <int V> __device__ __forceinline__ float sqrt_candidate(float x)
 TN_HD float rcpf_cr(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !(defined(TN_FAST) && TN_FAST)
-    return rcp_candidate<TN_RCP_VARIANT>(x);
+    return rcp_candidate<kRcpVariant>(x);
 #else
     return 1.0f/x;
 #endif
@@ -139,7 +134,7 @@ TN_HD float rcpf_cr(float x)
 TN_HD float sqrtf_cr(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !(defined(TN_FAST) && TN_FAST)
-    return sqrt_candidate<TN_SQRT_VARIANT>(x);
+    return sqrt_candidate<kSqrtVariant>(x);
 #else
     return sqrtf(x);
 #endif
@@ -155,15 +150,12 @@ TN_HD V3 cross(V3 a, V3 b) { return V3(a.y*b.z - b.y*a.z, a.z*b.x - a.x*b.z, a.x
 // mantissa is all ones and rounds to even: 255 wrong operands of 2^32, found by the self-test (and by one parity test, by luck).  From
 // v_rcp_f32(root) (2) or from y one ulp up (3) it is exact on all 2^32 (tinsel_hip_selftest_arith op 2); 3 is the default:
 // cornell +1.2 %, veach +0.9 % over variant 0 (profiles/r03_w_short_sqrt.md).
-#ifndef TN_RSQRT_VARIANT
-#define TN_RSQRT_VARIANT 3
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 template <int V> __device__ __forceinline__ float rsqrt_candidate(float x)
 {
     static_assert(V >= 0 && V <= 3, "unknown reciprocal-square-root variant");
     if (V == 0)
-        return rcp_candidate<TN_RCP_VARIANT>(sqrt_candidate<TN_SQRT_VARIANT>(x));
+        return rcp_candidate<kRcpVariant>(sqrt_candidate<kSqrtVariant>(x));
     const bool small = x < 0x1p-96f;
     const float xs = small ? x*0x1p32f : x;
     const float y = __builtin_amdgcn_rsqf(xs);
@@ -186,24 +178,16 @@ template <int V> __device__ __forceinline__ float rsqrt_candidate(float x)
 TN_HD float rsqrtf_cr(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !(defined(TN_FAST) && TN_FAST)
-    return rsqrt_candidate<TN_RSQRT_VARIANT>(x);
+    return rsqrt_candidate<kRsqrtVariant>(x);
 #else
     return 1.0f/sqrtf(x);
 #endif
 }
 
-// the three reciprocals of a direction behind ONE guard (TN_RCP3_GROUP): a slab test's 1/d
+// a slab test's 1/d
 TN_HD V3 rcp3_cr(V3 d)
 {
-#if defined(__HIP_DEVICE_COMPILE__) && !(defined(TN_FAST) && TN_FAST) && TN_RCP3_GROUP
-    const float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
-    const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(d.x), __builtin_fabsf(d.y)), __builtin_fabsf(d.z));
-    if (__builtin_expect(lo >= 0x1p-126f && hi < 0x1p126f && d.x == d.x && d.y == d.y && d.z == d.z, 1))
-        return V3(rcp_refine(d.x), rcp_refine(d.y), rcp_refine(d.z));
-    return V3(1.0f/d.x, 1.0f/d.y, 1.0f/d.z);
-#else
     return V3(rcpf_cr(d.x), rcpf_cr(d.y), rcpf_cr(d.z));
-#endif
 }
 TN_HD float length_sq(V3 a) { return dot(a, a); }
 TN_HD float length(V3 a) { return sqrtf_cr(dot(a, a)); }                                                // maths.h:259
@@ -254,23 +238,15 @@ TN_HD V3 face_forward(V3 n, V3 v) { return (dot(v, n) < 0.0f) ? -n : n; }
 //   * log (GTR1) is a per-material constant evaluated by the host's own glibc.
 //   * acosf / atan2f (probe lookups): glibc 2.35 still uses the fdlibm fp32 routines for these; m_acosf /
 //     m_atanf / m_atan2f restate them in the same fp32 operation order (also checked exhaustively).
-// TN_LIBM_DOUBLE=0 switches everything to the 1-2 ulp ocml fp32 routines (A/B only).
 #ifndef TN_FAST
 #define TN_FAST 0           // 1: the tolerance arm (tinsel_fast.hip): hardware transcendentals, see tn_launch.h
 #endif
-#ifndef TN_LIBM_DOUBLE
-#define TN_LIBM_DOUBLE (!TN_FAST)
-#endif
 __device__ const unsigned long long kExp2fTab[32] = { 0x3ff0000000000000ULL, 0x3fefd9b0d3158574ULL, 0x3fefb5586cf9890fULL, 0x3fef9301d0125b51ULL, 0x3fef72b83c7d517bULL, 0x3fef54873168b9aaULL, 0x3fef387a6e756238ULL, 0x3fef1e9df51fdee1ULL, 0x3fef06fe0a31b715ULL, 0x3feef1a7373aa9cbULL, 0x3feedea64c123422ULL, 0x3feece086061892dULL, 0x3feebfdad5362a27ULL, 0x3feeb42b569d4f82ULL, 0x3feeab07dd485429ULL, 0x3feea47eb03a5585ULL, 0x3feea09e667f3bcdULL, 0x3fee9f75e8ec5f74ULL, 0x3feea11473eb0187ULL, 0x3feea589994cce13ULL, 0x3feeace5422aa0dbULL, 0x3feeb737b0cdc5e5ULL, 0x3feec49182a3f090ULL, 0x3feed503b23e255dULL, 0x3feee89f995ad3adULL, 0x3feeff76f2fb5e47ULL, 0x3fef199bdd85529cULL, 0x3fef3720dcef9069ULL, 0x3fef5818dcfba487ULL, 0x3fef7c97337b9b5fULL, 0x3fefa4afa2a490daULL, 0x3fefd0765b6e4540ULL };
-#if TN_LIBM_DOUBLE
+#if !TN_FAST
 // A double-precision constant materialised WHERE IT IS USED, in a scalar register pair (two s_mov_b32 the compiler may neither hoist nor
 // merge).  Written as plain literals, the 25 coefficients of the two routines below are loop invariants to the compiler: it hoists them out
 // of the bounce loop of every kernel that samples a BSDF and keeps them in 24 VGPRs and a dozen SGPRs from the first instruction to the
-// last -- in kernels that spill at their register limit.  -DTN_K64_LOCAL=0: plain literals (A/B)
-#ifndef TN_K64_LOCAL
-#define TN_K64_LOCAL 1
-#endif
-#if TN_K64_LOCAL
+// last -- in kernels that spill at their register limit (plain literals: cornell -3 %, profiles/r04_v_ab_k64.md).
 TN_D double k64_here(double c)
 {
     unsigned hi = (unsigned)(__builtin_bit_cast(unsigned long long, c) >> 32), lo = (unsigned)__builtin_bit_cast(unsigned long long, c);
@@ -278,9 +254,6 @@ TN_D double k64_here(double c)
     return __hiloint2double((int)hi, (int)lo);
 }
 #define K64(c) k64_here(c)
-#else
-#define K64(c) (c)
-#endif
 // The same for an fp32 constant that a VOP3 instruction needs in a register (select operands: gfx950's VOP3 takes no literal): written plainly,
 // pi, pi/2 and their negatives (m_atan2f), 1e-3f and FLT_MAX are loop invariants that sat in six VGPRs from the first instruction of k_bounce
 // to the last; K32 puts the value in a scalar register at the point of use.
@@ -540,35 +513,15 @@ TN_D float m_atan2f(float y, float x)
 #undef pi_o_2
 #undef pi
 }
-#elif TN_FAST
-// tolerance arm.  TN_FAST_NATIVE_TRIG=1: v_sin_f32 / v_cos_f32 / v_exp_f32 (absolute error ~1e-6: visibly more paths leave
-// the exact arm's track in specular scenes); 0 (default): ocml's fp32 routines (1-2 ulp)
-#ifndef TN_FAST_NATIVE_TRIG
-#define TN_FAST_NATIVE_TRIG 0
-#endif
-#if TN_FAST_NATIVE_TRIG
-TN_D void m_sincosf(float x, float& s, float& c) { s = __sinf(x); c = __cosf(x); }
-TN_D float m_sinf(float x) { return __sinf(x); }
-TN_D float m_cosf(float x) { return __cosf(x); }
-TN_D float m_expf(float x) { return __expf(x); }
-template <class Tab> TN_D float m_expf_tab(float x, const Tab&) { return __expf(x); }
 #else
+// tolerance arm: ocml's fp32 routines (1-2 ulp).  (v_sin_f32 / v_cos_f32 / v_exp_f32, absolute error ~1e-6, visibly move more paths off
+// the exact arm's track in specular scenes: not kept)
 TN_D void m_sincosf(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
 TN_D float m_sinf(float x) { return ::sinf(x); }
 TN_D float m_cosf(float x) { return ::cosf(x); }
 TN_D float m_expf(float x) { return ::expf(x); }
 template <class Tab> TN_D float m_expf_tab(float x, const Tab&) { return ::expf(x); }
-#endif
 TN_D float m_logf(float x) { return __logf(x); }
-TN_D float m_acosf(float x) { return ::acosf(x); }
-TN_D float m_atan2f(float y, float x) { return ::atan2f(y, x); }
-#else
-TN_D void m_sincosf(float x, float& s, float& c) { s = ::sinf(x); c = ::cosf(x); }
-TN_D float m_sinf(float x) { return ::sinf(x); }
-TN_D float m_cosf(float x) { return ::cosf(x); }
-TN_D float m_expf(float x) { return ::expf(x); }
-template <class Tab> TN_D float m_expf_tab(float x, const Tab&) { return ::expf(x); }
-TN_D float m_logf(float x) { return ::logf(x); }
 TN_D float m_acosf(float x) { return ::acosf(x); }
 TN_D float m_atan2f(float y, float x) { return ::atan2f(y, x); }
 #endif

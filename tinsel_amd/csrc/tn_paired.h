@@ -78,8 +78,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_STEP) void k_step(DevScene scIn, S
                 if (fresh)
                 {
                     // k_generate wrote the ray and the RNG; the rest of a fresh path's state is path_begin's constants (render.cpp:233-248)
-                    const uint32_t at = sidx(pos);
-                    const float4 ro = ss.rayO[0][at], rd = ss.rayD[0][at], rr = ss.rngId[0][at];
+                    const float4 ro = ss.rayO[0][pos], rd = ss.rayD[0][pos], rr = ss.rngId[0][pos];
                     Rng rng;
                     rng.s1 = __float_as_uint(rr.x); rng.s2 = __float_as_uint(rr.y);
                     path_begin(p, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), ro.w, rng);

@@ -292,14 +292,14 @@ TN_D bool begin_path(const CameraParams& cam, const FrameParams& fp, const uint3
 // local too.
 struct SplitState
 {
-    float4* rayO[2];    // [bounce & 1][sidx(position)]: origin.xyz, time
+    float4* rayO[2];    // [bounce & 1][position]: origin.xyz, time
     float4* rayD[2];    // dir.xyz, bsdfPdf
     float4* thr[2];     // throughput.xyz, rayEta
     float4* rad[2];     // radiance.xyz, rayType (int bits)
     float4* rngId[2];   // rng.s1, rng.s2, path slot (bits), the medium the ray travels in (PathRegs::medium: a primitive index as bits, -1 = none)
-    float4* hit;        // [hidx(position)] this bounce's closest hit: t, n.xyz
-    int32_t* hitPrim;   // [hidx1(position)]
-    uint32_t* pathNee;  // [hidx1(position)] NEE position q of the path's shadow rays of this bounce
+    float4* hit;        // [position] this bounce's closest hit: t, n.xyz
+    int32_t* hitPrim;   // [position]
+    uint32_t* pathNee;  // [position] NEE position q of the path's shadow rays of this bounce
     float4* neeRay;     // [(k*2 + {0, 1})*capacity + q] = {o, dist} {wi, nl}: lanes are consecutive q        (k_lights -> k_walk, k_shadow, k_shade)
     float4* neeSky;     // [q] the probe sample's {skyColor, skyPdf}                                           (k_lights -> k_shade)
     float* neeTime;     // [q] rayTime of the path                                                              (k_lights -> k_walk, k_shadow)
@@ -377,9 +377,8 @@ TN_D StateBuf state_buf(const SplitState& ss, int buf) { StateBuf b = { ss.rayO[
 
 TN_D void load_state(const DevScene& sc, const StateBuf& sb, uint32_t pos, PathRegs& p, uint32_t& slot, bool hasMedia)
 {
-    const uint32_t at = sidx(pos);
-    const float4 ro = sb.rayO[at], rd = sb.rayD[at], th = sb.thr[at], ra = sb.rad[at];
-    const float4 rr = sb.rngId[at];
+    const float4 ro = sb.rayO[pos], rd = sb.rayD[pos], th = sb.thr[pos], ra = sb.rad[pos];
+    const float4 rr = sb.rngId[pos];
     p.o = V3(ro.x, ro.y, ro.z); p.time = ro.w;
     p.d = V3(rd.x, rd.y, rd.z); p.bsdfPdf = rd.w;
     p.thr = V3(th.x, th.y, th.z); p.eta = th.w;
@@ -397,12 +396,11 @@ TN_D void load_state(const DevScene& sc, const SplitState& ss, int buf, uint32_t
 
 TN_D void store_state(const StateBuf& sb, uint32_t pos, const PathRegs& p, uint32_t slot)
 {
-    const uint32_t at = sidx(pos);
-    sb.rayO[at] = make_float4(p.o.x, p.o.y, p.o.z, p.time);
-    sb.rayD[at] = make_float4(p.d.x, p.d.y, p.d.z, p.bsdfPdf);
-    sb.thr[at] = make_float4(p.thr.x, p.thr.y, p.thr.z, p.eta);
-    sb.rad[at] = make_float4(p.rad.x, p.rad.y, p.rad.z, __int_as_float(p.rayType));
-    sb.rngId[at] = make_float4(__uint_as_float(p.rng.s1), __uint_as_float(p.rng.s2), __uint_as_float(slot), __int_as_float(p.medium));
+    sb.rayO[pos] = make_float4(p.o.x, p.o.y, p.o.z, p.time);
+    sb.rayD[pos] = make_float4(p.d.x, p.d.y, p.d.z, p.bsdfPdf);
+    sb.thr[pos] = make_float4(p.thr.x, p.thr.y, p.thr.z, p.eta);
+    sb.rad[pos] = make_float4(p.rad.x, p.rad.y, p.rad.z, __int_as_float(p.rayType));
+    sb.rngId[pos] = make_float4(__uint_as_float(p.rng.s1), __uint_as_float(p.rng.s2), __uint_as_float(slot), __int_as_float(p.medium));
 }
 
 TN_D void store_state(const SplitState& ss, int buf, uint32_t pos, const PathRegs& p, uint32_t slot)

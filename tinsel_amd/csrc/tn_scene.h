@@ -118,8 +118,8 @@ struct alignas(32) PrimBox
 };
 static_assert(sizeof(PrimBox) == 32, "PrimBox");
 
-// One light of the scene as the light loops read it (LightCursor, nee_sum: tn_integrator.h): ONE 16-B record instead of the primitive index and,
-// behind it, two words of that primitive's 128-B material record
+// One light of the scene.  The light loops (LightCursor, nee_sum: tn_integrator.h) read only `prim`; the sample count and its reciprocal are
+// copies of the material's, which is where the kernels read them (tn_integrator.h says why)
 struct alignas(16) LightRec
 {
     int32_t prim;

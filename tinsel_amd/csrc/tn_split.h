@@ -122,10 +122,9 @@ __global__ __launch_bounds__(kBlock, 4) void k_generate(SplitState ss, QueueCtl 
             if (live)
             {
                 // ray and RNG only: the rest of a fresh path's state is constant and k_shade knows it (ShadeFetch::issue)
-                const uint32_t at = sidx(pos);
-                ss.rayO[0][at] = make_float4(p.o.x, p.o.y, p.o.z, p.time);
-                ss.rayD[0][at] = make_float4(p.d.x, p.d.y, p.d.z, p.bsdfPdf);
-                ss.rngId[0][at] = make_float4(__uint_as_float(p.rng.s1), __uint_as_float(p.rng.s2), __uint_as_float(slot), __int_as_float(-1));
+                ss.rayO[0][pos] = make_float4(p.o.x, p.o.y, p.o.z, p.time);
+                ss.rayD[0][pos] = make_float4(p.d.x, p.d.y, p.d.z, p.bsdfPdf);
+                ss.rngId[0][pos] = make_float4(__uint_as_float(p.rng.s1), __uint_as_float(p.rng.s2), __uint_as_float(slot), __int_as_float(-1));
             }
         }
         if (lane == 0)
@@ -167,7 +166,7 @@ TN_D void draw_shadow_rays(const SC& sc, const SplitState& ss, const BinPrims& b
     bool front = bp.count == 0;         // no big mesh: everything goes to the front
     if (has)
     {
-        const float2 rr = *reinterpret_cast<const float2*>(ss.rngId[cur] + sidx(pos));
+        const float2 rr = *reinterpret_cast<const float2*>(ss.rngId[cur] + pos);
         rng.s1 = __float_as_uint(rr.x); rng.s2 = __float_as_uint(rr.y);
 
         // the first shadow ray stays in registers across the append; the others are drawn after it
@@ -202,8 +201,8 @@ TN_D void draw_shadow_rays(const SC& sc, const SplitState& ss, const BinPrims& b
             store_nee_ray(ss, qn, k, g);
         }
         ss.neeTime[qn] = time;
-        ss.pathNee[hidx1(pos)] = qn;
-        *reinterpret_cast<float2*>(ss.rngId[cur] + sidx(pos)) = make_float2(__uint_as_float(rng.s1), __uint_as_float(rng.s2));
+        ss.pathNee[pos] = qn;
+        *reinterpret_cast<float2*>(ss.rngId[cur] + pos) = make_float2(__uint_as_float(rng.s1), __uint_as_float(rng.s2));
     }
 }
 
@@ -250,15 +249,15 @@ __global__ __launch_bounds__(kBlock, WONLY ? TN_WAVES_SCAN_EXTEND : LIGHTS ? TN_
             float time = 0.0f;
             if (j < n)
             {
-                const float4 ro = ss.rayO[cur][sidx(pos)];
-                const float4 rd = ss.rayD[cur][sidx(pos)];
+                const float4 ro = ss.rayO[cur][pos];
+                const float4 rd = ss.rayD[cur][pos];
                 sc.walkItem = pos*walkPrims;        // only front rays ever reach a walked primitive
 
                 float t;
                 const int prim = trace<SceneT<LDS, WONLY, 2, MIXED>, LdsStack<kBlock>, COUNT>(sc, st, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), ro.w, t, hitN, ctr);
 
-                ss.hit[hidx(pos)] = make_float4(t, hitN.x, hitN.y, hitN.z);
-                ss.hitPrim[hidx1(pos)] = prim;
+                ss.hit[pos] = make_float4(t, hitN.x, hitN.y, hitN.z);
+                ss.hitPrim[pos] = prim;
                 rays++;
                 has = prim >= 0;
                 hitP = V3(ro.x, ro.y, ro.z) + V3(rd.x, rd.y, rd.z)*t;       // on_hit_begin's h.p (render.cpp:275)
@@ -306,7 +305,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_LIGHTS) void k_lights(DevScene scI
         uint32_t npos = region_pos(rBase, rLen, nFront, lane < n ? lane : 0u);
         if (lane < n)
         {
-            nro = ss.rayO[cur][sidx(npos)]; nrd = ss.rayD[cur][sidx(npos)]; nhh = ss.hit[hidx(npos)]; nprim = ss.hitPrim[hidx1(npos)];
+            nro = ss.rayO[cur][npos]; nrd = ss.rayD[cur][npos]; nhh = ss.hit[npos]; nprim = ss.hitPrim[npos];
         }
         for (uint32_t j0 = 0; j0 < n; j0 += kWave)
         {
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_LIGHTS) void k_lights(DevScene scI
                 npos = region_pos(rBase, rLen, nFront, jn < n ? jn : 0u);
                 if (jn < n)
                 {
-                    nro = ss.rayO[cur][sidx(npos)]; nrd = ss.rayD[cur][sidx(npos)]; nhh = ss.hit[hidx(npos)]; nprim = ss.hitPrim[hidx1(npos)];
+                    nro = ss.rayO[cur][npos]; nrd = ss.rayD[cur][npos]; nhh = ss.hit[npos]; nprim = ss.hitPrim[npos];
                 }
             }
             V3 hitP, hitN;
@@ -426,8 +425,7 @@ struct ShadeFetch
     {
         if (!valid)
             return;
-        const uint32_t at = sidx(pos);
-        ro = sb.rayO[at]; rd = sb.rayD[at];
+        ro = sb.rayO[pos]; rd = sb.rayD[pos];
         if (fresh)
         {
             th = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
@@ -435,12 +433,12 @@ struct ShadeFetch
         }
         else
         {
-            th = sb.thr[at]; ra = sb.rad[at];
+            th = sb.thr[pos]; ra = sb.rad[pos];
         }
-        rr = sb.rngId[at];
-        hh = hit[hidx(pos)];
-        prim = hitPrim[hidx1(pos)];
-        qn = hasNee ? pathNee[hidx1(pos)] : 0u;
+        rr = sb.rngId[pos];
+        hh = hit[pos];
+        prim = hitPrim[pos];
+        qn = hasNee ? pathNee[pos] : 0u;
     }
     TN_D void issue(const SplitState& ss, int buf, uint32_t pos, bool valid, bool hasMedia, bool hasNee, bool fresh)
     {
@@ -546,7 +544,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade(DevScene scIn,
         // that hid a latency.  At three, the 30 registers of a second ShadeFetch are spilled ones, and the wait for the shadow-ray
         // records in the middle of the round -- vmcnt counts in order -- waited for the early request as well: without it k_shade spills
         // 124 B instead of 196 and runs 3-9 % faster on the 524k-triangle config and many_spheres, +-1 % on glass,
-        // profiles/r03_z3_ab_shade_fetch.md; -DTN_SHADE_PREFETCH=1 is the old arm.  Requesting the shadow-ray records a round ahead too, in
+        // profiles/r03_z3_ab_shade_fetch.md.  Requesting the shadow-ray records a round ahead too, in
         // registers or through LDS with global_load_lds, spills 352-400 B and doubles the kernel's time.)
         for (uint32_t j0 = 0; j0 < n; j0 += kWave)
         {
@@ -611,7 +609,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade_sorted(DevScen
         // their positions, or -- region read -- shades what is left, class after class, in as few rounds as the leftovers' sum needs.
         int nextPrim = -1;          // the hit primitives of the next round are requested a round ahead (4 B per path)
         if (lane < n)
-            nextPrim = ss.hitPrim[hidx1(region_pos(rBase, rLen, nFront, lane))];
+            nextPrim = ss.hitPrim[region_pos(rBase, rLen, nFront, lane)];
         uint32_t j0 = 0, e0 = 0;
         for (;;)
         {
@@ -637,7 +635,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade_sorted(DevScen
                 const uint32_t at = region_pos(rBase, rLen, nFront, j < n ? j : 0u);
                 const int prim = nextPrim;
                 if (j + kWave < n)
-                    nextPrim = ss.hitPrim[hidx1(region_pos(rBase, rLen, nFront, j + kWave))];
+                    nextPrim = ss.hitPrim[region_pos(rBase, rLen, nFront, j + kWave)];
                 int cls = -1;
                 if (j < n)
                 {

@@ -105,8 +105,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : TN_WAVES_SWALK) void k_s
         else
         {
             const V3 n = face_forward(cn, -d);              // render.cpp:59
-            ss.hit[hidx(pos)] = make_float4(minT, n.x, n.y, n.z);
-            ss.hitPrim[hidx1(pos)] = closest;
+            ss.hit[pos] = make_float4(minT, n.x, n.y, n.z);
+            ss.hitPrim[pos] = closest;
         }
     };
 
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : TN_WAVES_SWALK) void k_s
                     }
                     else
                     {
-                        ro = ss.rayO[cur][sidx(pos)]; rd = ss.rayD[cur][sidx(pos)];
+                        ro = ss.rayO[cur][pos]; rd = ss.rayD[cur][pos];
                         time = ro.w;
                     }
                     o = V3(ro.x, ro.y, ro.z);

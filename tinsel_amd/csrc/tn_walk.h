@@ -40,7 +40,6 @@
 #pragma once
 
 #include "tn_isect.h"
-#include "tn_layout.h"
 
 namespace tn {
 
@@ -50,7 +49,7 @@ struct WalkJob
 {
     const uint32_t* queue;          // the positions to walk (k_seg_expand: the front entries of every region), *frontCount of them
     const uint32_t* frontCount;
-    const float4* rayO;             // extension rays: origin|time, dir|- by path position (SplitState::rayO / rayD of the bounce: [sidx(position)])
+    const float4* rayO;             // extension rays: origin|time, dir|- by path position (SplitState::rayO / rayD of the bounce: [position])
     const float4* rayD;
     const float4* nee;              // shadow rays: SplitState::neeRay [(k*2 + {0: o|dist, 1: wi|nl})*neeStride + q] by NEE position q
     uint32_t neeStride;
@@ -281,12 +280,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
                     {
                         const float4* np = job.nee + (size_t)(k*2u)*job.neeStride + slot;
                         ro = np[0]; rd = np[job.neeStride];
-                        time = job.mixed ? job.rayO[sidx(slot)].w : job.neeTime[slot];
+                        time = job.mixed ? job.rayO[slot].w : job.neeTime[slot];
                         *s_stop = shadow_stop(ro.w);    // the record's .w is the sample's distance (< 0: probe sample)
                     }
                     else
                     {
-                        ro = job.rayO[sidx(slot)]; rd = job.rayD[sidx(slot)];
+                        ro = job.rayO[slot]; rd = job.rayD[slot];
                         time = ro.w;
                         if (job.mixed)
                             *s_stop = -kFltMax;         // (the lane's last ray may have been a shadow ray)
@@ -684,12 +683,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk_rays(DevScene sc, WalkJob
                     {
                         const float4* np = job.nee + (size_t)(k*2u)*job.neeStride + slot;
                         ro = np[0]; rd = np[job.neeStride];
-                        time = job.mixed ? job.rayO[sidx(slot)].w : job.neeTime[slot];
+                        time = job.mixed ? job.rayO[slot].w : job.neeTime[slot];
                         *s_stop = shadow_stop(ro.w);    // the record's .w is the sample's distance (< 0: probe sample)
                     }
                     else
                     {
-                        ro = job.rayO[sidx(slot)]; rd = job.rayD[sidx(slot)];
+                        ro = job.rayO[slot]; rd = job.rayD[slot];
                         time = ro.w;
                         if (job.mixed)
                             *s_stop = -kFltMax;         // (the lane's last ray may have been a shadow ray)
