@@ -10,10 +10,12 @@ from tests.test_gpu_parity import _load
 pytestmark = pytest.mark.gpu
 
 
-def _render(scene, cam, opt, passes, pipeline, batch=None):
+def _render(scene, cam, opt, passes, pipeline, batch=None, tuning=None):
     from tinsel_amd import create_gpu_renderer
     r = create_gpu_renderer(scene)
     r.set_pipeline(pipeline)
+    if tuning:
+        r.set_tuning(**tuning)
     if batch:
         r.set_batch_paths(batch)
     r.init(opt.width, opt.height)
@@ -48,10 +50,12 @@ def test_odd_frames_and_batches(name, size):
 def test_queue_counts_of_both_pipelines():
     scene, cam, opt, g = _load("cornell")
     passes = 3
-    for pipeline in (abi.PIPELINE_WAVEFRONT, abi.PIPELINE_WAVEFRONT_SPLIT):
-        _, (live, shadow), st = _render(scene, cam, opt, passes, pipeline)
-        assert len(live) == opt.max_depth
-        assert live[0] == passes*opt.width*opt.height
-        assert all(a >= b for a, b in zip(live, live[1:])) and live[-1] > 0
-    # the split pipeline also counts the paths with shadow rays: the paths that hit something
-    assert 0 < shadow[0] <= live[0]
+    # overlap 1: the batch's 3 passes as two chunks of 2 and 1 on two streams, each in its own dense state; the counts are the last chunk's
+    for tuning, counted in ((None, passes), ({"overlap": 1}, 1)):
+        for pipeline in (abi.PIPELINE_WAVEFRONT, abi.PIPELINE_WAVEFRONT_SPLIT):
+            _, (live, shadow), st = _render(scene, cam, opt, passes, pipeline, tuning=tuning)
+            assert len(live) == opt.max_depth
+            assert live[0] == counted*opt.width*opt.height, (tuning, pipeline)
+            assert all(a >= b for a, b in zip(live, live[1:])) and live[-1] > 0
+        # the split pipeline also counts the paths with shadow rays: the paths that hit something
+        assert 0 < shadow[0] <= live[0]

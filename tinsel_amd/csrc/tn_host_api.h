@@ -886,7 +886,7 @@ int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth)
     int perBatch = (int)std::max<size_t>(1, batch_slots(r)/perPass);
     if (perBatch > passes)
         perBatch = passes;
-    return ensure_batch(r, perPass*(size_t)perBatch, max_depth);
+    return ensure_batch(r, plan_batch(r, perPass, perBatch, /*mayOverlap*/ false), max_depth);
 }
 
 int tinsel_hip_set_batch_paths(tinsel_hip* r, unsigned long long max_paths)
@@ -1008,11 +1008,12 @@ int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces)
     const int n = std::min(max_bounces, std::min(r->batchDepth, r->lastFp.maxDepth));
     if (r->lastPipeline == TINSEL_PIPELINE_MEGAKERNEL || r->batchPipeline != r->lastPipeline)
         return fail("queue_counts: the last batch did not run a wavefront pipeline");
-    // the counts are kept per region
+    // the counts are kept per region, in the lane of the chunk traced last
+    const tinsel_hip::DenseLane& lane = r->lane[r->lastLane];
     const bool split = r->lastPipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT && r->neePerPath > 0;
-    const size_t W = r->lastRegions;
+    const size_t W = lane.regions;
     std::vector<uint32_t> seg(W*(size_t)n*4, 0u);
-    uint32_t* const src[4] = { r->ss.segFront, r->ss.segBack, r->ss.neeFront, r->ss.neeBack };
+    uint32_t* const src[4] = { lane.ss.segFront, lane.ss.segBack, lane.ss.neeFront, lane.ss.neeBack };
     for (int a = 0; a < (split ? 4 : 2); ++a)
         HIP_TRY(hipMemcpy(seg.data() + (size_t)a*W*n, src[a], W*(size_t)n*sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < n; ++b)
@@ -1024,7 +1025,7 @@ int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces)
             nee += seg[2*W*n + (size_t)b*W + g] + seg[3*W*n + (size_t)b*W + g];
         }
         // the fused kernel generates bounce 0's paths itself
-        out[b] = (b == 0 && r->lastPipeline == TINSEL_PIPELINE_WAVEFRONT) ? r->lastFp.genCount : (uint32_t)live;
+        out[b] = (b == 0 && r->lastPipeline == TINSEL_PIPELINE_WAVEFRONT) ? lane.paths : (uint32_t)live;
         out[max_bounces + b] = (uint32_t)nee;
     }
     return n;
@@ -1043,19 +1044,13 @@ int tinsel_hip_plan_regions(unsigned long long slots, int num_cus, int nee_per_p
 {
     if (!out || slots == 0 || slots >= 0xffffffffull || num_cus < 1 || num_cus > 4096)
         return fail("plan_regions: bad arguments");
-    tinsel_hip* r = new tinsel_hip();
-    r->numCUs = num_cus;
-    r->neePerPath = nee_per_path;
-    // (alloc_dense's capacities)
-    const size_t maxRegions = (size_t)num_cus*(size_t)grid_mult(r)*(kBlock/kWave)*3/2;
-    r->splitMaxRegions = (uint32_t)maxRegions;
-    r->splitCap = (size_t)slots + maxRegions*kWave;
-    LaunchArgs a = {};
-    int grid = streaming_grid(r, (size_t)slots, fused ? TINSEL_PIPELINE_WAVEFRONT : TINSEL_PIPELINE_WAVEFRONT_SPLIT);
-    const int rc = cut_regions(r, a, (size_t)slots, &grid, fused ? (size_t)r->splitMaxRegions : (size_t)0);
-    out[0] = a.ss.numRegions; out[1] = a.ss.regionLen; out[2] = a.ss.bigRegions; out[3] = a.ss.shortLen;
-    out[4] = (unsigned int)grid; out[5] = r->splitMaxRegions;
-    delete r;
+    // (the default tuning; alloc_dense's region arrays, positions for the batch + a wave per region)
+    RegionSpec s = region_spec(tuning_defaults(), num_cus, nee_per_path, fused != 0, kBounceWaves);
+    s.capacity = (size_t)slots + s.maxRegions*kWave;
+    RegionCut c;
+    const int rc = cut_regions(s, (size_t)slots, streaming_grid(s, (size_t)slots), c) ? 0 : fail("render: path buffers too small for this batch");
+    out[0] = c.numRegions; out[1] = c.regionLen; out[2] = c.bigRegions; out[3] = c.shortLen;
+    out[4] = (unsigned int)c.grid(); out[5] = (unsigned int)s.maxRegions;
     return rc;
 }
 

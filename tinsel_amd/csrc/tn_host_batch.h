@@ -9,12 +9,12 @@ void free_batch(tinsel_hip* r)
     for (void* p : r->batchAllocs)
         (void)hipFree(p);
     r->batchAllocs.clear();
-    r->walkRec = nullptr;
+    for (tinsel_hip::DenseLane& lane : r->lane)
     {
         tinsel_hip::DenseLane fresh;
-        fresh.walkOverflow = r->laneB.walkOverflow;
-        fresh.walkOverflowCap = r->laneB.walkOverflowCap;
-        r->laneB = fresh;
+        fresh.walkOverflow = lane.walkOverflow;
+        fresh.walkOverflowCap = lane.walkOverflowCap;
+        lane = fresh;
     }
     r->batchPipeline = -1;
     r->batchSlots = 0;
@@ -102,123 +102,6 @@ int resolve_pipeline(const tinsel_hip* r)
     // features 690 -> 616, 10 rays: features + probe 589 -> 515; until the BSDF terms moved behind the shadow traces the
     // many-ray scenes were faster split); scenes with meshes or a scene BVH in HBM run the split pipeline.
     return r->scene.allInArena ? TINSEL_PIPELINE_WAVEFRONT : TINSEL_PIPELINE_WAVEFRONT_SPLIT;
-}
-
-// The wavefront pipelines' state (SplitState, tn_kernels.h): by POSITION, two buffers of everything a bounce rewrites; for the
-// split pipeline also what its kernels hand to each other (hit, shadow rays and their results, k_walk's records and list)
-int alloc_dense(tinsel_hip* r, size_t slots, int maxDepth, bool split, bool paired = false)
-{
-    const size_t K = (split || paired) ? (size_t)r->neePerPath : 0;
-    // (half as many again as the widest grid: the short regions at the end of a batch, split_tail_regions)
-    const size_t maxRegions = (size_t)r->numCUs*(size_t)grid_mult(r)*(kBlock/kWave)*3/2;
-    const size_t cap = (slots + maxRegions*kWave + kWave - 1)/kWave*kWave;       // a region is a whole number of waves long
-    SplitState& ss = r->ss;
-    memset(&ss, 0, sizeof(ss));
-    for (int b = 0; b < 2; ++b)
-        if (batch_alloc(r, &ss.rayO[b], cap) || batch_alloc(r, &ss.rayD[b], cap) || batch_alloc(r, &ss.thr[b], cap) ||
-            batch_alloc(r, &ss.rad[b], cap) || batch_alloc(r, &ss.rngId[b], cap))
-            return -1;
-    if (batch_alloc(r, &ss.segFront, maxRegions*((size_t)maxDepth + 2)) || batch_alloc(r, &ss.segBack, maxRegions*((size_t)maxDepth + 2)) ||
-        batch_alloc(r, &r->regionOrder, maxRegions/(kBlock/kWave)) || batch_alloc(r, &r->regionOrderNee, maxRegions/(kBlock/kWave)))
-        return -1;
-    ss.radOut = r->ps.rad;
-    ss.capacity = (uint32_t)cap;
-    r->splitCap = cap;
-    r->splitMaxRegions = (uint32_t)maxRegions;
-    r->walkRec = nullptr;
-    r->walkList = nullptr;
-    r->segPrefix = nullptr;
-    if (paired)
-    {
-        // the K pending light samples of every path, by position, double-buffered like the state (tn_paired.h); k_walk's records: K + 1 rays per position
-        ss.neePerPath = (int32_t)K;
-        for (int b = 0; b < 2; ++b)
-            if (batch_alloc(r, &ss.pairThr[b], K ? cap : 1) || batch_alloc(r, &ss.pairRay[b], cap*K*2) || batch_alloc(r, &ss.pairPend[b], K > 1 ? cap*K*2 : cap))     // (sample k's two records at (2k, 2k + 1)*cap; sample 0 has no second one)
-                return -1;
-        if (r->walkPrims.count > 0 && r->walkEnabled && (double)cap*(double)(K + 1)*r->walkPrims.count < 2147483648.0)
-            if (batch_alloc(r, &r->walkRec, cap*(K + 1)*(size_t)r->walkPrims.count*2) || batch_alloc(r, &r->walkList, cap) ||
-                batch_alloc(r, &r->segPrefix, maxRegions + 1))
-                return -1;
-        return 0;
-    }
-    if (!split)
-        return 0;
-
-    if (batch_alloc(r, &ss.hit, cap) || batch_alloc(r, &ss.hitPrim, cap) || batch_alloc(r, &ss.pathNee, K ? cap : 1) ||
-        batch_alloc(r, &ss.neeRay, cap*K*2) || batch_alloc(r, &ss.neeSky, r->scene.probe.valid ? cap : 1) ||
-        batch_alloc(r, &ss.neeTime, K ? cap : 1) || batch_alloc(r, &ss.neeRes, cap*K) ||
-        batch_alloc(r, &ss.neeFront, maxRegions*(size_t)maxDepth) || batch_alloc(r, &ss.neeBack, maxRegions*(size_t)maxDepth))
-        return -1;
-    ss.neePerPath = (int32_t)K;
-    // k_walk: one 32-B closest hit per (ray, walked primitive), by position; extension and shadow rays share the buffer
-    if (r->walkPrims.count > 0 && r->walkEnabled && (double)cap*(K > 1 ? K : 1)*r->walkPrims.count < 2147483648.0)
-        if (batch_alloc(r, &r->walkRec, cap*(size_t)(K > 1 ? K : 1)*(size_t)r->walkPrims.count*2) || batch_alloc(r, &r->walkList, cap) ||
-            batch_alloc(r, &r->segPrefix, maxRegions + 1))
-            return -1;
-    // k_swalk's list (scenes the flat scan cannot take): the same two arrays (such scenes have no walked primitives)
-    if (!r->walkList && !r->scene.flatScan)
-        if (batch_alloc(r, &r->walkList, cap) || batch_alloc(r, &r->segPrefix, maxRegions + 1))
-            return -1;
-    return 0;
-}
-
-void lane_swap(tinsel_hip* r)
-{
-    tinsel_hip::DenseLane& b = r->laneB;
-    std::swap(r->ss, b.ss);
-    std::swap(r->splitCap, b.splitCap);
-    std::swap(r->splitMaxRegions, b.splitMaxRegions);
-    std::swap(r->regionOrder, b.regionOrder);
-    std::swap(r->regionOrderNee, b.regionOrderNee);
-    std::swap(r->walkList, b.walkList);
-    std::swap(r->segPrefix, b.segPrefix);
-    std::swap(r->walkRec, b.walkRec);
-    std::swap(r->walkOverflow, b.walkOverflow);
-    std::swap(r->walkOverflowCap, b.walkOverflowCap);
-}
-
-// slots: paths whose radiance ps.rad holds (a whole batch); stateSlots: paths each set of dense state holds (a chunk of the batch
-// where chunks overlap, render_impl; 0: the whole batch); lanes: how many sets
-int ensure_batch(tinsel_hip* r, size_t slots, int maxDepth, size_t stateSlots = 0, int lanes = 1)
-{
-    const int K = r->neePerPath;
-    const int pipeline = resolve_pipeline(r);
-    if (stateSlots == 0 || stateSlots > slots)
-        stateSlots = slots;
-    if (r->batchSlots >= slots && r->batchStateSlots >= stateSlots && r->batchLanes >= lanes && r->batchNee == K && r->batchDepth >= maxDepth &&
-        r->batchPipeline == pipeline)
-        return 0;
-    free_batch(r);
-
-    // the radiance of finished paths by slot is what every pipeline hands to the accumulate kernels
-    PathState& ps = r->ps;
-    memset(&ps, 0, sizeof(ps));
-    if (batch_alloc(r, &ps.rad, slots))
-        return -1;
-    if (pipeline != TINSEL_PIPELINE_MEGAKERNEL)
-        for (int lane = lanes; lane-- > 0; )
-        {
-            if (alloc_dense(r, stateSlots, maxDepth, pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT, pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED))
-                return -1;
-            if (lane > 0)
-                lane_swap(r);           // the set just made becomes laneB
-        }
-
-    // slots of other shards are never written (gen_slot): keep their radiance at zero for the test hook
-    HIP_TRY(hipMemset(ps.rad, 0, sizeof(float4)*slots));
-    // (a memset of device memory only enqueues on the null stream, and the kernels that follow may run on a NON-BLOCKING stream
-    // -- a group member's, the look-ahead's -- which the null stream does not order: without this wait the zeroes could land on
-    // radiance a kernel had already written.  Allocation path only.)
-    HIP_TRY(hipStreamSynchronize(nullptr));
-
-    r->ctl.stats = r->statsDev;
-    r->batchSlots = slots;
-    r->batchStateSlots = stateSlots;
-    r->batchLanes = pipeline != TINSEL_PIPELINE_MEGAKERNEL ? lanes : 1;
-    r->batchNee = K;
-    r->batchDepth = maxDepth;
-    r->batchPipeline = pipeline;
-    return 0;
 }
 
 // CameraSampler constructor (util.h:45-71) + Mat44(Transform) (maths.h:841-849), host side, once per call
@@ -351,27 +234,409 @@ void launch_path(tinsel_hip* r, int which, const LaunchArgs& a, hipStream_t st)
         launch_path_kernel(which, a, st);
 }
 
-// k_walk's records are used by the scan kernels unless the detail counters are on (those count the inline walk)
-const float4* walk_records(const tinsel_hip* r) { return r->countDetail ? nullptr : r->walkRec; }
-
-// what every launch of a batch shares
-LaunchArgs batch_args(tinsel_hip* r, const CameraParams& cam, const FrameParams& fp)
+// What cutting a batch into regions depends on (streaming_grid, cut_regions): plain values, no renderer
+struct RegionSpec
 {
-    LaunchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = r->scene;
-    a.ps = r->ps;
-    a.ctl = r->ctl;
-    a.cam = cam;
-    a.fp = fp;
-    a.passSeeds = r->passSeeds;
-    a.walkRec = walk_records(r);
-    a.walkPrims = (uint32_t)r->walkPrims.count;
-    a.bins = r->binPrims;
-    a.stackEntries = r->stackNeed;
-    a.countDetail = r->countDetail ? 1 : 0;
-    a.ldsBytes = (uint32_t)stack_bytes(r);
-    return a;
+    int numCUs = 256;
+    int gridMult = kGridMultDefault;
+    int K = 0;                          // shadow rays per path (tinsel_hip::neePerPath)
+    bool fused = false;                 // k_bounce's batch; the split and paired pipelines keep their regions alike (cut_regions)
+    int resident = kBounceWaves;        // k_bounce's workgroups resident per CU (plan_bounce)
+    size_t maxRegions = 0;              // what the lane's arrays hold: regions (max_regions) and positions (DenseLane::splitCap)
+    size_t capacity = 0;
+    int tailSplit = -1, tailDivide = 4; // tinsel_hip_tuning::tail_split / tail_share / tail_divide
+    float tailShare = 0.0f;
+};
+
+// how a batch is cut (SplitState::numRegions .. shortLen); a launch gives each group of four regions a workgroup of its own
+struct RegionCut
+{
+    uint32_t numRegions = 0, regionLen = 0, bigRegions = 0, shortLen = 0;
+    int grid() const { return (int)(numRegions/(kBlock/kWave)); }
+};
+
+// (half as many again as the widest grid: the short regions at the end of a batch, split_tail_regions)
+size_t max_regions(int numCUs, int gridMult) { return (size_t)numCUs*(size_t)gridMult*(kBlock/kWave)*3/2; }
+
+RegionSpec region_spec(const tinsel_hip_tuning& t, int numCUs, int K, bool fused, int resident)
+{
+    RegionSpec s;
+    s.numCUs = numCUs;
+    s.gridMult = t.grid_mult > 0 ? t.grid_mult : kGridMultDefault;
+    s.K = K;
+    s.fused = fused;
+    s.resident = resident;
+    s.maxRegions = max_regions(numCUs, s.gridMult);
+    s.tailSplit = t.tail_split;
+    s.tailShare = t.tail_share;
+    s.tailDivide = t.tail_divide;
+    return s;
+}
+
+// Blocks of the streaming kernels' grid = a quarter of the regions the batch is cut into (one region per wave, SplitState,
+// tn_kernels.h).  A wave works through its region 64 entries at a time and a round is as long as its slowest lane, so
+// regions should stay long as paths die (the last round of a region is the ragged one), yet there must be enough of them to
+// balance: ~1024 positions per region, between 2 and 32 blocks per CU.  Fused kernel, cornell: a 1 M-path batch 1417 / 1520 /
+// 1655 / 1747 Msamples/s at 16 / 8 / 4 / 2 blocks per CU (regions of 64 ... 512); a 64 Mi batch 2644 / 2735 / 2803 at 8 / 16 /
+// 32 (regions of 8192 / 4096 / 2048).
+int streaming_grid(const RegionSpec& s, size_t slots)
+{
+    // (where the fused kernel's waves share their workgroup's regions -- three or more shadow rays per bounce, k_bounce -- the
+    // regions may be twice as long: features 707 -> 740, features + probe 595 -> 622, veach +-0)
+    const size_t regionTarget = (s.fused && s.K >= 3) ? 2048 : 1024;
+    const size_t perBlock = regionTarget*(kBlock/kWave);
+    const size_t blocks = (slots + perBlock - 1)/perBlock;
+    // (at least as many workgroups as the chip holds at once -- k_bounce's resident workgroups per CU, three for the split pipeline's kernels --
+    // where the batch has that many 256-path pieces: a 1 M-path batch would otherwise leave the last wave slot empty)
+    const int gridMin = s.fused ? s.resident : 3;
+    const size_t lo = std::min<size_t>((size_t)s.numCUs*(size_t)gridMin, (slots + kBlock - 1)/kBlock), hi = (size_t)s.numCUs*(size_t)s.gridMult;
+    size_t grid = std::max<size_t>(1, std::min(hi, std::max(lo, blocks)));
+    // The workgroups that HAVE work (regions are a whole number of waves long, so fewer than the grid may) as close to a whole number
+    // of resident sets (gridMin per CU) as the region length allows within +-25 %: the last set of a launch is then full instead
+    // of, say, two thirds empty.  Glass at 20 passes per batch 1262 -> 1291 Msamples/s, the 524k-triangle config 2024 -> 2034, the
+    // fused configs +-0 (profiles/r03_s_ab_grid_round.txt)
+    const size_t resident = (size_t)s.numCUs*(size_t)gridMin;
+    if (grid > 2*resident)
+    {
+        auto busy = [&](size_t g) {         // workgroups with work for a grid of g (set_regions' region length)
+            const size_t regions = g*(kBlock/kWave);
+            const size_t len = ((slots + regions - 1)/regions + kWave - 1)/kWave*kWave;
+            return (slots + len*(kBlock/kWave) - 1)/(len*(kBlock/kWave));
+        };
+        size_t best = grid;
+        double bestWaste = 2.0;
+        for (size_t g = std::max(grid*3/4, 2*resident); g <= std::min(hi, grid*5/4); g += std::max<size_t>(1, resident/16))
+        {
+            const size_t b = busy(g);
+            const double sets = (double)b/(double)resident;
+            const double waste = std::ceil(sets) - sets;        // empty fraction of the last resident set
+            if (waste < bestWaste - 1e-9)
+            {
+                bestWaste = waste;
+                best = g;
+            }
+        }
+        grid = best;
+    }
+    return (int)grid;
+}
+
+// `grid` region groups, all alike; false where the lane's arrays cannot hold them
+bool set_regions(const RegionSpec& s, size_t slots, int grid, RegionCut& c)
+{
+    c.numRegions = (uint32_t)grid*(kBlock/kWave);
+    c.regionLen = (uint32_t)(((slots + c.numRegions - 1)/c.numRegions + kWave - 1)/kWave*kWave);
+    c.bigRegions = c.numRegions;
+    c.shortLen = c.regionLen;
+    return c.numRegions <= s.maxRegions && (size_t)c.numRegions*c.regionLen <= s.capacity;
+}
+
+// The last `tailShare` of the batch's positions in regions 1/divide as long (SplitState::bigRegions / shortLen, tn_kernels.h): what the chip
+// works on when a launch runs out.  The region arrays bound their number: where the uniform cut is already at the bound the long regions get
+// longer.  Leaves `c` as set_regions made it when the batch is too small for any of that.
+void split_tail_regions(const RegionSpec& s, RegionCut& c, size_t slots, double tailShare, int divide)
+{
+    const uint32_t per = kBlock/kWave;                        // regions per group
+    const size_t maxRegions = s.maxRegions;
+    if (c.regionLen < (uint32_t)(kWave*divide*2) || c.numRegions < 64u*per || maxRegions < 128u*per)
+        return;
+    const double factor = (1.0 - tailShare) + tailShare*(double)divide;
+    uint32_t L = c.regionLen;
+    if ((double)slots*factor/(double)L + 2.0*per > (double)maxRegions)
+        L = (uint32_t)(((size_t)((double)slots*factor/(double)(maxRegions - 2*per)) + kWave)/kWave*kWave);
+    const uint32_t S = L/(uint32_t)divide/kWave*kWave;        // short regions: a multiple of 64 positions
+    const uint32_t big = (uint32_t)((double)slots*(1.0 - tailShare)/(double)L)/per*per;
+    const size_t covered = (size_t)big*L;
+    if (S < (uint32_t)kWave || big < per || covered >= slots)
+        return;
+    const size_t rest = slots - covered;
+    const uint32_t small = (uint32_t)((rest + (size_t)S*per - 1)/((size_t)S*per))*per;
+    if (big + small > maxRegions || (size_t)big*L + (size_t)small*S > s.capacity)
+        return;
+    c.regionLen = L;
+    c.bigRegions = big;
+    c.shortLen = S;
+    c.numRegions = big + small;
+}
+
+// A batch that ONE resident set of workgroups takes whole (cfg1: 256^2 x 16 passes = 683 region groups for 768 slots): two thirds of the CUs
+// get three groups, a third gets two, and the launch lasts as long as three.  Cut so that every CU gets TWO long groups -- three quarters of
+// the batch -- and the rest in groups a third as long, which the dispatcher deals out as slots come free: every CU ends up with the same
+// work.  cornell 256^2 x 16 passes 2402 -> 2670 Msamples/s, 512^2 x 4 2600 -> 2919, veach 256^2 x 16 1176 -> 1324 (call Z10).
+bool split_one_set(const RegionSpec& s, RegionCut& c, size_t slots)
+{
+    const uint32_t per = kBlock/kWave;
+    const size_t cus = (size_t)s.numCUs;
+    // (W workgroups resident per CU: W - 1 long groups per CU hold W/(W + 1) of the batch -- three waves: two groups, three quarters)
+    const size_t W = (size_t)s.resident;
+    if (W < 2)
+        return false;
+    const uint32_t L = (uint32_t)((slots*W/(W + 1))/((W - 1)*cus*per)/kWave*kWave);
+    if (L < 3u*kWave)
+        return false;
+    const uint32_t S = L/3/kWave*kWave;
+    const uint32_t big = (uint32_t)((W - 1)*cus)*per;
+    const size_t covered = (size_t)big*L;
+    if (covered >= slots)
+        return false;
+    const uint32_t small = (uint32_t)((slots - covered + (size_t)S*per - 1)/((size_t)S*per))*per;
+    if (big + small > s.maxRegions || (size_t)big*L + (size_t)small*S > s.capacity)
+        return false;
+    c.regionLen = L;
+    c.bigRegions = big;
+    c.shortLen = S;
+    c.numRegions = big + small;
+    return true;
+}
+
+// set_regions + the short regions at the end.  The last eighth or so of the positions in regions a quarter as long: a workgroup's region group
+// is 0.75 ms of a 5 ms launch (cornell, 20 passes) and a launch ends when its last workgroup does.  k_bounce alone (round 3, call Z5):
+// cornell 1024^2 x 20 passes 3878 -> 4012 Msamples/s, x 8 3539 -> 3685, 512^2 x 16 2812 -> 3021, features 1183 -> 1292, veach 1080p
+// 2414 -> 2610 (profiles/r03_z5_ab_tail_split.md).  tinsel_hip_tuning::tail_split / tail_share / tail_divide (A/B).  The cut's grid() is
+// the number of region groups = the workgroups of a launch that gives every group its own.  False where the lane's arrays cannot hold the batch.
+bool cut_regions(const RegionSpec& s, size_t slots, int grid, RegionCut& c)
+{
+    if (!set_regions(s, slots, grid, c))
+        return false;
+    // No short regions at the end for the split and paired pipelines: the launches are many and short, k_walk cuts its
+    // own list into static ranges, and more regions cost k_seg_prefix / k_walk more than the other kernels' tails gain -- the 524k-triangle
+    // config 2319 -> 2254 Msamples/s, many_spheres 2108 -> 2082, glass +-0 (profiles/r03_z5_ab_tail_split.md).
+    if (!s.fused)
+        return true;
+    double share = -0.5;
+    int divide = 4;
+    if (s.tailSplit == 0)
+        share = 0.0;
+    else if (s.tailSplit > 0)
+    {
+        share = (double)s.tailShare;
+        divide = s.tailDivide;
+    }
+    // (s.resident workgroups per CU are resident: plan_bounce)
+    if (share < 0.0 && (size_t)grid <= (size_t)s.numCUs*s.resident && (size_t)grid > (size_t)s.numCUs*(s.resident - 1) && split_one_set(s, c, slots))
+        return true;
+    if (share < 0.0)
+    {
+        // a negative share: that multiple of ONE resident set's part of the batch (s.resident workgroups per CU).  The default, half a
+        // set's part, against a fixed eighth: cornell x 20 passes 4036 -> 4059, x 64 4203 -> 4221, features 1289 -> 1298, veach 1080p
+        // 2610 -> 2621, gloss 10570 -> 10530 (call Z8)
+        const double sets = (double)grid/(double)(s.resident*s.numCUs);
+        share = std::min(0.25, std::max(0.03, -share/std::max(1.0, sets)));
+    }
+    if (share > 0.0 && share < 0.9 && divide >= 2)
+        split_tail_regions(s, c, slots, share, divide);
+    return true;
+}
+
+// k_bounce's LDS plan for the scene: does it close ranks through the waves' shading pools (returned)?  Pools (25 KB of LDS per workgroup)
+// where rays can LEAVE the scene -- veach 1515 -> 1866 Msamples/s, features 755 -> 865, env_loft 3598 -> 3793, gloss 7584 -> 7934 when they
+// were introduced; between two facing planes every ray hits something and the pools only cost (cornell 2919 -> 2894) -- and where they do not
+// cost the third resident workgroup (features' 32-KB arena + pools would leave two).  The kernel runs four waves per SIMD = four workgroups
+// per CU by its registers (kBounceWaves); *resident, which the grid and the region cut are sized by, is what the LDS lets be resident.
+bool plan_bounce(const tinsel_hip* r, int* resident)
+{
+    const size_t perCU = 160u*1024u;
+    const size_t lds = stack_bytes(r), withPool = lds + kPoolWords*sizeof(uint32_t);
+    const bool want = r->tune.repack >= 0 ? r->tune.repack != 0 : !r->sceneEnclosed;      // tinsel_hip_tuning::repack 0 / 1: never / always; default: open scenes
+    const bool pools = want && withPool*3 <= perCU && withPool <= (size_t)r->sharedMemLimit;
+    // the workgroups per CU the grid and the region cut are sized by = the ones that ARE resident: four by the registers, fewer where a
+    // workgroup's LDS (stacks + staged arena + pools) says so (ADVICE r05: with pools, three fit where four times their LDS do not)
+    const size_t ldsPerGroup = std::max<size_t>(1, pools ? withPool : lds);
+    *resident = (int)std::max<size_t>(1, std::min<size_t>((size_t)kBounceWaves, perCU/ldsPerGroup));
+    return pools;
+}
+
+// What a render call's batches run, decided once per call (plan_batch), each field from the ones before it: pipeline, overlap, capacity, k_walk,
+// the scan kernels' stack and LDS, k_swalk, the split pipeline's light and shade launches, k_bounce's pools and resident workgroups.
+// render_impl, ensure_batch / alloc_dense, render_batch and the launch helpers read it; none decides again.
+struct BatchPlan
+{
+    int pipeline = TINSEL_PIPELINE_MEGAKERNEL;
+    // a batch of `slots` paths (ps.rad) traced as `lanes` chunks of at most chunkPasses passes, each in a lane of stateSlots paths
+    int lanes = 1, chunkPasses = 1;
+    size_t slots = 0, stateSlots = 0;
+    // a lane's arrays (alloc_dense): positions, regions, shadow rays per path they hold (0: the fused kernel's, which keeps none)
+    size_t capacity = 0, maxRegions = 0;
+    int K = 0;
+    // k_walk (split, paired): its records fit (allocated; `walkRays` rays per position), and it runs (not while the detail counters count the inline walk)
+    bool walkRecords = false, walk = false;
+    size_t walkRays = 0;
+    // the scan kernels (walked_only_level: their lean variants with the scene-level stack only): variant, stack entries, dynamic LDS
+    int walkedLevel = 0, stackScan = 0;
+    uint32_t ldsTrace = 0;
+    // a walk list is allocated (k_walk's, or k_swalk's for scenes the flat scan cannot take): k_seg_prefix bounds the regions
+    bool workList = false;
+    bool sceneWalk = false;             // k_swalk in the place of k_extend / k_shadow (split)
+    // split: the light samples drawn by k_extend (lightsInMixed: its variant for a staged arena with meshes in HBM); k_shade_sorted;
+    // the arena k_shade stages and the LDS of k_shade and k_lights
+    bool lightsInMixed = false, lightsInExtend = false, shadeSorted = false;
+    uint32_t arenaLdsShade = 0, ldsShade = 0, ldsLights = 0;
+    bool pools = false;                 // fused: k_bounce's shading pools (plan_bounce; its resident workgroups are regions.resident)
+    RegionSpec regions;                 // how a batch is cut (render_batch bounds it by the lane's arrays)
+};
+
+// perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve)
+BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap)
+{
+    BatchPlan p;
+    p.pipeline = resolve_pipeline(r);
+    const bool fused = p.pipeline == TINSEL_PIPELINE_WAVEFRONT, split = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT,
+               paired = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED;
+
+    // Overlapped chunks.  A batch of several passes can be traced as TWO chunks of passes on two streams, each with its own dense state
+    // (a lane, ensure_batch), both writing their slots of the one radiance array; a chunk's accumulate kernel follows its own trace
+    // on its own stream and the previous chunk's accumulate by an event -- the framebuffer adds keep the reference's pass order, so no
+    // bit changes (tests/test_gpu_switches.py) -- and the two chunks' kernels fill each other's tails.  Measured built in
+    // (profiles/r04_k_ab_overlap.md, Msamples/s off -> on): it pays where a bounce is MANY SHORT launches that leave the chip half empty
+    // at their ends -- the scene-level walk of scenes beyond the flat scan (k_seg_* + k_swalk twice a bounce: many_spheres 2118 -> 2304)
+    // -- and nowhere else: the fused kernel is one launch that already ends in short regions (cornell 1024^2 x 20 passes 4173 -> 4145,
+    // x 256 4338 -> 4268, veach 4K 2838 -> 2846, gloss 10972 -> 10588, a 1 M-path batch 2748 -> 2406: two launches, two tails);
+    // k_walk's workgroups take a CU's whole LDS and gain nothing from a neighbour (the 524k-triangle config 2223 -> 2114, glass 1426 ->
+    // 1418).  (Two RENDERERS on two streams had looked like +4 % on cornell, profiles/r04_j_two_streams.txt: that was the host's
+    // share of a call overlapping, not the device's.)  Default: scenes whose scene level is walked by k_swalk, batches of 8 Mi paths
+    // or more.  tinsel_hip_tuning::overlap = 0 / 1: never / wherever a batch has two passes (A/B, tests).
+    // (Decided before the capacity, so by the walk a scene asks for rather than by whether its records fit: walkRecords.)
+    p.chunkPasses = perBatch;
+    {
+        const size_t minPaths = (size_t)8u << 20;
+        const bool can = mayOverlap && perBatch >= 2 && p.pipeline != TINSEL_PIPELINE_MEGAKERNEL;
+        const bool sceneWalked = split && !r->scene.flatScan && r->tune.scene_walk != 0 && !r->countDetail && !(r->walkPrims.count > 0 && r->walkEnabled);
+        const bool want = r->tune.overlap >= 0 ? r->tune.overlap != 0 : (sceneWalked && perPass*(size_t)perBatch >= minPaths);
+        if (can && want)
+        {
+            p.chunkPasses = (perBatch + 1)/2;
+            p.lanes = 2;
+        }
+    }
+    p.slots = perPass*(size_t)perBatch;
+    p.stateSlots = perPass*(size_t)p.chunkPasses;
+
+    p.K = (split || paired) ? r->neePerPath : 0;
+    p.maxRegions = max_regions(r->numCUs, grid_mult(r));
+    p.capacity = (p.stateSlots + p.maxRegions*kWave + kWave - 1)/kWave*kWave;      // a region is a whole number of waves long
+
+    // k_walk: one 32-B closest hit per (ray, walked primitive), by position, fewer than 2^31 of them.  Split: extension and shadow rays share
+    // the buffer (K rays per position, at least one); paired: K + 1 rays per position
+    p.walkRays = split ? (size_t)std::max(p.K, 1) : (size_t)p.K + 1;
+    p.walkRecords = (split || paired) && r->walkPrims.count > 0 && r->walkEnabled &&
+                    (double)p.capacity*(double)p.walkRays*r->walkPrims.count < 2147483648.0;
+    p.walk = p.walkRecords && !r->countDetail;
+
+    p.walkedLevel = p.walk ? walked_only_level(r) : 0;
+    p.stackScan = p.walkedLevel ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
+    p.ldsTrace = (uint32_t)(((size_t)p.stackScan*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes);
+
+    p.workList = p.walkRecords || (split && !r->scene.flatScan);
+    // (not where k_walk does the walking: what is left for the scan kernels is too short for the two extra launches per
+    // bounce to pay -- glass 1087 -> 1077, config 3 1891 -> 1881; many_spheres, scene BVH walked inline, 1168 -> 1290)
+    // scenes the flat scan cannot take (more than 64 primitives): the scene-level walk with ray replacement (k_swalk, tn_swalk.h)
+    // in the place of k_extend / k_shadow; the detail counters count the inline walks
+    p.sceneWalk = split && r->tune.scene_walk != 0 && !r->scene.flatScan && !r->countDetail && !p.walk;
+
+    // the lean k_extend draws the light samples itself (tn_launch.h launches it when walkedOnly and not counting)
+    // ... and so does the variant for a staged arena with meshes in HBM (glass): without the SLP vectoriser it fits 128 VGPRs and
+    // saves k_lights' pass over the path state (k_extend 5.7 + k_lights 7.1 -> 11.2 ms per 32 passes, glass 1366 -> 1425 Msamples/s;
+    // round 2, 170 VGPRs: 29.1 apart, 31.5 together; profiles/r03_k_ab_lights_in_extend.txt)
+    const bool mixedArena = !r->scene.allInArena && r->scene.arenaLdsBytes != 0 && r->scene.arenaLdsBytes == r->scene.arenaBytes;
+    p.lightsInMixed = split && !p.walkedLevel && !r->countDetail && mixedArena && !(r->tune.scene_walk != 0 && !r->scene.flatScan);
+    p.lightsInExtend = p.walkedLevel != 0 || p.lightsInMixed;
+    // k_shade has no traversal stacks in LDS and reads a material per path: an arena too large to sit beside the stacks of the
+    // trace kernels (32 KB) is still staged by it up to 60 KB (many_spheres, 39 KB of primitive and material records: k_shade
+    // 7.8 -> 6.7 ms; staged in the trace kernels too it costs them their fourth wave per SIMD, 1380 -> 1280 Msamples/s, and
+    // k_lights reads too little of it to repay the copy, 2.7 -> 3.1 ms)
+    p.arenaLdsShade = (r->scene.arenaLdsBytes == 0 && r->scene.arenaBytes <= 61440u && r->tune.lds_scene != 0) ? r->scene.arenaBytes : r->scene.arenaLdsBytes;
+    p.ldsShade = r->scene.allInArena ? r->scene.arenaBytes : p.arenaLdsShade;
+    p.ldsLights = r->scene.allInArena ? r->scene.arenaBytes : r->scene.arenaLdsBytes;
+    // k_shade_sorted takes a region's paths class by class (tn_kernels.h): chosen PER SCENE.  It pays where a good share of a
+    // bounce's paths are rays that LEFT the scene (a cheap class that otherwise idles through its wave-mates' shading) and the
+    // path state is not already ordered by k_walk's front / back split: many_spheres 2087 -> 2122 Msamples/s, and in the split
+    // pipeline veach 1902 -> 2003, features 1047 -> 1093; it loses in an enclosed scene (glass: no ray leaves, 17.5 -> 19.3 ms) and
+    // where k_walk runs (the 524k-triangle config 6.47 -> 6.86 ms) (profiles/r03_g_ab_shade_sorted.txt, r04_e_rates.md).
+    // tinsel_hip_tuning::shade_sorted = 0 / 1 forces either arm (A/B, tests).
+    p.shadeSorted = (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !p.walk)) &&
+                    (size_t)p.ldsShade + kShadeListWords*sizeof(uint32_t) <= (size_t)r->sharedMemLimit;
+
+    int resident = kBounceWaves;
+    if (fused)
+        p.pools = plan_bounce(r, &resident);
+    p.regions = region_spec(r->tune, r->numCUs, r->neePerPath, fused, resident);
+    return p;
+}
+
+// The wavefront pipelines' state (SplitState, tn_kernels.h) of one lane: by POSITION, two buffers of everything a bounce rewrites; for the
+// split pipeline also what its kernels hand to each other (hit, shadow rays and their results), for the paired one its light samples;
+// k_walk's records and the walk list where the plan has them
+int alloc_dense(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& lane, int maxDepth)
+{
+    const size_t K = (size_t)p.K, cap = p.capacity, maxRegions = p.maxRegions;
+    SplitState& ss = lane.ss;
+    memset(&ss, 0, sizeof(ss));
+    for (int b = 0; b < 2; ++b)
+        if (batch_alloc(r, &ss.rayO[b], cap) || batch_alloc(r, &ss.rayD[b], cap) || batch_alloc(r, &ss.thr[b], cap) ||
+            batch_alloc(r, &ss.rad[b], cap) || batch_alloc(r, &ss.rngId[b], cap))
+            return -1;
+    if (batch_alloc(r, &ss.segFront, maxRegions*((size_t)maxDepth + 2)) || batch_alloc(r, &ss.segBack, maxRegions*((size_t)maxDepth + 2)) ||
+        batch_alloc(r, &lane.regionOrder, maxRegions/(kBlock/kWave)) || batch_alloc(r, &lane.regionOrderNee, maxRegions/(kBlock/kWave)))
+        return -1;
+    ss.capacity = (uint32_t)cap;
+    ss.neePerPath = (int32_t)K;
+    lane.splitCap = cap;
+    lane.splitMaxRegions = (uint32_t)maxRegions;
+    if (p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED)
+    {
+        // the K pending light samples of every path, by position, double-buffered like the state (tn_paired.h)
+        for (int b = 0; b < 2; ++b)
+            if (batch_alloc(r, &ss.pairThr[b], K ? cap : 1) || batch_alloc(r, &ss.pairRay[b], cap*K*2) || batch_alloc(r, &ss.pairPend[b], K > 1 ? cap*K*2 : cap))     // (sample k's two records at (2k, 2k + 1)*cap; sample 0 has no second one)
+                return -1;
+    }
+    if (p.pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT)
+        if (batch_alloc(r, &ss.hit, cap) || batch_alloc(r, &ss.hitPrim, cap) || batch_alloc(r, &ss.pathNee, K ? cap : 1) ||
+            batch_alloc(r, &ss.neeRay, cap*K*2) || batch_alloc(r, &ss.neeSky, r->scene.probe.valid ? cap : 1) ||
+            batch_alloc(r, &ss.neeTime, K ? cap : 1) || batch_alloc(r, &ss.neeRes, cap*K) ||
+            batch_alloc(r, &ss.neeFront, maxRegions*(size_t)maxDepth) || batch_alloc(r, &ss.neeBack, maxRegions*(size_t)maxDepth))
+            return -1;
+    if (p.walkRecords && batch_alloc(r, &lane.walkRec, cap*p.walkRays*(size_t)r->walkPrims.count*2))
+        return -1;
+    if (p.workList && (batch_alloc(r, &lane.walkList, cap) || batch_alloc(r, &lane.segPrefix, maxRegions + 1)))
+        return -1;
+    return 0;
+}
+
+// the batch buffers for a render call's plan: the radiance of p.slots paths, p.lanes lanes of dense state; kept where they hold the plan
+int ensure_batch(tinsel_hip* r, const BatchPlan& p, int maxDepth)
+{
+    const int K = r->neePerPath;
+    const tinsel_hip::DenseLane& lane = r->lane[0];
+    if (r->batchSlots >= p.slots && r->batchStateSlots >= p.stateSlots && r->batchLanes >= p.lanes && r->batchNee == K && r->batchDepth >= maxDepth &&
+        r->batchPipeline == p.pipeline && (lane.walkRec != nullptr) == p.walkRecords && (lane.walkList != nullptr) == p.workList)
+        return 0;
+    free_batch(r);
+
+    // the radiance of finished paths by slot is what every pipeline hands to the accumulate kernels
+    PathState& ps = r->ps;
+    memset(&ps, 0, sizeof(ps));
+    if (batch_alloc(r, &ps.rad, p.slots))
+        return -1;
+    if (p.pipeline != TINSEL_PIPELINE_MEGAKERNEL)
+        for (int k = 0; k < p.lanes; ++k)
+            if (alloc_dense(r, p, r->lane[k], maxDepth))
+                return -1;
+
+    // slots of other shards are never written (gen_slot): keep their radiance at zero for the test hook
+    HIP_TRY(hipMemset(ps.rad, 0, sizeof(float4)*p.slots));
+    // (a memset of device memory only enqueues on the null stream, and the kernels that follow may run on a NON-BLOCKING stream
+    // -- a group member's, the look-ahead's -- which the null stream does not order: without this wait the zeroes could land on
+    // radiance a kernel had already written.  Allocation path only.)
+    HIP_TRY(hipStreamSynchronize(nullptr));
+
+    r->ctl.stats = r->statsDev;
+    r->batchSlots = p.slots;
+    r->batchStateSlots = p.stateSlots;
+    r->batchLanes = p.lanes;
+    r->batchNee = K;
+    r->batchDepth = maxDepth;
+    r->batchPipeline = p.pipeline;
+    return 0;
 }
 
 // k_seg_prefix stages one count per region in dynamic LDS beside 64 B of static: what a launch may ask for (prepare_path_kernels raises
@@ -382,12 +647,27 @@ uint32_t seg_prefix_max_regions(tinsel_hip* r)
     return (uint32_t)std::max(0, r->segPrefixLds/4);
 }
 
+// k_seg_prefix's walk list visits the regions a golden-section step apart: every workgroup's static range gets the same mix of rays
+// (k_walk's lesson; in k_swalk's index order a 256-thread grid of 8 workgroups per CU took 14.4 ms where 32 per CU took 9.2)
+uint32_t seg_step(uint32_t numRegions)
+{
+    uint32_t step = (uint32_t)(numRegions*0.6180339887) | 1u;
+    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
+    while (step > 1 && gcd(step, numRegions) != 1)
+        step -= 1;
+    if (step >= numRegions || numRegions > 65535u)       // k_seg_prefix multiplies in 32 bits
+        step = 1;
+    return step;
+}
+
 // k_walk (tn_walk.h): closest hits of the front rays of `queue` against the large meshes in HBM, ahead of the scan kernel.
 // One 1024-thread workgroup per CU whose LDS holds the traversal stacks and, in what is left of the 160 KB, the top of
 // the walked trees; trees too deep for that (a device-built LBVH of 524k triangles: 48 entries per lane) run 256-thread
 // workgroups without a staged top.
 // (mixed: the paired pipeline's walk -- K shadow rays + the extension ray of every queued position, tn_paired.h)
-int launch_walk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* regionCounts, bool shadowRays, bool mixed = false)
+// `slots`: the paths of the batch (or chunk) lane L traces
+int launch_walk(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs a, size_t slots, const uint32_t* regionCounts,
+                bool shadowRays, bool mixed = false)
 {
     // (measured and settled, profiles/EXPERIMENTS.md: one resident set of workgroups; a refill once 24 lanes idle; a triangle phase once 8 wait)
     const int gridMult = r->tune.walk_grid_mult > 0 ? r->tune.walk_grid_mult : 1, refillMin = r->tune.walk_refill_min > 0 ? r->tune.walk_refill_min : 24, leafMin = r->tune.walk_leaf_min > 0 ? r->tune.walk_leaf_min : 8;
@@ -395,34 +675,26 @@ int launch_walk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* reg
     prepare_kernels_once(r);
     // the work list: the front entries of every region (paths / shadow-ray bundles whose ray enters a walked mesh's box)
     const SplitState& ss = a.ss;
-    // the list visits the regions a golden-section step apart
-    uint32_t step = (uint32_t)(ss.numRegions*0.6180339887) | 1u;
-    {
-        auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-        while (step > 1 && gcd(step, ss.numRegions) != 1)
-            step -= 1;
-        if (step >= ss.numRegions || ss.numRegions > 65535u)       // k_seg_prefix multiplies in 32 bits
-            step = 1;
-    }
+    const uint32_t step = seg_step(ss.numRegions);
     {
         ScopedTimer t(r, KN_SEG, st);
         if (ss.numRegions > seg_prefix_max_regions(r))
             return fail("k_seg_prefix: " + std::to_string(ss.numRegions) + " regions do not fit its LDS (tinsel_hip_tuning::grid_mult too large for this device)");
-        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, regionCounts, (const uint32_t*)nullptr, ss.numRegions, step, r->segPrefix);
-        hipLaunchKernelGGL(k_seg_expand, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, regionCounts, (const uint32_t*)r->segPrefix, ss, r->walkList);
+        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, regionCounts, (const uint32_t*)nullptr, ss.numRegions, step, L.segPrefix);
+        hipLaunchKernelGGL(k_seg_expand, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, regionCounts, (const uint32_t*)L.segPrefix, ss, L.walkList);
     }
     WalkJob& job = a.walk;
-    job.queue = r->walkList;
-    job.frontCount = r->segPrefix + ss.numRegions;
+    job.queue = L.walkList;
+    job.frontCount = L.segPrefix + ss.numRegions;
     job.rayO = ss.rayO[a.bounce & 1];
     job.rayD = ss.rayD[a.bounce & 1];
     job.nee = ss.neeRay;
     job.neeStride = ss.capacity;
     job.neeTime = ss.neeTime;
-    job.rec = r->walkRec;
+    job.rec = L.walkRec;
     job.neePerPath = shadowRays ? r->neePerPath : 0;
     job.mixed = 0;
-    if (r->lastPipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED)
+    if (p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED)
     {
         job.nee = ss.pairRay[a.bounce & 1];
         job.mixed = mixed ? 1 : 0;
@@ -478,7 +750,7 @@ int launch_walk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* reg
     // (k_walk_rays, whatever the number of walked primitives: ADVICE r05)
     if (!a.walkSingle && (ss.capacity >= (1u << 27) || r->neePerPath >= 32))
         return fail("k_walk_rays: batch too large (>= 2^27 positions) or too many shadow rays per path (>= 32): lower tinsel_hip_tuning::batch_paths");
-    const size_t items = r->lastBatchSlots*(size_t)((shadowRays && r->neePerPath > 1 ? r->neePerPath : 1) + (mixed ? 1 : 0));
+    const size_t items = slots*(size_t)((shadowRays && r->neePerPath > 1 ? r->neePerPath : 1) + (mixed ? 1 : 0));
     const int perCU = big ? gridMult*(twoPerCU ? 2 : 1) : gridMult*4;
     a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + block - 1)/block, (size_t)r->numCUs*(size_t)perCU));
     a.walkBig = big ? (twoPerCU ? 2 : 1) : 0;
@@ -488,19 +760,19 @@ int launch_walk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* reg
         // the overflow columns are sized for the WIDEST grid this function launches (numCUs x perCU workgroups), once: nothing is freed or
         // allocated between the launches of a batch
         const size_t need = (size_t)r->numCUs*(size_t)perCU*(size_t)block*(size_t)(entries - ldsEntries);
-        if (r->walkOverflowCap < need)
+        if (L.walkOverflowCap < need)
         {
-            if (r->walkOverflow)
+            if (L.walkOverflow)
             {
                 (void)hipDeviceSynchronize();       // (another stream's launch may still use the old columns)
-                (void)hipFree(r->walkOverflow);
+                (void)hipFree(L.walkOverflow);
             }
-            r->walkOverflow = nullptr;
-            r->walkOverflowCap = 0;
-            if (hipMalloc((void**)&r->walkOverflow, need*sizeof(uint32_t)) == hipSuccess)
-                r->walkOverflowCap = need;
+            L.walkOverflow = nullptr;
+            L.walkOverflowCap = 0;
+            if (hipMalloc((void**)&L.walkOverflow, need*sizeof(uint32_t)) == hipSuccess)
+                L.walkOverflowCap = need;
         }
-        job.overflow = r->walkOverflow;
+        job.overflow = L.walkOverflow;
         job.overflowEntries = entries - ldsEntries;
         if (!job.overflow)
             return fail("k_walk: no memory for the stack overflow");
@@ -512,31 +784,23 @@ int launch_walk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* reg
 
 // k_swalk (tn_swalk.h): the scene-level walk with ray replacement, for scenes the flat scan cannot take.  The list: every live
 // entry of every region (front and back), regions in index order -- the workgroups' static ranges are image patches, coherent rays.
-int launch_swalk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* front, const uint32_t* back, bool shadowRays)
+int launch_swalk(tinsel_hip* r, const tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs a, size_t slots, const uint32_t* front, const uint32_t* back,
+                 bool shadowRays)
 {
     const int refillMin = 32, leafMin = 16;         // (settled: profiles/r03_d_ab_swalk.txt, r03_e_ab_swalk.txt)
     const bool noLds = r->tune.swalk_lds == 0;
     const SplitState& ss = a.ss;
-    // the list visits the regions a golden-section step apart: every workgroup's static range gets the same mix of rays
-    // (k_walk's lesson; in index order a 256-thread grid of 8 workgroups per CU took 14.4 ms where 32 per CU took 9.2)
-    uint32_t step = (uint32_t)(ss.numRegions*0.6180339887) | 1u;
-    {
-        auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-        while (step > 1 && gcd(step, ss.numRegions) != 1)
-            step -= 1;
-        if (step >= ss.numRegions || ss.numRegions > 65535u)
-            step = 1;
-    }
+    const uint32_t step = seg_step(ss.numRegions);
     {
         ScopedTimer t(r, KN_SEG, st);
         if (ss.numRegions > seg_prefix_max_regions(r))
             return fail("k_seg_prefix: " + std::to_string(ss.numRegions) + " regions do not fit its LDS");
-        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, front, back, ss.numRegions, step, r->segPrefix);
-        hipLaunchKernelGGL(k_seg_expand_all, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, front, back, (const uint32_t*)r->segPrefix, ss, r->walkList);
+        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, front, back, ss.numRegions, step, L.segPrefix);
+        hipLaunchKernelGGL(k_seg_expand_all, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, front, back, (const uint32_t*)L.segPrefix, ss, L.walkList);
     }
     SwalkJob& job = a.swalk;
-    job.list = r->walkList;
-    job.count = r->segPrefix + ss.numRegions;
+    job.list = L.walkList;
+    job.count = L.segPrefix + ss.numRegions;
     job.neePerPath = shadowRays ? r->neePerPath : 0;
     job.stackEntries = r->stackNeed;
     job.refillMin = std::min(64, std::max(1, refillMin));
@@ -550,7 +814,7 @@ int launch_swalk(tinsel_hip* r, hipStream_t st, LaunchArgs a, const uint32_t* fr
     a.swalkMode = big ? (allInArena ? 1 : 2) : 0;
     const int block = big ? 1024 : kBlock;
     const int gridMult = big ? 1 : 32;
-    const size_t items = r->lastBatchSlots*(size_t)(shadowRays && r->neePerPath > 1 ? r->neePerPath : 1);
+    const size_t items = slots*(size_t)(shadowRays && r->neePerPath > 1 ? r->neePerPath : 1);
     a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + block - 1)/block, (size_t)r->numCUs*(size_t)gridMult));
     if (big)
     {
@@ -645,9 +909,10 @@ size_t slots_per_pass(const tinsel_hip* r, int width, int height, int* tilesXOut
     return std::max<size_t>(1, (size_t)owned*r->shardTile*r->shardTile);
 }
 
-// The accumulate stage of a traced batch: adds the batch passes [fp.accBegin, fp.accEnd) to `target`.
-int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* target)
+// The accumulate stage of a traced batch: adds the batch passes [fp.accBegin, fp.accEnd), their radiance at `rad`, to `target`.
+int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* rad, float4* target)
 {
+    const PathState ps = { rad };
     const size_t npix = (size_t)fp.width*fp.height;
     ScopedTimer t(r, KN_ACCUMULATE, st);
     const int halo = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth);
@@ -679,208 +944,226 @@ int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, floa
                 wide = r->tune.accumulate == TINSEL_ACCUMULATE_WIDE;
             }
             if (span == 3 && piped)
-                hipLaunchKernelGGL((k_accumulate_piped<3>), dim3(tiles), dim3(kAccPipeThreads), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_piped<3>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, r->passSeeds, tileList);
             else if (span == 4 && piped)
-                hipLaunchKernelGGL((k_accumulate_piped<4>), dim3(tiles), dim3(kAccPipeThreads), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_piped<4>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, r->passSeeds, tileList);
             else if (span == 3 && wide)
-                hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
             else if (span == 4 && wide)
-                hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
             else if (span == 3)
-                hipLaunchKernelGGL((k_accumulate_tiled<3>), dim3(tiles), dim3(kBlock), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_tiled<3>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
             else if (span == 4)
-                hipLaunchKernelGGL((k_accumulate_tiled<4>), dim3(tiles), dim3(kBlock), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_tiled<4>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
             else
-                hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, r->ps, fp, target, r->passSeeds, tileList);
+                hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
         }
     }
     else
     {
         const int gridPix = (int)((npix + kBlock - 1)/kBlock);
-        hipLaunchKernelGGL(k_accumulate, dim3(gridPix), dim3(kBlock), 0, st, r->ps, fp, target, r->passSeeds);
+        hipLaunchKernelGGL(k_accumulate, dim3(gridPix), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds);
     }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Blocks of the streaming kernels' grid = a quarter of the regions the batch is cut into (one region per wave, SplitState,
-// tn_kernels.h).  A wave works through its region 64 entries at a time and a round is as long as its slowest lane, so
-// regions should stay long as paths die (the last round of a region is the ragged one), yet there must be enough of them to
-// balance: ~1024 positions per region, between 2 and 32 blocks per CU.  Fused kernel, cornell: a 1 M-path batch 1417 / 1520 /
-// 1655 / 1747 Msamples/s at 16 / 8 / 4 / 2 blocks per CU (regions of 64 ... 512); a 64 Mi batch 2644 / 2735 / 2803 at 8 / 16 /
-// 32 (regions of 8192 / 4096 / 2048).
-int streaming_grid(const tinsel_hip* r, size_t slots, int pipeline)
+// The batch's regions in lane L: at most `grid` region groups (cut_regions, bounded by the lane's arrays) into a.ss; on return *grid is the
+// number of groups.  The lane keeps the cut and the batch's paths for tinsel_hip_queue_counts.
+int cut_batch(const BatchPlan& p, tinsel_hip::DenseLane& L, LaunchArgs& a, size_t slots, int* grid)
 {
-    // (where the fused kernel's waves share their workgroup's regions -- three or more shadow rays per bounce, k_bounce -- the
-    // regions may be twice as long: features 707 -> 740, features + probe 595 -> 622, veach +-0)
-    const size_t regionTarget = (pipeline == TINSEL_PIPELINE_WAVEFRONT && r->neePerPath >= 3) ? 2048 : 1024;
-    const size_t perBlock = regionTarget*(kBlock/kWave);
-    const size_t blocks = (slots + perBlock - 1)/perBlock;
-    // (at least as many workgroups as the chip holds at once -- k_bounce's resident workgroups per CU, three for the split pipeline's kernels --
-    // where the batch has that many 256-path pieces: a 1 M-path batch would otherwise leave the last wave slot empty)
-    const int gridMin = pipeline == TINSEL_PIPELINE_WAVEFRONT ? r->bounceWaves : 3;
-    const size_t lo = std::min<size_t>((size_t)r->numCUs*(size_t)gridMin, (slots + kBlock - 1)/kBlock), hi = (size_t)r->numCUs*(size_t)grid_mult(r);
-    size_t grid = std::max<size_t>(1, std::min(hi, std::max(lo, blocks)));
-    // The workgroups that HAVE work (regions are a whole number of waves long, so fewer than the grid may) as close to a whole number
-    // of resident sets (gridMin per CU) as the region length allows within +-25 %: the last set of a launch is then full instead
-    // of, say, two thirds empty.  Glass at 20 passes per batch 1262 -> 1291 Msamples/s, the 524k-triangle config 2024 -> 2034, the
-    // fused configs +-0 (profiles/r03_s_ab_grid_round.txt)
-    const size_t resident = (size_t)r->numCUs*(size_t)gridMin;
-    if (grid > 2*resident)
+    RegionSpec s = p.regions;
+    s.maxRegions = L.splitMaxRegions;
+    s.capacity = L.splitCap;
+    RegionCut c;
+    if (!cut_regions(s, slots, *grid, c))
+        return fail("render: path buffers too small for this batch");
+    a.ss.numRegions = c.numRegions;
+    a.ss.regionLen = c.regionLen;
+    a.ss.bigRegions = c.bigRegions;
+    a.ss.shortLen = c.shortLen;
+    L.regions = c.numRegions;
+    L.paths = (uint32_t)slots;
+    *grid = c.grid();
+    return 0;
+}
+
+// The split and paired pipelines' batch: cut into regions in lane L and its paths generated.  On return *grid is the launches' grid.
+// (k_seg_prefix stages one count per region in LDS, (sharedMemLimit - 1024)/4 of them at most: where a walk list is built the grid is
+// clamped to what fits)
+int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots, int* grid)
+{
+    *grid = streaming_grid(p.regions, slots);
+    if (p.workList)
+        *grid = std::max(1, std::min(*grid, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
+    if (cut_batch(p, L, a, slots, grid))
+        return -1;
+    ScopedTimer t(r, KN_GENERATE, st);
+    a.grid = *grid;
+    launch_path(r, PK_GENERATE, a, st);
+    return 0;
+}
+
+// region groups, longest first (k_region_order, tn_kernels.h), by the live entries of the regions' fronts and backs
+void order_regions(tinsel_hip* r, hipStream_t st, const LaunchArgs& a, const uint32_t* front, const uint32_t* back, uint32_t* out)
+{
+    ScopedTimer t(r, KN_SEG, st);
+    hipLaunchKernelGGL(k_region_order, dim3(1), dim3(kOrderBlock), 0, st, front, back, a.ss.numRegions, out);
+}
+
+// the fused pipeline: ONE launch takes every region through all the bounces (k_bounce, tn_kernels.h)
+int trace_fused(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots)
+{
+    int grid = streaming_grid(p.regions, slots);
+    if (cut_batch(p, L, a, slots, &grid))
+        return -1;
+    a.grid = grid;
+    // (the shading pools and the waves per SIMD were planned before the batch was cut: plan_bounce)
+    if (p.pools)
     {
-        auto busy = [&](size_t g) {         // workgroups with work for a grid of g (set_regions' region length)
-            const size_t regions = g*(kBlock/kWave);
-            const size_t len = ((slots + regions - 1)/regions + kWave - 1)/kWave*kWave;
-            return (slots + len*(kBlock/kWave) - 1)/(len*(kBlock/kWave));
-        };
-        size_t best = grid;
-        double bestWaste = 2.0;
-        for (size_t g = std::max(grid*3/4, 2*resident); g <= std::min(hi, grid*5/4); g += std::max<size_t>(1, resident/16))
+        a.fp.repack = 1;
+        a.ldsBytes += (uint32_t)(kPoolWords*sizeof(uint32_t));
+    }
+    // bounces > 0: a workgroup's four regions as ONE stream dealt to its waves -- where a round is long (three or more shadow rays)
+    // and where the regions are short (a small batch: the ragged last round of every region and bounce weighs more)
+    {
+        const int shareLen = 512;       // cornell 256^2 x 16 passes (regions of 384): 2258 -> 2311 Msamples/s; 1024^2 x 20 (regions of 2048) +0.3 %
+        a.fp.share = r->tune.bounce_share >= 0 ? (r->tune.bounce_share != 0) : (r->neePerPath >= 3 || (int)a.ss.regionLen <= shareLen);
+    }
+    // (Workgroup b takes region group b: a golden-section step, which k_walk's static ranges need, loses here -- the dispatcher already
+    // hands workgroups out dynamically: veach 1970 -> 1904 Msamples/s, features 898 -> 880, cornell 2999 -> 2979.  The per-bounce launches
+    // of rounds 1-2, regions longest first, went in round 5.)
+    a.bounce = 0;
+    a.bounceEnd = a.fp.maxDepth;
+    a.order = nullptr;
+    ScopedTimer t(r, KN_BOUNCE, st);
+    launch_path(r, PK_BOUNCE, a, st);
+    return 0;
+}
+
+// the paired pipeline: ONE k_walk and ONE streaming kernel per bounce (tn_paired.h): walk { shadow rays of bounce b - 1, extension rays of bounce b }, then k_step(b)
+int trace_paired(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots)
+{
+    int grid = 0;
+    a.walkedOnly = p.walkedLevel;
+    if (cut_and_generate(r, p, L, st, a, slots, &grid))
+        return -1;
+    const size_t W = a.ss.numRegions;
+    const int K = r->neePerPath, maxDepth = a.fp.maxDepth;
+    // (the step after the last bounce only resolves the last bounce's light samples: nothing to do without lights)
+    const int steps = maxDepth + (K > 0 ? 1 : 0);
+    for (int bounce = 0; bounce < steps; ++bounce)
+    {
+        a.bounce = bounce;
+        a.order = nullptr;
+        if (p.walk)
         {
-            const size_t b = busy(g);
-            const double sets = (double)b/(double)resident;
-            const double waste = std::ceil(sets) - sets;        // empty fraction of the last resident set
-            if (waste < bestWaste - 1e-9)
+            a.grid = grid;
+            const bool first = bounce == 0, last = bounce >= maxDepth;
+            if (launch_walk(r, p, L, st, a, slots, L.ss.segFront + (size_t)bounce*W, /*shadowRays*/ !first && K > 0, /*mixed*/ !first && !last && K > 0))
+                return -1;
+        }
+        // k_step's region groups longest first (k_region_order) where paths are deep: by bounce 6 most regions are nearly empty and the few
+        // full ones should not start last -- transmission.tin (depth 16) k_step 13.45 -> 11.81 ms, 1329 -> 1396 Msamples/s; at depth 4 the sort's
+        // launch costs what it saves (the 524k-triangle config 2562 / 2555: profiles/r06_r_ab_step_order.md)
+        if (bounce > 0 && maxDepth >= 6 && grid > r->numCUs*2)
+        {
+            order_regions(r, st, a, L.ss.segFront + (size_t)bounce*W, L.ss.segBack + (size_t)bounce*W, L.regionOrder);
+            a.order = L.regionOrder;
+        }
+        ScopedTimer t(r, KN_STEP, st);
+        a.grid = grid;
+        a.ldsBytes = p.ldsTrace;
+        a.stackEntries = p.stackScan;
+        launch_path(r, PK_STEP, a, st);
+    }
+    return 0;
+}
+
+// the split pipeline: per bounce k_walk / k_swalk, k_extend, k_lights, k_walk / k_swalk or k_shadow, k_shade
+int trace_split(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots)
+{
+    int grid = 0;
+    const uint32_t arenaLdsTrace = r->scene.arenaLdsBytes;
+    a.walkedOnly = p.walkedLevel;
+    a.lightsInExtend = p.lightsInMixed ? 1 : 0;
+    if (cut_and_generate(r, p, L, st, a, slots, &grid))
+        return -1;
+    const size_t W = a.ss.numRegions;
+    // (the trace kernels stride over the regions: one block per four regions like the others)
+    const bool ordered = !p.walk && grid > r->numCUs*2;
+    for (int bounce = 0; bounce < a.fp.maxDepth; ++bounce)
+    {
+        a.bounce = bounce;
+        // longest regions first (k_region_order, tn_kernels.h): the paths' order serves k_extend, k_lights and k_shade,
+        // the shadow-ray bundles' order k_shadow; bounce 0's regions are all full
+        a.order = nullptr;
+        if (ordered && bounce > 0)
+        {
+            order_regions(r, st, a, L.ss.segFront + (size_t)bounce*W, L.ss.segBack + (size_t)bounce*W, L.regionOrder);
+            a.order = L.regionOrder;
+        }
+        const uint32_t* const pathOrder = a.order;
+        a.grid = grid;
+        if (p.walk && launch_walk(r, p, L, st, a, slots, L.ss.segFront + (size_t)bounce*W, false))
+            return -1;
+        if (p.sceneWalk)
+        {
+            if (launch_swalk(r, L, st, a, slots, L.ss.segFront + (size_t)bounce*W, L.ss.segBack + (size_t)bounce*W, false))
+                return -1;
+        }
+        else
+        {
+            ScopedTimer t(r, KN_EXTEND, st);
+            a.ldsBytes = p.ldsTrace;
+            a.stackEntries = p.stackScan;
+            launch_path(r, PK_EXTEND, a, st);
+        }
+        if (r->neePerPath > 0)
+        {
+            if (!p.lightsInExtend)
             {
-                bestWaste = waste;
-                best = g;
+                ScopedTimer t(r, KN_LIGHTS, st);
+                a.ldsBytes = p.ldsLights;
+                launch_path(r, PK_LIGHTS, a, st);
+            }
+            if (p.walk && launch_walk(r, p, L, st, a, slots, L.ss.neeFront + (size_t)bounce*W, true))
+                return -1;
+            if (p.sceneWalk)
+            {
+                if (launch_swalk(r, L, st, a, slots, L.ss.neeFront + (size_t)bounce*W, L.ss.neeBack + (size_t)bounce*W, true))
+                    return -1;
+            }
+            else
+            {
+                if (ordered && bounce > 0)
+                {
+                    order_regions(r, st, a, L.ss.neeFront + (size_t)bounce*W, L.ss.neeBack + (size_t)bounce*W, L.regionOrderNee);
+                    a.order = L.regionOrderNee;
+                }
+                ScopedTimer t(r, KN_SHADOW, st);
+                a.ldsBytes = p.ldsTrace;
+                a.stackEntries = p.stackScan;
+                launch_path(r, PK_SHADOW, a, st);
+                a.order = pathOrder;
             }
         }
-        grid = best;
+        {
+            ScopedTimer t(r, KN_SHADE, st);
+            a.shadeSorted = p.shadeSorted ? 1 : 0;
+            a.ldsBytes = p.ldsShade + (p.shadeSorted ? (uint32_t)(kShadeListWords*sizeof(uint32_t)) : 0u);
+            a.stackEntries = p.stackScan;
+            a.scene.arenaLdsBytes = p.arenaLdsShade;
+            launch_path(r, PK_SHADE, a, st);
+            a.scene.arenaLdsBytes = arenaLdsTrace;
+        }
     }
-    return (int)grid;
-}
-
-int set_regions(tinsel_hip* r, LaunchArgs& a, size_t slots, int gridPersist)
-{
-    a.ss = r->ss;
-    a.ss.numRegions = (uint32_t)gridPersist*(kBlock/kWave);
-    a.ss.regionLen = (uint32_t)(((slots + a.ss.numRegions - 1)/a.ss.numRegions + kWave - 1)/kWave*kWave);
-    a.ss.bigRegions = a.ss.numRegions;
-    a.ss.shortLen = a.ss.regionLen;
-    if (a.ss.numRegions > r->splitMaxRegions || (size_t)a.ss.numRegions*a.ss.regionLen > r->splitCap)
-        return fail("render: path buffers too small for this batch");
-    r->lastRegions = a.ss.numRegions;
     return 0;
 }
 
-// The last `tailShare` of the batch's positions in regions 1/divide as long (SplitState::bigRegions / shortLen, tn_kernels.h): what the chip
-// works on when a launch runs out.  `maxRegions` bounds their number (the region arrays; k_seg_prefix's LDS): where the uniform cut is
-// already at the bound the long regions get longer.  Leaves `a` as set_regions made it when the batch is too small for any of that.
-void split_tail_regions(tinsel_hip* r, LaunchArgs& a, size_t slots, double tailShare, int divide, size_t maxRegions)
-{
-    const uint32_t per = kBlock/kWave;                        // regions per group
-    maxRegions = std::min<size_t>(maxRegions, r->splitMaxRegions);
-    if (a.ss.regionLen < (uint32_t)(kWave*divide*2) || a.ss.numRegions < 64u*per || maxRegions < 128u*per)
-        return;
-    const double factor = (1.0 - tailShare) + tailShare*(double)divide;
-    uint32_t L = a.ss.regionLen;
-    if ((double)slots*factor/(double)L + 2.0*per > (double)maxRegions)
-        L = (uint32_t)(((size_t)((double)slots*factor/(double)(maxRegions - 2*per)) + kWave)/kWave*kWave);
-    const uint32_t S = L/(uint32_t)divide/kWave*kWave;        // short regions: a multiple of 64 positions
-    const uint32_t big = (uint32_t)((double)slots*(1.0 - tailShare)/(double)L)/per*per;
-    const size_t covered = (size_t)big*L;
-    if (S < (uint32_t)kWave || big < per || covered >= slots)
-        return;
-    const size_t rest = slots - covered;
-    const uint32_t small = (uint32_t)((rest + (size_t)S*per - 1)/((size_t)S*per))*per;
-    if (big + small > maxRegions || (size_t)big*L + (size_t)small*S > r->splitCap)
-        return;
-    a.ss.regionLen = L;
-    a.ss.bigRegions = big;
-    a.ss.shortLen = S;
-    a.ss.numRegions = big + small;
-    r->lastRegions = a.ss.numRegions;
-}
-
-// A batch that ONE resident set of workgroups takes whole (cfg1: 256^2 x 16 passes = 683 region groups for 768 slots): two thirds of the CUs
-// get three groups, a third gets two, and the launch lasts as long as three.  Cut so that every CU gets TWO long groups -- three quarters of
-// the batch -- and the rest in groups a third as long, which the dispatcher deals out as slots come free: every CU ends up with the same
-// work.  cornell 256^2 x 16 passes 2402 -> 2670 Msamples/s, 512^2 x 4 2600 -> 2919, veach 256^2 x 16 1176 -> 1324 (call Z10).
-bool split_one_set(tinsel_hip* r, LaunchArgs& a, size_t slots)
-{
-    const uint32_t per = kBlock/kWave;
-    const size_t cus = (size_t)r->numCUs;
-    // (W workgroups resident per CU: W - 1 long groups per CU hold W/(W + 1) of the batch -- three waves: two groups, three quarters)
-    const size_t W = (size_t)r->bounceWaves;
-    if (W < 2)
-        return false;
-    const uint32_t L = (uint32_t)((slots*W/(W + 1))/((W - 1)*cus*per)/kWave*kWave);
-    if (L < 3u*kWave)
-        return false;
-    const uint32_t S = L/3/kWave*kWave;
-    const uint32_t big = (uint32_t)((W - 1)*cus)*per;
-    const size_t covered = (size_t)big*L;
-    if (covered >= slots)
-        return false;
-    const uint32_t small = (uint32_t)((slots - covered + (size_t)S*per - 1)/((size_t)S*per))*per;
-    if (big + small > r->splitMaxRegions || (size_t)big*L + (size_t)small*S > r->splitCap)
-        return false;
-    a.ss.regionLen = L;
-    a.ss.bigRegions = big;
-    a.ss.shortLen = S;
-    a.ss.numRegions = big + small;
-    r->lastRegions = a.ss.numRegions;
-    return true;
-}
-
-// set_regions + the short regions at the end.  The last eighth or so of the positions in regions a quarter as long: a workgroup's region group
-// is 0.75 ms of a 5 ms launch (cornell, 20 passes) and a launch ends when its last workgroup does.  k_bounce alone (round 3, call Z5):
-// cornell 1024^2 x 20 passes 3878 -> 4012 Msamples/s, x 8 3539 -> 3685, 512^2 x 16 2812 -> 3021, features 1183 -> 1292, veach 1080p
-// 2414 -> 2610 (profiles/r03_z5_ab_tail_split.md).  tinsel_hip_tuning::tail_split / tail_share / tail_divide (A/B).  On return *grid is the number
-// of region groups = the workgroups of a launch that gives every group its own.
-int cut_regions(tinsel_hip* r, LaunchArgs& a, size_t slots, int* grid, size_t maxRegions)
-{
-    if (set_regions(r, a, slots, *grid))
-        return -1;
-    double share = -0.5;
-    int divide = 4;
-    if (r->tune.tail_split == 0)
-        share = 0.0;
-    else if (r->tune.tail_split > 0)
-    {
-        share = (double)r->tune.tail_share;
-        divide = r->tune.tail_divide;
-    }
-    // (r->bounceWaves workgroups per CU are resident: plan_bounce)
-    if (share < 0.0 && maxRegions > 0 && (size_t)*grid <= (size_t)r->numCUs*r->bounceWaves && (size_t)*grid > (size_t)r->numCUs*(r->bounceWaves - 1) && split_one_set(r, a, slots))
-    {
-        *grid = (int)(a.ss.numRegions/(kBlock/kWave));
-        return 0;
-    }
-    if (share < 0.0)
-    {
-        // a negative share: that multiple of ONE resident set's part of the batch (r->bounceWaves workgroups per CU).  The default, half a
-        // set's part, against a fixed eighth: cornell x 20 passes 4036 -> 4059, x 64 4203 -> 4221, features 1289 -> 1298, veach 1080p
-        // 2610 -> 2621, gloss 10570 -> 10530 (call Z8)
-        const double sets = (double)*grid/(double)(r->bounceWaves*r->numCUs);
-        share = std::min(0.25, std::max(0.03, -share/std::max(1.0, sets)));
-    }
-    if (share > 0.0 && share < 0.9 && divide >= 2)
-        split_tail_regions(r, a, slots, share, divide, maxRegions);
-    *grid = (int)(a.ss.numRegions/(kBlock/kWave));
-    return 0;
-}
-
-// k_bounce's LDS plan for the scene: does it close ranks through the waves' shading pools (returned)?  Pools (25 KB of LDS per workgroup)
-// where rays can LEAVE the scene -- veach 1515 -> 1866 Msamples/s, features 755 -> 865, env_loft 3598 -> 3793, gloss 7584 -> 7934 when they
-// were introduced; between two facing planes every ray hits something and the pools only cost (cornell 2919 -> 2894) -- and where they do not
-// cost the third resident workgroup (features' 32-KB arena + pools would leave two).  The kernel runs four waves per SIMD = four workgroups
-// per CU by its registers (kBounceWaves); r->bounceWaves, which the grid and the region cut are sized by, is what the LDS lets be resident.
-bool plan_bounce(tinsel_hip* r)
-{
-    const size_t perCU = 160u*1024u;
-    const size_t lds = stack_bytes(r), withPool = lds + kPoolWords*sizeof(uint32_t);
-    const bool want = r->tune.repack >= 0 ? r->tune.repack != 0 : !r->sceneEnclosed;      // tinsel_hip_tuning::repack 0 / 1: never / always; default: open scenes
-    const bool pools = want && withPool*3 <= perCU && withPool <= (size_t)r->sharedMemLimit;
-    // the workgroups per CU the grid and the region cut are sized by = the ones that ARE resident: four by the registers, fewer where a
-    // workgroup's LDS (stacks + staged arena + pools) says so (ADVICE r05: with pools, three fit where four times their LDS do not)
-    const size_t ldsPerGroup = std::max<size_t>(1, pools ? withPool : lds);
-    r->bounceWaves = (int)std::max<size_t>(1, std::min<size_t>((size_t)kBounceWaves, perCU/ldsPerGroup));
-    return pools;
-}
-
-int render_batch(tinsel_hip* r, hipStream_t st, const CameraParams& cam, FrameParams fp, bool accumulate = true)
+// One batch -- or one overlapped chunk -- of passes fp.passBase .. + fp.numPasses, traced in lane L; the paths' radiance goes to rad[0, slots)
+int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams& cam, FrameParams fp, float4* rad,
+                 bool accumulate = true)
 {
     // path slots of this shard per pass and per batch (slot_pixel / slot_of, tn_kernels.h): rank-local numbering
     const size_t perPass = slots_per_pass(r, fp.width, fp.height, &fp.shardTilesX, &fp.shardOwnedTiles);
@@ -901,246 +1184,43 @@ int render_batch(tinsel_hip* r, hipStream_t st, const CameraParams& cam, FramePa
     fp.rrStart = r->rrStart;
     fp.repack = 0;
     fp.share = 0;
-    const int gridFlat = (int)std::max<size_t>(1, (slots + kBlock - 1)/kBlock);
-    const bool repackPlan = resolve_pipeline(r) == TINSEL_PIPELINE_WAVEFRONT && plan_bounce(r);
-    int gridPersist = streaming_grid(r, slots, resolve_pipeline(r));
-    // the trace kernels stride over the regions: by default one block per four regions like the others
-    int gridTrace = gridPersist;
-    r->lastBatchSlots = slots;
+    r->lastPipeline = p.pipeline;
 
-    const int pipeline = resolve_pipeline(r);
-    if (pipeline != r->batchPipeline)
-        return fail("render: path buffers were reserved for another pipeline");
-    r->lastPipeline = pipeline;
-
-    LaunchArgs a = batch_args(r, cam, fp);
-    if (pipeline == TINSEL_PIPELINE_MEGAKERNEL)
+    // what every launch of the batch shares
+    LaunchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene = r->scene;
+    a.ps.rad = rad;
+    a.ctl = r->ctl;
+    a.cam = cam;
+    a.fp = fp;
+    a.passSeeds = r->passSeeds;
+    a.walkRec = p.walk ? L.walkRec : nullptr;
+    a.walkPrims = (uint32_t)r->walkPrims.count;
+    a.bins = r->binPrims;
+    a.stackEntries = r->stackNeed;
+    a.countDetail = r->countDetail ? 1 : 0;
+    a.ldsBytes = (uint32_t)stack_bytes(r);
+    if (p.pipeline == TINSEL_PIPELINE_MEGAKERNEL)
     {
         ScopedTimer t(r, KN_MEGA, st);
-        a.grid = gridFlat;
+        a.grid = (int)std::max<size_t>(1, (slots + kBlock - 1)/kBlock);
         launch_path(r, PK_MEGA, a, st);
-    }
-    else if (pipeline == TINSEL_PIPELINE_WAVEFRONT)
-    {
-        if (cut_regions(r, a, slots, &gridPersist, r->splitMaxRegions))
-            return -1;
-        a.grid = gridPersist;
-        // (the shading pools and the waves per SIMD were planned before the batch was cut: plan_bounce)
-        if (repackPlan)
-        {
-            a.fp.repack = 1;
-            a.ldsBytes += (uint32_t)(kPoolWords*sizeof(uint32_t));
-        }
-        // bounces > 0: a workgroup's four regions as ONE stream dealt to its waves -- where a round is long (three or more shadow rays)
-        // and where the regions are short (a small batch: the ragged last round of every region and bounce weighs more)
-        {
-            const int shareLen = 512;       // cornell 256^2 x 16 passes (regions of 384): 2258 -> 2311 Msamples/s; 1024^2 x 20 (regions of 2048) +0.3 %
-            a.fp.share = r->tune.bounce_share >= 0 ? (r->tune.bounce_share != 0) : (r->neePerPath >= 3 || (int)a.ss.regionLen <= shareLen);
-        }
-        // ONE launch takes every region through all the bounces (k_bounce, tn_kernels.h).  (Workgroup b takes region group b: a golden-section
-        // step, which k_walk's static ranges need, loses here -- the dispatcher already hands workgroups out dynamically: veach 1970 -> 1904
-        // Msamples/s, features 898 -> 880, cornell 2999 -> 2979.  The per-bounce launches of rounds 1-2, regions longest first, went in round 5.)
-        a.bounce = 0;
-        a.bounceEnd = fp.maxDepth;
-        a.order = nullptr;
-        ScopedTimer t(r, KN_BOUNCE, st);
-        launch_path(r, PK_BOUNCE, a, st);
-    }
-    else if (pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED)
-    {
-        // ONE k_walk and ONE streaming kernel per bounce (tn_paired.h): walk { shadow rays of bounce b - 1, extension rays of bounce b }, then k_step(b)
-        const bool walk = walk_records(r) != nullptr;
-        const int walkedLevel = walk ? walked_only_level(r) : 0;
-        const bool walkedOnly = walkedLevel != 0;
-        const int stackScan = walkedOnly ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
-        const uint32_t ldsTrace = walkedOnly ? (uint32_t)(((size_t)stackScan*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes) : a.ldsBytes;
-        a.walkedOnly = walkedLevel;
-        if (r->walkList != nullptr)
-            gridPersist = std::max(1, std::min(gridPersist, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
-        if (cut_regions(r, a, slots, &gridPersist, (size_t)0))
-            return -1;
-        const size_t W = a.ss.numRegions;
-        {
-            ScopedTimer t(r, KN_GENERATE, st);
-            a.grid = gridPersist;
-            launch_path(r, PK_GENERATE, a, st);
-        }
-        const int K = r->neePerPath;
-        // (the step after the last bounce only resolves the last bounce's light samples: nothing to do without lights)
-        const int steps = fp.maxDepth + (K > 0 ? 1 : 0);
-        for (int bounce = 0; bounce < steps; ++bounce)
-        {
-            a.bounce = bounce;
-            a.order = nullptr;
-            if (walk)
-            {
-                a.grid = gridPersist;
-                const bool first = bounce == 0, last = bounce >= fp.maxDepth;
-                if (launch_walk(r, st, a, r->ss.segFront + (size_t)bounce*W, /*shadowRays*/ !first && K > 0, /*mixed*/ !first && !last && K > 0))
-                    return -1;
-            }
-            // k_step's region groups longest first (k_region_order) where paths are deep: by bounce 6 most regions are nearly empty and the few
-            // full ones should not start last -- transmission.tin (depth 16) k_step 13.45 -> 11.81 ms, 1329 -> 1396 Msamples/s; at depth 4 the sort's
-            // launch costs what it saves (the 524k-triangle config 2562 / 2555: profiles/r06_r_ab_step_order.md)
-            if (bounce > 0 && fp.maxDepth >= 6 && gridPersist > r->numCUs*2)
-            {
-                ScopedTimer t(r, KN_SEG, st);
-                hipLaunchKernelGGL(k_region_order, dim3(1), dim3(kOrderBlock), 0, st, (const uint32_t*)(r->ss.segFront + (size_t)bounce*W), (const uint32_t*)(r->ss.segBack + (size_t)bounce*W),
-                                   a.ss.numRegions, r->regionOrder);
-                a.order = r->regionOrder;
-            }
-            ScopedTimer t(r, KN_STEP, st);
-            a.grid = gridPersist;
-            a.ldsBytes = ldsTrace;
-            a.stackEntries = stackScan;
-            launch_path(r, PK_STEP, a, st);
-        }
     }
     else
     {
-        const bool walk = walk_records(r) != nullptr;
-        // every mesh primitive walked by k_walk: the scan kernels run their lean variants with the scene-level stack only
-        const int walkedLevel = walk ? walked_only_level(r) : 0;
-        const bool walkedOnly = walkedLevel != 0;
-        const int stackScan = walkedOnly ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
-        const uint32_t ldsTrace = walkedOnly ? (uint32_t)(((size_t)stackScan*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes) : a.ldsBytes;
-        // k_shade has no traversal stacks in LDS and reads a material per path: an arena too large to sit beside the stacks of the
-        // trace kernels (32 KB) is still staged by it up to 60 KB (many_spheres, 39 KB of primitive and material records: k_shade
-        // 7.8 -> 6.7 ms; staged in the trace kernels too it costs them their fourth wave per SIMD, 1380 -> 1280 Msamples/s, and
-        // k_lights reads too little of it to repay the copy, 2.7 -> 3.1 ms)
-        const uint32_t arenaLdsTrace = r->scene.arenaLdsBytes;
-        const uint32_t arenaLdsShade = (arenaLdsTrace == 0 && r->scene.arenaBytes <= 61440u && r->tune.lds_scene != 0) ? r->scene.arenaBytes : arenaLdsTrace;
-        const uint32_t ldsShade = r->scene.allInArena ? r->scene.arenaBytes : arenaLdsShade;
-        a.walkedOnly = walkedLevel;
-        const bool noSceneWalkEarly = r->tune.scene_walk == 0;
-        // the lean k_extend draws the light samples itself (tn_launch.h launches it when walkedOnly and not counting)
-        // ... and so does the variant for a staged arena with meshes in HBM (glass): without the SLP vectoriser it fits 128 VGPRs and
-        // saves k_lights' pass over the path state (k_extend 5.7 + k_lights 7.1 -> 11.2 ms per 32 passes, glass 1366 -> 1425 Msamples/s;
-        // round 2, 170 VGPRs: 29.1 apart, 31.5 together; profiles/r03_k_ab_lights_in_extend.txt)
-        const bool mixedArena = !r->scene.allInArena && r->scene.arenaLdsBytes != 0 && r->scene.arenaLdsBytes == r->scene.arenaBytes;
-        const bool lightsInMixed = !walkedOnly && !r->countDetail && mixedArena && !(!noSceneWalkEarly && !r->scene.flatScan);
-        a.lightsInExtend = lightsInMixed ? 1 : 0;
-        const bool lightsInExtend = (walkedOnly && !r->countDetail) || lightsInMixed;
-        // No short regions at the end here: the launches are many and short, k_walk cuts its
-        // own list into static ranges, and more regions cost k_seg_prefix / k_walk more than the other kernels' tails gain -- the 524k-triangle
-        // config 2319 -> 2254 Msamples/s, many_spheres 2108 -> 2082, glass +-0 (profiles/r03_z5_ab_tail_split.md).  (k_seg_prefix stages
-        // the regions' counts in LDS: (sharedMemLimit - 1024)/4 of them at most where a walk list is built.)
-        // (k_seg_prefix stages one count per region in LDS: where a walk list is built the grid is clamped to what fits)
-        if (r->walkList != nullptr)
-            gridPersist = std::max(1, std::min(gridPersist, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
-        if (cut_regions(r, a, slots, &gridPersist, (size_t)0))
+        a.ss = L.ss;
+        a.ss.radOut = rad;
+        const int rc = p.pipeline == TINSEL_PIPELINE_WAVEFRONT ? trace_fused(r, p, L, st, a, slots) :
+                       p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED ? trace_paired(r, p, L, st, a, slots) : trace_split(r, p, L, st, a, slots);
+        if (rc)
             return -1;
-        gridTrace = gridPersist;
-        const size_t W = a.ss.numRegions;
-        {
-            ScopedTimer t(r, KN_GENERATE, st);
-            a.grid = gridPersist;
-            launch_path(r, PK_GENERATE, a, st);
-        }
-        // (not where k_walk does the walking: what is left for the scan kernels is too short for the two extra launches per
-        // bounce to pay -- glass 1087 -> 1077, config 3 1891 -> 1881; many_spheres, scene BVH walked inline, 1168 -> 1290)
-        // scenes the flat scan cannot take (more than 64 primitives): the scene-level walk with ray replacement (k_swalk, tn_swalk.h)
-        // in the place of k_extend / k_shadow; the detail counters count the inline walks
-        const bool noSceneWalk = r->tune.scene_walk == 0;
-        const bool sceneWalk = !noSceneWalk && !r->scene.flatScan && !r->countDetail && r->walkList != nullptr && !walk;
-        const bool ordered = !walk && gridPersist > r->numCUs*2;
-        auto order_regions = [&](const uint32_t* front, const uint32_t* back, uint32_t* out) {
-            ScopedTimer t(r, KN_SEG, st);
-            hipLaunchKernelGGL(k_region_order, dim3(1), dim3(kOrderBlock), 0, st, front, back, a.ss.numRegions, out);
-        };
-        for (int bounce = 0; bounce < fp.maxDepth; ++bounce)
-        {
-            a.bounce = bounce;
-            // longest regions first (k_region_order, tn_kernels.h): the paths' order serves k_extend, k_lights and k_shade,
-            // the shadow-ray bundles' order k_shadow; bounce 0's regions are all full
-            a.order = nullptr;
-            if (ordered && bounce > 0)
-            {
-                order_regions(r->ss.segFront + (size_t)bounce*W, r->ss.segBack + (size_t)bounce*W, r->regionOrder);
-                a.order = r->regionOrder;
-            }
-            const uint32_t* const pathOrder = a.order;
-            if (walk)
-            {
-                a.grid = gridPersist;
-                if (launch_walk(r, st, a, r->ss.segFront + (size_t)bounce*W, false))
-                    return -1;
-            }
-            if (sceneWalk)
-            {
-                a.grid = gridPersist;
-                if (launch_swalk(r, st, a, r->ss.segFront + (size_t)bounce*W, r->ss.segBack + (size_t)bounce*W, false))
-                    return -1;
-            }
-            else
-            {
-                ScopedTimer t(r, KN_EXTEND, st);
-                a.grid = gridTrace;
-                a.ldsBytes = ldsTrace;
-                a.stackEntries = stackScan;
-                launch_path(r, PK_EXTEND, a, st);
-            }
-            if (r->neePerPath > 0)
-            {
-                if (!lightsInExtend)
-                {
-                    ScopedTimer t(r, KN_LIGHTS, st);
-                    a.grid = gridPersist;
-                    a.ldsBytes = r->scene.allInArena ? r->scene.arenaBytes : arenaLdsTrace;
-                    launch_path(r, PK_LIGHTS, a, st);
-                }
-                if (walk)
-                {
-                    a.grid = gridPersist;
-                    if (launch_walk(r, st, a, r->ss.neeFront + (size_t)bounce*W, true))
-                        return -1;
-                }
-                if (sceneWalk)
-                {
-                    a.grid = gridPersist;
-                    if (launch_swalk(r, st, a, r->ss.neeFront + (size_t)bounce*W, r->ss.neeBack + (size_t)bounce*W, true))
-                        return -1;
-                }
-                else
-                {
-                    if (ordered && bounce > 0)
-                    {
-                        order_regions(r->ss.neeFront + (size_t)bounce*W, r->ss.neeBack + (size_t)bounce*W, r->regionOrderNee);
-                        a.order = r->regionOrderNee;
-                    }
-                    ScopedTimer t(r, KN_SHADOW, st);
-                    a.grid = gridTrace;
-                    a.ldsBytes = ldsTrace;
-                    a.stackEntries = stackScan;
-                    launch_path(r, PK_SHADOW, a, st);
-                    a.order = pathOrder;
-                }
-            }
-            {
-                ScopedTimer t(r, KN_SHADE, st);
-                // k_shade_sorted takes a region's paths class by class (tn_kernels.h): chosen PER SCENE.  It pays where a good share of a
-                // bounce's paths are rays that LEFT the scene (a cheap class that otherwise idles through its wave-mates' shading) and the
-                // path state is not already ordered by k_walk's front / back split: many_spheres 2087 -> 2122 Msamples/s, and in the split
-                // pipeline veach 1902 -> 2003, features 1047 -> 1093; it loses in an enclosed scene (glass: no ray leaves, 17.5 -> 19.3 ms) and
-                // where k_walk runs (the 524k-triangle config 6.47 -> 6.86 ms) (profiles/r03_g_ab_shade_sorted.txt, r04_e_rates.md).
-                // tinsel_hip_tuning::shade_sorted = 0 / 1 forces either arm (A/B, tests).
-                const bool shadeSorted = (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !walk)) &&
-                                         (size_t)ldsShade + kShadeListWords*sizeof(uint32_t) <= (size_t)r->sharedMemLimit;
-                a.grid = gridPersist;
-                a.shadeSorted = shadeSorted ? 1 : 0;
-                a.ldsBytes = ldsShade + (shadeSorted ? (uint32_t)(kShadeListWords*sizeof(uint32_t)) : 0u);
-                a.stackEntries = stackScan;
-                a.scene.arenaLdsBytes = arenaLdsShade;
-                launch_path(r, PK_SHADE, a, st);
-                a.scene.arenaLdsBytes = arenaLdsTrace;
-            }
-        }
     }
 
     r->lastFp = fp;
     if (!accumulate)
         return 0;
-    return launch_accumulate(r, st, fp, r->accum);
+    return launch_accumulate(r, st, fp, rad, r->accum);
 }
 
 // traceOnly: the passes must fit ONE batch; their paths are traced (radiance left in ps.rad, r->lastFp set) but not
@@ -1247,40 +1327,13 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     if (perBatch > passes)
         perBatch = passes;
 
-    // Overlapped chunks.  A batch of several passes can be traced as TWO chunks of passes on two streams, each with its own dense state
-    // (ensure_batch's lanes), both writing their slots of the one radiance array; a chunk's accumulate kernel follows its own trace
-    // on its own stream and the previous chunk's accumulate by an event -- the framebuffer adds keep the reference's pass order, so no
-    // bit changes (tests/test_gpu_switches.py) -- and the two chunks' kernels fill each other's tails.  Measured built in
-    // (profiles/r04_k_ab_overlap.md, Msamples/s off -> on): it pays where a bounce is MANY SHORT launches that leave the chip half empty
-    // at their ends -- the scene-level walk of scenes beyond the flat scan (k_seg_* + k_swalk twice a bounce: many_spheres 2118 -> 2304)
-    // -- and nowhere else: the fused kernel is one launch that already ends in short regions (cornell 1024^2 x 20 passes 4173 -> 4145,
-    // x 256 4338 -> 4268, veach 4K 2838 -> 2846, gloss 10972 -> 10588, a 1 M-path batch 2748 -> 2406: two launches, two tails);
-    // k_walk's workgroups take a CU's whole LDS and gain nothing from a neighbour (the 524k-triangle config 2223 -> 2114, glass 1426 ->
-    // 1418).  (Two RENDERERS on two streams had looked like +4 % on cornell, profiles/r04_j_two_streams.txt: that was the host's
-    // share of a call overlapping, not the device's.)  Default: scenes whose scene level is walked by k_swalk, batches of 8 Mi paths
-    // or more.  tinsel_hip_tuning::overlap = 0 / 1: never / wherever a batch has two passes (A/B, tests).
-    int chunkPasses = perBatch;
-    int lanes = 1;
-    {
-        const size_t minPaths = (size_t)8u << 20;
-        const int pipeline = resolve_pipeline(r);
-        const bool can = !traceOnly && perBatch >= 2 && pipeline != TINSEL_PIPELINE_MEGAKERNEL;
-        const bool noSceneWalk = r->tune.scene_walk == 0;
-        const bool sceneWalked = pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT && !r->scene.flatScan && !noSceneWalk && !r->countDetail &&
-                                 !(r->walkPrims.count > 0 && r->walkEnabled);
-        const bool want = r->tune.overlap >= 0 ? r->tune.overlap != 0 : (sceneWalked && perPass*(size_t)perBatch >= minPaths);
-        if (can && want)
-        {
-            chunkPasses = (perBatch + 1)/2;
-            lanes = 2;
-        }
-    }
-    if (ensure_batch(r, perPass*(size_t)perBatch, fp.maxDepth, perPass*(size_t)chunkPasses, lanes))
+    const BatchPlan plan = plan_batch(r, perPass, perBatch, !traceOnly);
+    if (ensure_batch(r, plan, fp.maxDepth))
         return -1;
 
     if (traceOnly && perBatch < passes)
         return fail("render: look-ahead batch does not fit");
-    if (lanes == 2 && !r->laneStream)
+    if (plan.lanes == 2 && !r->laneStream)
     {
         HIP_TRY(hipStreamCreateWithFlags(&r->laneStream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&r->laneFork, hipEventDisableTiming));
@@ -1291,39 +1344,36 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     for (int done = 0; done < passes; done += perBatch)
     {
         const int n = std::min(perBatch, passes - done);
-        if (lanes == 1 || n < 2)
+        // (the test hooks: tinsel_hip_read_batch_radiance reads the whole batch, tinsel_hip_queue_counts the lane of the chunk traced last)
+        r->lastBatchSlots = perPass*(size_t)n;
+        if (plan.lanes == 1 || n < 2)
         {
             fp.passBase = done;
             fp.numPasses = n;
-            if (render_batch(r, st, cam, fp, !traceOnly))
+            r->lastLane = 0;
+            if (render_batch(r, plan, r->lane[0], st, cam, fp, r->ps.rad, !traceOnly))
                 return -1;
             continue;
         }
-        float4* const radBase = r->ps.rad;
-        const int first = std::min(chunkPasses, (n + 1)/2);
+        // the overlapped chunks (plan_batch): chunk c in lane c on its own stream, its radiance at its passes' slots
+        const int first = std::min(plan.chunkPasses, (n + 1)/2);
         HIP_TRY(hipEventRecord(r->laneFork, st));                       // whatever the caller's stream holds comes first
         HIP_TRY(hipStreamWaitEvent(r->laneStream, r->laneFork, 0));
         int rc = 0;
         for (int c = 0; c < 2 && !rc; ++c)
         {
             hipStream_t s = c ? r->laneStream : st;
-            if (c)
-                lane_swap(r);
+            float4* const rad = r->ps.rad + (size_t)(c ? first : 0)*perPass;
             fp.passBase = done + (c ? first : 0);
             fp.numPasses = c ? n - first : first;
-            r->ps.rad = radBase + (size_t)(c ? first : 0)*perPass;
-            r->ss.radOut = r->ps.rad;
-            rc = render_batch(r, s, cam, fp, false);
+            r->lastLane = c;
+            rc = render_batch(r, plan, r->lane[c], s, cam, fp, rad, false);
             if (!rc && c)
                 rc = hipStreamWaitEvent(s, r->accDone[0], 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
             if (!rc)
-                rc = launch_accumulate(r, s, r->lastFp, r->accum);
+                rc = launch_accumulate(r, s, r->lastFp, rad, r->accum);
             if (!rc)
                 rc = hipEventRecord(c ? r->laneJoin : r->accDone[0], s) == hipSuccess ? 0 : fail("render: hipEventRecord");
-            r->ps.rad = radBase;
-            r->ss.radOut = radBase;
-            if (c)
-                lane_swap(r);
         }
         if (!rc)
             rc = hipStreamWaitEvent(st, r->laneJoin, 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
@@ -1334,8 +1384,7 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
             (void)hipStreamSynchronize(r->laneStream);
             return -1;
         }
-        // the test hooks read a whole batch (tinsel_hip_read_batch_radiance; queue_counts reports the second chunk's regions)
-        r->lastBatchSlots = perPass*(size_t)n;
+        // (r->lastFp: the whole batch, its radiance at ps.rad)
         r->lastFp.passBase = done;
         r->lastFp.numPasses = n;
         r->lastFp.genCount = (uint32_t)(perPass*(size_t)n);

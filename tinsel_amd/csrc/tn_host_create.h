@@ -545,8 +545,8 @@ void tinsel_hip_destroy(tinsel_hip* r)
     if (r->workStream) (void)hipStreamDestroy(r->workStream);
     if (r->copyStream) (void)hipStreamDestroy(r->copyStream);
     if (r->probeAlias) (void)hipFree(r->probeAlias);
-    if (r->walkOverflow) (void)hipFree(r->walkOverflow);
-    if (r->laneB.walkOverflow) (void)hipFree(r->laneB.walkOverflow);
+    for (const tinsel_hip::DenseLane& lane : r->lane)
+        if (lane.walkOverflow) (void)hipFree(lane.walkOverflow);
     if (r->walkProf)
     {
         unsigned long long wp[16] = { 0 };

@@ -67,7 +67,7 @@ int lookahead_extend(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
         FrameParams fp = r->lastFp;
         fp.accBegin = j*passes;
         fp.accEnd = (j + 1)*passes;
-        if (launch_accumulate(r, r->workStream, fp, dst))
+        if (launch_accumulate(r, r->workStream, fp, r->ps.rad, dst))
             return -1;
         tinsel_hip::SpecShot shot = { dst, get_event(r) };
         HIP_TRY(hipEventRecord(shot.ready, r->workStream));

@@ -69,7 +69,6 @@ struct tinsel_hip
     std::vector<int32_t> planeTablePrims;       // the planes DevScene::planeEq holds (their PrimBox says 2: re-marked when the boxes are rewritten)
     int sceneStackNeed = 1;
     std::string prepRefused;            // non-empty: a kernel whose dynamic-LDS limit the runtime refused to raise (prepare_kernels_once)
-    int bounceWaves = kBounceWaves;     // k_bounce's waves per SIMD = the workgroups per CU its grids and region cuts are sized by
     bool sceneEnclosed = false;         // two planes face each other: (practically) no ray leaves the scene (k_bounce's shading pools stay off)
     int bvhMode = TINSEL_BVH_REFERENCE;
     int rrStart = 0;                    // > 0: Russian roulette from this bounce on (opt-in)
@@ -96,39 +95,34 @@ struct tinsel_hip
     std::vector<void*> batchAllocs;
     PathState ps;
     QueueCtl ctl;
-    // the wavefront pipelines' dense state (SplitState, tn_kernels.h); the split pipeline's hit / shadow-ray arrays only when
-    // that is the pipeline in force
-    SplitState ss;
     int batchPipeline = -1;             // the pipeline the current batch buffers were allocated for
-    size_t splitCap = 0;                // positions per SplitState array: the batch slots + one wave of padding per region
-    uint32_t splitMaxRegions = 0;
-    uint32_t* regionOrder = nullptr;    // region groups, longest first (k_region_order): by live paths, by shadow-ray bundles
-    uint32_t* regionOrderNee = nullptr;
-    uint32_t* walkList = nullptr;       // k_walk's work list (k_seg_expand) and the prefix of the regions' front counts behind it
-    uint32_t* segPrefix = nullptr;
     BinPrims binPrims = { 0, { 0, 0, 0, 0, 0, 0, 0 } };
     BinPrims walkPrims = { 0, { 0, 0, 0, 0, 0, 0, 0 } };   // the subset of binPrims whose closest hits k_walk computes (large trees)
     int walkPrimMesh[7] = { 0, 0, 0, 0, 0, 0, 0 };         // DevScene::meshes index of each walked primitive
-    float4* walkRec = nullptr;                          // k_walk's closest-hit records (tn_walk.h); batch-sized
-    // A SECOND set of the dense state (render_impl's overlapped chunks: two halves of a batch on two streams, each chunk's accumulate
-    // behind the other chunk's kernels).  The fields above are the set in use; lane_swap exchanges them with this one between ENQUEUES
-    // (a launch has copied its pointers by the time it returns).
+    // The wavefront pipelines' dense state (SplitState, tn_kernels.h), by lane: lane 1 only where render_impl traces a batch as two
+    // overlapped chunks on two streams (plan_batch), each chunk's accumulate behind the other chunk's kernels.  The split pipeline's
+    // hit / shadow-ray arrays only when that is the pipeline in force.
     struct DenseLane
     {
         SplitState ss;
-        size_t splitCap = 0;
+        size_t splitCap = 0;                // positions per SplitState array: the batch slots + one wave of padding per region
         uint32_t splitMaxRegions = 0;
-        uint32_t *regionOrder = nullptr, *regionOrderNee = nullptr, *walkList = nullptr, *segPrefix = nullptr;
-        float4* walkRec = nullptr;
-        uint32_t* walkOverflow = nullptr;       // (allocated by launch_walk on first use; freed with the renderer, not with the batch)
+        uint32_t* regionOrder = nullptr;    // region groups, longest first (k_region_order): by live paths, by shadow-ray bundles
+        uint32_t* regionOrderNee = nullptr;
+        uint32_t* walkList = nullptr;       // k_walk's / k_swalk's work list (k_seg_expand) and the prefix of the regions' front counts behind it
+        uint32_t* segPrefix = nullptr;
+        float4* walkRec = nullptr;          // k_walk's closest-hit records (tn_walk.h); batch-sized
+        // k_walk's stack entries beyond the LDS ones (tinsel_hip_tuning::walk_lds_stack): allocated by launch_walk on first use, freed with
+        // the renderer, not with the batch
+        uint32_t* walkOverflow = nullptr;
         size_t walkOverflowCap = 0;
-    } laneB;
-    int batchLanes = 1;                 // dense-state sets allocated (1 or 2)
-    size_t batchStateSlots = 0;         // path slots each set holds (batchSlots: what ps.rad holds)
+        uint32_t regions = 0, paths = 0;    // of the chunk last traced here: its regions and paths (tinsel_hip_queue_counts)
+    } lane[2];
+    int lastLane = 0;                   // the lane of the chunk traced last
+    int batchLanes = 1;                 // lanes allocated (1 or 2)
+    size_t batchStateSlots = 0;         // path slots each lane holds (batchSlots: what ps.rad holds)
     hipStream_t laneStream = nullptr;   // the second chunk's stream
     hipEvent_t laneFork = nullptr, laneJoin = nullptr, accDone[2] = { nullptr, nullptr };
-    uint32_t* walkOverflow = nullptr;                   // k_walk's stack entries beyond the LDS ones (tinsel_hip_tuning::walk_lds_stack)
-    size_t walkOverflowCap = 0;
     bool walkEnabled = true;                            // tinsel_hip_tuning::walk == 0: walk meshes inline in k_extend / k_shadow (A/B)
     unsigned long long* walkProf = nullptr;             // developer-only (-DTN_WALK_PROF builds): section counters of k_walk
     uint2* probeAlias = nullptr;                        // alias table of the probe (tinsel_hip_set_probe_sampling), built on first use
@@ -141,9 +135,8 @@ struct tinsel_hip
     hipStream_t passSeedsStream = nullptr;
     unsigned long long* statsDev = nullptr;
 
-    size_t lastBatchSlots = 0;
+    size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)
-    uint32_t lastRegions = 0;
     size_t maxBatchSlots = 8u << 20;
     bool batchSlotsExplicit = false;     // set by tinsel_hip_tuning::batch_paths / tinsel_hip_set_batch_paths
     int pipeline = TINSEL_PIPELINE_AUTO;
