@@ -1,4 +1,4 @@
-// tn_host_api.h -- C-ABI: init / render / present / refit / rebuild / settings / statistics / test hooks / scene packs
+// tn_host_api.h -- C-ABI: init / render / present / settings / statistics / test hooks / scene packs
 // (part of the library's one host translation unit: included by tinsel_hip.hip, in this order, never on its own)
 #pragma once
 
@@ -182,442 +182,6 @@ int tinsel_image_quantize_rgb8(const float* rgba, int width, int height, unsigne
             rgb[i*3 + c] = (unsigned char)(int)cl;
         }
     }
-    return 0;
-}
-
-int tinsel_hip_set_mesh_bvh(tinsel_hip* r, int mode, double* build_ms)
-{
-    lookahead_cancel(r);
-    if (!r || (mode != TINSEL_BVH_REFERENCE && mode != TINSEL_BVH_LBVH && mode != TINSEL_BVH_PLOC))
-        return fail("set_mesh_bvh: bad arguments");
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (build_ms)
-        *build_ms = 0.0;
-
-    std::vector<DevMesh> next = r->meshesRef;
-    const size_t prevAllocs = r->lbvhAllocs.size();
-    if (mode != TINSEL_BVH_REFERENCE)
-    {
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        (void)hipEventRecord(e0, nullptr);
-        int rc = 0;
-        for (size_t m = 0; m < next.size() && !rc; ++m)
-            if (!next[m].inArena && next[m].numTris >= 2)       // LDS-resident meshes keep their (tiny) reference trees
-                rc = build_device_bvh(r, r->meshesRef[m], next[m], mode);
-        (void)hipEventRecord(e1, nullptr);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc)
-            return -1;
-        if (build_ms)
-            *build_ms = ms;
-    }
-
-    int maxMeshNeed = 0;
-    for (const DevMesh& dm : next)
-        if (dm.stackNeed > maxMeshNeed)
-            maxMeshNeed = dm.stackNeed;
-    const int stack = pick_stack(r->sceneStackNeed + maxMeshNeed);
-    const size_t ldsNeed = stack < 0 ? 0 : ((size_t)stack*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes;
-    if (stack < 0 || ldsNeed > (size_t)r->sharedMemLimit)
-    {
-        // keep what was there: drop the trees just built
-        for (size_t k = prevAllocs; k < r->lbvhAllocs.size(); ++k)
-            (void)hipFree(r->lbvhAllocs[k]);
-        r->lbvhAllocs.resize(prevAllocs);
-        return fail("set_mesh_bvh: tree too deep for the LDS traversal stack (previous trees kept)");
-    }
-    if (!next.empty())
-        HIP_TRY(hipMemcpy((void*)r->scene.meshes, next.data(), sizeof(DevMesh)*next.size(), hipMemcpyHostToDevice));
-    r->meshesNow = next;
-    r->stackNeed = stack;
-    r->bvhMode = mode;
-    // the previous generation of device-built trees is unreachable now (a per-frame rebuild must not grow)
-    for (size_t k = 0; k < prevAllocs; ++k)
-        (void)hipFree(r->lbvhAllocs[k]);
-    r->lbvhAllocs.erase(r->lbvhAllocs.begin(), r->lbvhAllocs.begin() + (long)prevAllocs);
-    return 0;
-}
-
-// Refit of a deforming mesh: new vertex positions (and optionally normals), same topology, same tree shape.
-int tinsel_hip_refit_mesh(tinsel_hip* r, int primitive, const float* positions_xyz, int num_vertices, const float* normals_xyz)
-{
-    lookahead_cancel(r);
-    if (!r || !positions_xyz || primitive < 0 || primitive >= r->scene.numPrims || r->primMesh[(size_t)primitive] < 0)
-        return fail("refit_mesh: bad arguments (a mesh primitive and its new positions)");
-    const int mi = r->primMesh[(size_t)primitive];
-    DevMesh& dm = r->meshesNow[(size_t)mi];
-    // (a mesh of the LDS-staged arena is refitted in the arena's copy in HBM, which every launch stages from)
-    if (num_vertices != r->meshNumVertices[(size_t)mi])
-        return fail("refit_mesh: the topology must not change (vertex count differs)");
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipDeviceSynchronize());
-
-    const int numTris = dm.numTris;
-    const int numNodes = numTris - 1;           // one triangle per leaf: internal nodes
-    float* posDev = nullptr;
-    float* own = nullptr;
-    int* gen = nullptr;
-    int rc = 0;
-    do {
-        if (hipMalloc((void**)&posDev, sizeof(float)*3*(size_t)num_vertices) != hipSuccess ||
-            hipMemcpy(posDev, positions_xyz, sizeof(float)*3*(size_t)num_vertices, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("refit_mesh: upload failed"); break; }
-        hipLaunchKernelGGL(k_refit_tris, dim3((unsigned)((numTris + 255)/256)), dim3(256), 0, nullptr, const_cast<Tri48*>(dm.tris), numTris, posDev);
-        if (normals_xyz && hipMemcpy(const_cast<float*>(dm.normals), normals_xyz, sizeof(float)*3*(size_t)num_vertices, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("refit_mesh: normals upload failed"); break; }
-        if (numNodes > 0)
-        {
-            if (hipMalloc((void**)&own, sizeof(float)*6*(size_t)numNodes) != hipSuccess || hipMalloc((void**)&gen, sizeof(int)*(size_t)numNodes) != hipSuccess)
-            { rc = fail("refit_mesh: device allocation failed"); break; }
-            // the tree in use and, when a device-built one is, the reference's too (switching back must not find stale boxes)
-            const DevMesh* trees[2] = { &dm, r->meshesRef[(size_t)mi].nodes != dm.nodes ? &r->meshesRef[(size_t)mi] : nullptr };
-            for (const DevMesh* tree : trees)
-            {
-                if (!tree || rc)
-                    continue;
-                if (hipMemset(gen, 0, sizeof(int)*(size_t)numNodes) != hipSuccess) { rc = fail("refit_mesh: memset failed"); break; }
-                // the root of a converted tree is node 0 (reference trees: convert_bvh; device-built ones: the Karras root)
-                int rootGen = 0;
-                for (int pass = 1; pass <= 4096 && !rootGen; )
-                {
-                    for (int k = 0; k < 16; ++k, ++pass)
-                        hipLaunchKernelGGL(k_refit_pass, dim3((unsigned)((numNodes + 255)/256)), dim3(256), 0, nullptr, const_cast<Node64*>(tree->nodes), numNodes, dm.tris, own, gen, pass);
-                    if (hipMemcpy(&rootGen, gen + (tree->root & ~kLeafBit), sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-                        break;
-                }
-                if (!rootGen)
-                    rc = fail("refit_mesh: the refit did not reach the root");
-            }
-            if (rc)
-                break;
-        }
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { rc = fail("refit_mesh: kernels failed"); break; }
-    } while (false);
-    if (posDev) (void)hipFree(posDev);
-    if (own) (void)hipFree(own);
-    if (gen) (void)hipFree(gen);
-    if (rc)
-        return rc;
-
-    // Mesh::RebuildCDF (mesh.cpp:340-368) in the reference's own serial fp32 order, then PrimitiveArea of every instance
-    const std::vector<int32_t>& idx = r->meshIndices[(size_t)mi];
-    std::vector<float> cdf((size_t)numTris);
-    float totalArea = 0.0f;
-    for (int t = 0; t < numTris; ++t)
-    {
-        const float* a = positions_xyz + (size_t)idx[(size_t)t*3 + 0]*3;
-        const float* b = positions_xyz + (size_t)idx[(size_t)t*3 + 1]*3;
-        const float* c = positions_xyz + (size_t)idx[(size_t)t*3 + 2]*3;
-        const V3 ab(b[0] - a[0], b[1] - a[1], b[2] - a[2]), ac(c[0] - a[0], c[1] - a[1], c[2] - a[2]);
-        const float area = 0.5f*length(cross(ab, ac));
-        totalArea += area;
-        cdf[(size_t)t] = totalArea;
-    }
-    for (int t = 0; t < numTris; ++t)
-        cdf[(size_t)t] /= totalArea;
-    HIP_TRY(hipMemcpy(const_cast<float*>(dm.cdf), cdf.data(), sizeof(float)*(size_t)numTris, hipMemcpyHostToDevice));
-    for (int p = 0; p < r->scene.numPrims; ++p)
-        if (r->primMesh[(size_t)p] == mi)
-        {
-            const float area = totalArea*r->primEndScale[(size_t)p];          // intersection.h:843-847
-            const float rcpArea = 1.0f/area;
-            HIP_TRY(hipMemcpy((void*)&r->scene.mats[p].area, &area, sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy((void*)&r->scene.mats[p].rcpArea, &rcpArea, sizeof(float), hipMemcpyHostToDevice));
-        }
-
-    // The scene level follows: Scene::Build (scene.cpp:4-16) gives the scene BVH builder PrimitiveBounds(p) (intersection.h:906-939)
-    // = the mesh root's box under the start and end transforms.  The tree keeps its shape here too: the leaf box of every
-    // instance is recomputed with the reference's expressions and its ancestors become the union of their children (what the
-    // builder stores for that shape: min and max do not round).  Without this a deformation that leaves the old box is
-    // clipped: the flat scan, the queue sort and k_walk's `enters` test all start from the leaf box.
-    V3 lo(kFltMax, kFltMax, kFltMax), hi(-kFltMax, -kFltMax, -kFltMax);     // the root's box: the union of the triangles' (Bounds::AddPoint)
-    for (size_t k = 0; k < (size_t)numTris*3; ++k)
-    {
-        const float* v = positions_xyz + (size_t)idx[k]*3;
-        lo = V3(minT(lo.x, v[0]), minT(lo.y, v[1]), minT(lo.z, v[2]));
-        hi = V3(maxT(hi.x, v[0]), maxT(hi.y, v[1]), maxT(hi.z, v[2]));
-    }
-    r->meshRootLo[(size_t)mi] = lo;
-    r->meshRootHi[(size_t)mi] = hi;
-    r->meshArea[(size_t)mi] = totalArea;
-    std::vector<tinsel_bvh_node>& sb = r->sceneBvhHost;
-    std::vector<int> leafOf((size_t)r->scene.numPrims, -1);
-    for (size_t k = 0; k < sb.size(); ++k)
-        if (ref_is_leaf(sb[k]) && sb[k].left_index < (uint32_t)r->scene.numPrims)
-            leafOf[sb[k].left_index] = (int)k;
-    std::vector<PrimBox> newBoxes;
-    std::vector<int> newBoxPrim;
-    for (int p = 0; p < r->scene.numPrims; ++p)
-    {
-        if (r->primMesh[(size_t)p] != mi || leafOf[(size_t)p] < 0)
-            continue;
-        V3 sl, su, el, eu;
-        transform_bounds(r->primStart[(size_t)p], lo, hi, sl, su);
-        transform_bounds(r->primEnd[(size_t)p], lo, hi, el, eu);
-        tinsel_bvh_node& leaf = sb[(size_t)leafOf[(size_t)p]];
-        leaf.lower.x = minT(sl.x, el.x); leaf.lower.y = minT(sl.y, el.y); leaf.lower.z = minT(sl.z, el.z);      // Union, maths.h:1023-1026
-        leaf.upper.x = maxT(su.x, eu.x); leaf.upper.y = maxT(su.y, eu.y); leaf.upper.z = maxT(su.z, eu.z);
-        newBoxes.push_back(make_prim_box(leaf));
-        newBoxPrim.push_back(p);
-    }
-    {
-        // ancestors: post-order over the reference's tree (validated acyclic by convert_bvh at create)
-        std::vector<uint32_t> order, stack(1, 0u);
-        while (!stack.empty())
-        {
-            const uint32_t k = stack.back();
-            stack.pop_back();
-            order.push_back(k);
-            if (!ref_is_leaf(sb[k]))
-            {
-                stack.push_back(sb[k].left_index);
-                stack.push_back(ref_right(sb[k]));
-            }
-        }
-        for (size_t q = order.size(); q-- > 0; )
-        {
-            tinsel_bvh_node& n = sb[order[q]];
-            if (ref_is_leaf(n))
-                continue;
-            const tinsel_bvh_node& a = sb[n.left_index];
-            const tinsel_bvh_node& b = sb[ref_right(n)];
-            n.lower.x = minT(a.lower.x, b.lower.x); n.lower.y = minT(a.lower.y, b.lower.y); n.lower.z = minT(a.lower.z, b.lower.z);
-            n.upper.x = maxT(a.upper.x, b.upper.x); n.upper.y = maxT(a.upper.y, b.upper.y); n.upper.z = maxT(a.upper.z, b.upper.z);
-        }
-    }
-    ConvertedBvh sceneBvh;
-    if (!convert_bvh(sb.data(), (int)sb.size(), r->scene.numPrims, 0, sceneBvh))
-        return fail("refit_mesh: the scene BVH could not be refitted");
-    unsigned char* arenaDev = const_cast<unsigned char*>(r->scene.arena);
-    if (!sceneBvh.nodes.empty())
-        HIP_TRY(hipMemcpy(arenaDev + r->arenaOffNodes, sceneBvh.nodes.data(), sizeof(Node64)*sceneBvh.nodes.size(), hipMemcpyHostToDevice));
-    for (size_t k = 0; k < newBoxes.size(); ++k)
-        HIP_TRY(hipMemcpy(arenaDev + r->arenaOffBoxes + sizeof(PrimBox)*(size_t)newBoxPrim[k], &newBoxes[k], sizeof(PrimBox), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// A primitive moves (the reference mutates Scene::primitives[i].startTransform / endTransform and re-runs Scene::Build).
-int tinsel_hip_set_primitive_transform(tinsel_hip* r, int index, const tinsel_transform* start, const tinsel_transform* end)
-{
-    lookahead_cancel(r);
-    if (!r || !start || !end || index < 0 || index >= r->scene.numPrims)
-        return fail("set_primitive_transform: bad arguments");
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const Xform xs = to_xform(*start), xe = to_xform(*end);
-    const bool isStatic = memcmp(start, end, sizeof(tinsel_transform)) == 0;
-    r->primStart[(size_t)index] = xs;
-    r->primEnd[(size_t)index] = xe;
-    r->primEndScale[(size_t)index] = xe.s;
-    Prim64& o = r->primsHost[(size_t)index];
-    set_prim_pose(o, xs, xe, isStatic);
-    set_prim_derived(o);
-    const Moving64 mv = make_moving(xs, xe);
-    unsigned char* arenaDev = const_cast<unsigned char*>(r->scene.arena);
-    HIP_TRY(hipMemcpy(arenaDev + r->arenaOffPrims + sizeof(Prim64)*(size_t)index, &o, sizeof(Prim64), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(arenaDev + r->arenaOffMoving + sizeof(Moving64)*(size_t)index, &mv, sizeof(Moving64), hipMemcpyHostToDevice));
-    if (o.type == kPrimMesh)
-    {
-        // PrimitiveArea of a mesh: area*endTransform.s (intersection.h:843-847)
-        const float area = r->meshArea[(size_t)r->primMesh[(size_t)index]]*xe.s;
-        const float rcpArea = 1.0f/area;
-        HIP_TRY(hipMemcpy(arenaDev + r->arenaOffMats + sizeof(Mat128)*(size_t)index + offsetof(Mat128, area), &area, sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(arenaDev + r->arenaOffMats + sizeof(Mat128)*(size_t)index + offsetof(Mat128, rcpArea), &rcpArea, sizeof(float), hipMemcpyHostToDevice));
-    }
-    r->sceneDirty = true;
-    return 0;
-}
-
-namespace {
-
-// PrimitiveBounds (intersection.h:906-939) of primitive i as it is now: the local box (sphere: +-radius; plane: +-1e8; mesh: its root's)
-// under the start and the end transform, TransformBounds (maths.h:1004-1021), united
-void primitive_bounds(const tinsel_hip* r, int i, V3& lower, V3& upper)
-{
-    const Prim64& p = r->primsHost[(size_t)i];
-    V3 lo, hi;
-    if (p.type == kPrimSphere)      { lo = V3(-p.g0); hi = V3(p.g0); }
-    else if (p.type == kPrimPlane)  { lo = V3(-1.e+8f); hi = V3(1.e+8f); }
-    else                            { lo = r->meshRootLo[(size_t)r->primMesh[(size_t)i]]; hi = r->meshRootHi[(size_t)r->primMesh[(size_t)i]]; }
-    V3 sl, su, el, eu;
-    transform_bounds(r->primStart[(size_t)i], lo, hi, sl, su);
-    transform_bounds(r->primEnd[(size_t)i], lo, hi, el, eu);
-    lower = V3(minT(sl.x, el.x), minT(sl.y, el.y), minT(sl.z, el.z));      // Union, maths.h:1023-1026
-    upper = V3(maxT(su.x, eu.x), maxT(su.y, eu.y), maxT(su.z, eu.z));
-}
-
-// a Node64 tree (as the device builders emit it) back into the reference's node array: what tinsel_hip_refit_mesh walks to refit
-// the scene level, and what a later TINSEL_SCENE_BVH_NODES caller would hand in
-void node64_to_reference(const std::vector<Node64>& nodes, uint32_t ref, float lminx, float lminy, float lminz, float lmaxx, float lmaxy, float lmaxz,
-                         std::vector<tinsel_bvh_node>& out, uint32_t at)
-{
-    tinsel_bvh_node& me = out[at];
-    me.lower.x = lminx; me.lower.y = lminy; me.lower.z = lminz;
-    me.upper.x = lmaxx; me.upper.y = lmaxy; me.upper.z = lmaxz;
-    if (ref & kLeafBit)
-    {
-        me.left_index = ref & ~kLeafBit;
-        me.right_index_leaf = 0x80000000u;
-        return;
-    }
-    const Node64 n = nodes[ref];
-    const uint32_t l = (uint32_t)out.size();
-    out.push_back(tinsel_bvh_node());
-    out.push_back(tinsel_bvh_node());
-    out[at].left_index = l;
-    out[at].right_index_leaf = l + 1u;
-    node64_to_reference(nodes, n.left, n.lminx, n.lminy, n.lminz, n.lmaxx, n.lmaxy, n.lmaxz, out, l);
-    node64_to_reference(nodes, n.right, n.rminx, n.rminy, n.rminz, n.rmaxx, n.rmaxy, n.rmaxz, out, l + 1u);
-}
-
-} // namespace
-
-int tinsel_hip_rebuild_scene(tinsel_hip* r, int mode, const tinsel_bvh_node* nodes, int num_nodes, double* build_ms)
-{
-    lookahead_cancel(r);
-    if (!r || (mode != TINSEL_SCENE_BVH_NODES && mode != TINSEL_SCENE_BVH_DEVICE) || (mode == TINSEL_SCENE_BVH_NODES && (!nodes || num_nodes <= 0)))
-        return fail("rebuild_scene: bad arguments");
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (build_ms)
-        *build_ms = 0.0;
-    const int P = r->scene.numPrims;
-
-    std::vector<tinsel_bvh_node> ref;       // the new tree in the reference's format
-    if (mode == TINSEL_SCENE_BVH_NODES)
-        ref.assign(nodes, nodes + num_nodes);
-    else
-    {
-        // leaf boxes: PrimitiveBounds of every primitive as it is now
-        std::vector<V3> lo((size_t)P), hi((size_t)P);
-        for (int i = 0; i < P; ++i)
-            primitive_bounds(r, i, lo[(size_t)i], hi[(size_t)i]);
-        if (P == 1)
-        {
-            ref.resize(1);
-            ref[0].lower.x = lo[0].x; ref[0].lower.y = lo[0].y; ref[0].lower.z = lo[0].z;
-            ref[0].upper.x = hi[0].x; ref[0].upper.y = hi[0].y; ref[0].upper.z = hi[0].z;
-            ref[0].left_index = 0;
-            ref[0].right_index_leaf = 0x80000000u;
-        }
-        else
-        {
-            // The mesh builders' kernels over the primitives' boxes: a box travels as a degenerate triangle record (a = c = lower, b = upper),
-            // whose min / max IS the box; Morton order of the centroids, agglomerative clustering by surface area (tn_lbvh.h)
-            std::vector<Tri48> items((size_t)P);
-            for (int i = 0; i < P; ++i)
-            {
-                Tri48& T = items[(size_t)i];
-                T.ax = lo[(size_t)i].x; T.ay = lo[(size_t)i].y; T.az = lo[(size_t)i].z; T.i0 = i;
-                T.bx = hi[(size_t)i].x; T.by = hi[(size_t)i].y; T.bz = hi[(size_t)i].z; T.i1 = i;
-                T.cx = lo[(size_t)i].x; T.cy = lo[(size_t)i].y; T.cz = lo[(size_t)i].z; T.i2 = i;
-            }
-            Tri48* itemsDev = nullptr;
-            HIP_TRY(hipMalloc((void**)&itemsDev, sizeof(Tri48)*(size_t)P));
-            int rc = 0;
-            std::vector<Node64> built((size_t)P - 1);
-            DevMesh fake, out;
-            memset(&fake, 0, sizeof(fake));
-            fake.tris = itemsDev;
-            fake.numTris = P;
-            fake.inArena = 1;           // (no bottom-level records for this one)
-            const size_t allocsBefore = r->lbvhAllocs.size();
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (hipMemcpy(itemsDev, items.data(), sizeof(Tri48)*(size_t)P, hipMemcpyHostToDevice) != hipSuccess ||
-                hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-                rc = fail("rebuild_scene: upload failed");
-            if (!rc)
-            {
-                (void)hipEventRecord(e0, nullptr);
-                rc = build_device_bvh(r, fake, out, TINSEL_BVH_PLOC);
-                (void)hipEventRecord(e1, nullptr);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.0f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                if (build_ms)
-                    *build_ms = ms;
-            }
-            if (!rc && hipMemcpy(built.data(), out.nodes, sizeof(Node64)*((size_t)P - 1), hipMemcpyDeviceToHost) != hipSuccess)
-                rc = fail("rebuild_scene: read-back failed");
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            // the builder's own allocation for this tree: the arena takes a copy
-            for (size_t k = allocsBefore; k < r->lbvhAllocs.size(); ++k)
-                (void)hipFree(r->lbvhAllocs[k]);
-            r->lbvhAllocs.resize(allocsBefore);
-            (void)hipFree(itemsDev);
-            if (rc)
-                return rc;
-            // root box: the union of its children's
-            const Node64& rt = built[0];
-            ref.reserve((size_t)2*P - 1);
-            ref.push_back(tinsel_bvh_node());
-            node64_to_reference(built, 0u, minT(rt.lminx, rt.rminx), minT(rt.lminy, rt.rminy), minT(rt.lminz, rt.rminz),
-                                maxT(rt.lmaxx, rt.rmaxx), maxT(rt.lmaxy, rt.rmaxy), maxT(rt.lmaxz, rt.rmaxz), ref, 0u);
-        }
-    }
-
-    // from here on as at create: validate, convert, leaf boxes by primitive, stack depth
-    ConvertedBvh sceneBvh;
-    if (!convert_bvh(ref.data(), (int)ref.size(), P, 0, sceneBvh))
-        return fail("rebuild_scene: malformed scene BVH");
-    if ((int)sceneBvh.nodes.size() != (P > 1 ? P - 1 : 0))
-        return fail("rebuild_scene: the scene BVH must have one leaf per primitive");
-    std::vector<PrimBox> boxes((size_t)P);
-    std::vector<char> seen((size_t)P, 0);
-    for (const tinsel_bvh_node& nd : ref)
-        if (ref_is_leaf(nd) && nd.left_index < (uint32_t)P)
-        {
-            boxes[nd.left_index] = make_prim_box(nd);
-            seen[nd.left_index] = 1;
-        }
-    for (int k = 0; k < P; ++k)
-        if (!seen[(size_t)k])
-            return fail("rebuild_scene: a primitive has no leaf in the scene BVH");
-    int maxMeshNeed = 0;
-    for (const DevMesh& dm : r->meshesNow)
-        maxMeshNeed = std::max(maxMeshNeed, dm.stackNeed);
-    const int stack = pick_stack(sceneBvh.maxLeafDepth + 1 + maxMeshNeed);
-    if (stack < 0 || ((size_t)stack*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes > (size_t)r->sharedMemLimit)
-        return fail("rebuild_scene: tree too deep for the LDS traversal stack (previous tree kept)");
-
-    unsigned char* arenaDev = const_cast<unsigned char*>(r->scene.arena);
-    if (!sceneBvh.nodes.empty())
-        HIP_TRY(hipMemcpy(arenaDev + r->arenaOffNodes, sceneBvh.nodes.data(), sizeof(Node64)*sceneBvh.nodes.size(), hipMemcpyHostToDevice));
-    // The plane table (flat scan of the split pipeline's kernels: the always-hit planes' equations, tested ahead of the loop) follows the new
-    // boxes: a table plane whose leaf box is no longer "infinite" (the primitive was scaled below 0.1, or the caller's tree has a tighter
-    // leaf) is box-tested in the loop like everything else -- its table entry becomes d == 0, IntersectRayPlane's own "no hit" -- and one
-    // whose box is infinite again gets its equation back (the table used to be written at create only).
-    if (!r->planeTablePrims.empty() && r->scene.planeEq)
-    {
-        std::vector<float> eq(r->planeTablePrims.size()*4, 0.0f);
-        for (size_t t = 0; t < r->planeTablePrims.size(); ++t)
-        {
-            const int32_t k = r->planeTablePrims[t];
-            if (boxes[(size_t)k].alwaysHit)
-            {
-                boxes[(size_t)k].alwaysHit = 2u;
-                const Prim64& pp = r->primsHost[(size_t)k];
-                eq[t*4 + 0] = pp.g0; eq[t*4 + 1] = pp.g1; eq[t*4 + 2] = pp.g2; eq[t*4 + 3] = pp.g3;
-            }
-        }
-        HIP_TRY(hipMemcpy(const_cast<float4*>(r->scene.planeEq), eq.data(), eq.size()*sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(arenaDev + r->arenaOffBoxes, boxes.data(), sizeof(PrimBox)*(size_t)P, hipMemcpyHostToDevice));
-    r->scene.scanMask = 0;
-    for (int k = 0; k < P && k < 64; ++k)
-        if (boxes[(size_t)k].alwaysHit != 2u)
-            r->scene.scanMask |= 1ull << k;
-    r->scene.root = sceneBvh.root;
-    r->sceneStackNeed = sceneBvh.maxLeafDepth + 1;
-    r->stackNeed = stack;
-    r->sceneBvhHost = ref;
-    r->sceneDirty = false;
     return 0;
 }
 

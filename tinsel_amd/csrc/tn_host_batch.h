@@ -200,7 +200,9 @@ int pick_stack(int need)
     return -1;
 }
 
-size_t stack_bytes(const tinsel_hip* r) { return ((size_t)r->stackNeed*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes; }
+// LDS per workgroup of traversal stacks `stack` deep (+ the staged arena)
+size_t stack_bytes(const tinsel_hip* r, int stack) { return ((size_t)stack*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes; }
+size_t stack_bytes(const tinsel_hip* r) { return stack_bytes(r, r->stackNeed); }
 
 // The path kernels exist twice (tn_launch.h): this translation unit's, bit-identical to the CPU oracle, and
 // tinsel_fast.hip's, built under the tolerance contract.  tinsel_hip_set_arithmetic picks the arm.
@@ -524,7 +526,7 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
 
     p.walkedLevel = p.walk ? walked_only_level(r) : 0;
     p.stackScan = p.walkedLevel ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
-    p.ldsTrace = (uint32_t)(((size_t)p.stackScan*kBlock + kScanWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes);
+    p.ldsTrace = (uint32_t)stack_bytes(r, p.stackScan);
 
     p.workList = p.walkRecords || (split && !r->scene.flatScan);
     // (not where k_walk does the walking: what is left for the scan kernels is too short for the two extra launches per

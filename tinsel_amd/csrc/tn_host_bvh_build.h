@@ -155,4 +155,24 @@ int build_device_bvh(tinsel_hip* r, const DevMesh& dm, DevMesh& out, int mode)
     return rc;
 }
 
+// Refits mesh tree `tree` in place over its moved triangles `tris` (same topology, same shape): k_refit_pass bottom-up, the root's
+// generation read back every 16 passes.  `own` / `gen`: scratch of one box and one generation per internal node (numTris - 1: one
+// triangle per leaf).
+int refit_device_bvh(const DevMesh& tree, const Tri48* tris, float* own, int* gen)
+{
+    const int numNodes = tree.numTris - 1;
+    if (hipMemset(gen, 0, sizeof(int)*(size_t)numNodes) != hipSuccess)
+        return fail("refit_mesh: memset failed");
+    // the root of a converted tree is node 0 (reference trees: convert_bvh; device-built ones: the Karras root)
+    int rootGen = 0;
+    for (int pass = 1; pass <= 4096 && !rootGen; )
+    {
+        for (int k = 0; k < 16; ++k, ++pass)
+            hipLaunchKernelGGL(k_refit_pass, dim3((unsigned)((numNodes + 255)/256)), dim3(256), 0, nullptr, const_cast<Node64*>(tree.nodes), numNodes, tris, own, gen, pass);
+        if (hipMemcpy(&rootGen, gen + (tree.root & ~kLeafBit), sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            break;
+    }
+    return rootGen ? 0 : fail("refit_mesh: the refit did not reach the root");
+}
+
 } // namespace

@@ -247,8 +247,9 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
             r->primMesh[(size_t)i] = (int)prims[(size_t)i].mesh;
     }
 
-    ConvertedBvh sceneBvh;
-    if (ok && !convert_bvh(desc->bvh_nodes, desc->num_bvh_nodes, P, 0, sceneBvh))
+    // the scene level (tn_host_scene.h); the plane table is decided below
+    SceneLevel lvl;
+    if (ok && !build_scene_level(std::vector<tinsel_bvh_node>(desc->bvh_nodes, desc->bvh_nodes + desc->num_bvh_nodes), prims, {}, lvl))
     {
         fail("create: malformed scene BVH");
         ok = false;
@@ -256,7 +257,7 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
 
     if (ok)
     {
-        const int need = sceneBvh.maxLeafDepth + 1 + maxMeshNeed;
+        const int need = lvl.bvh.maxLeafDepth + 1 + maxMeshNeed;
         r->stackNeed = pick_stack(need);
         if (r->stackNeed < 0)
         {
@@ -267,21 +268,7 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
 
     if (ok)
     {
-        // leaf boxes of the scene BVH, by primitive index (flat scene-level scan)
-        std::vector<PrimBox> boxes((size_t)P);
-        std::vector<char> seen((size_t)P, 0);
-        for (int k = 0; k < desc->num_bvh_nodes; ++k)
-        {
-            const tinsel_bvh_node& nd = desc->bvh_nodes[k];
-            if (!ref_is_leaf(nd) || nd.left_index >= (uint32_t)P)
-                continue;
-            boxes[nd.left_index] = make_prim_box(nd);
-            seen[nd.left_index] = 1;
-        }
-        bool everyPrimHasALeaf = true;
-        for (int k = 0; k < P; ++k)
-            everyPrimHasALeaf = everyPrimHasALeaf && seen[(size_t)k];
-        const bool flatScan = everyPrimHasALeaf && P <= 64 && tune.flat_scan != 0;
+        const bool flatScan = lvl.everyPrimHasALeaf && P <= 64 && tune.flat_scan != 0;
 
         // primitives whose mesh lives in HBM (flat-scan scenes, the first 7): their leaf-box test sorts the ray queues
         // (k_generate, k_shade), and they are walked by k_walk ahead of the scan kernels (tn_walk.h).  That includes trees
@@ -323,7 +310,7 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
 #endif
 
         // one contiguous arena: scene BVH, Prim64, Mat128, moving poses, lights, mesh table (+ small meshes, added above)
-        const size_t offNodes = arena.add(sceneBvh.nodes.data(), sceneBvh.nodes.size());
+        const size_t offNodes = arena.add(lvl.bvh.nodes.data(), lvl.bvh.nodes.size());
         const size_t offPrims = arena.add(prims.data(), prims.size());
         const size_t offMats = arena.add(mats.data(), mats.size());
         const size_t offMoving = arena.add(moving.data(), moving.size());
@@ -338,33 +325,28 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
         // -5 %, round 4) and -- since k_bounce has the registers for it, round 5 -- fused scenes with at least one full block of four
         // (cornell 5283 -> 5450 Msamples/s, cfg1 +2.5 %); with fewer planes the table's remainder code only costs (gloss, env_loft -1 %:
         // profiles/r05_d_ab_plane_table_fused.md), so those keep the loop.
-        std::vector<float> planeEq;
-        std::vector<int32_t> planeIdx;
         int alwaysHitPlanes = 0;
         bool anyMeshInHbm = false;
         for (int k = 0; k < P; ++k)
         {
-            alwaysHitPlanes += (prims[(size_t)k].type == kPrimPlane && boxes[(size_t)k].alwaysHit) ? 1 : 0;
+            alwaysHitPlanes += (prims[(size_t)k].type == kPrimPlane && lvl.boxes[(size_t)k].alwaysHit) ? 1 : 0;
             anyMeshInHbm = anyMeshInHbm || (prims[(size_t)k].type == kPrimMesh && !meshes[prims[(size_t)k].mesh].inArena);
         }
         if (flatScan && (alwaysHitPlanes >= 4 || anyMeshInHbm))
         {
             for (int k = 0; k < P; ++k)
-                if (prims[(size_t)k].type == kPrimPlane && boxes[(size_t)k].alwaysHit)
-                {
-                    const Prim64& pp = prims[(size_t)k];
-                    planeEq.insert(planeEq.end(), { pp.g0, pp.g1, pp.g2, pp.g3 });
-                    planeIdx.push_back(k);
-                    boxes[(size_t)k].alwaysHit = 2u;
-                }
-            r->planeTablePrims = planeIdx;
-            while (planeIdx.size() % 4)
-            {
-                planeEq.insert(planeEq.end(), { 0.0f, 0.0f, 0.0f, 0.0f });      // d == 0: IntersectRayPlane's own "no hit"
-                planeIdx.push_back(0);
-            }
+                if (prims[(size_t)k].type == kPrimPlane && lvl.boxes[(size_t)k].alwaysHit)
+                    r->planeTablePrims.push_back(k);
+            mark_plane_table(lvl, prims, r->planeTablePrims);
         }
-        const size_t offBoxes = arena.add(boxes.data(), boxes.size());
+        std::vector<float> planeEq = lvl.planeEq;
+        std::vector<int32_t> planeIdx = r->planeTablePrims;
+        while (planeIdx.size() % 4)
+        {
+            planeEq.insert(planeEq.end(), { 0.0f, 0.0f, 0.0f, 0.0f });      // d == 0: IntersectRayPlane's own "no hit"
+            planeIdx.push_back(0);
+        }
+        const size_t offBoxes = arena.add(lvl.boxes.data(), lvl.boxes.size());
         const size_t offPlaneEq = arena.add(planeEq.data(), planeEq.size());
         const size_t offPlaneIdx = arena.add(planeIdx.data(), planeIdx.size());
         arena.bytes.resize((arena.bytes.size() + 127) & ~size_t(127), 0);
@@ -407,16 +389,11 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
             sc.lights = reinterpret_cast<const LightRec*>(arenaDev + offLights);
             sc.meshes = reinterpret_cast<const DevMesh*>(arenaDev + offMeshes);
             sc.numMeshes = (int)meshes.size();
-            r->sceneStackNeed = sceneBvh.maxLeafDepth + 1;
             sc.primBoxes = reinterpret_cast<const PrimBox*>(arenaDev + offBoxes);
             sc.planeEq = reinterpret_cast<const float4*>(arenaDev + offPlaneEq);
             sc.planeIdx = reinterpret_cast<const int32_t*>(arenaDev + offPlaneIdx);
             sc.numPlanes = (int32_t)r->planeTablePrims.size();
-            sc.scanMask = 0;
-            for (int k = 0; k < P && k < 64; ++k)
-                if (boxes[(size_t)k].alwaysHit != 2u)
-                    sc.scanMask |= 1ull << k;
-            r->sceneBvhHost.assign(desc->bvh_nodes, desc->bvh_nodes + desc->num_bvh_nodes);
+            adopt_scene_level(r, lvl);
             r->arenaOffNodes = offNodes;
             r->arenaOffBoxes = offBoxes;
             r->arenaOffPrims = offPrims;
@@ -441,7 +418,7 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
             {
                 int planes = 0;
                 for (int k = 0; k < P; ++k)
-                    planes += boxes[(size_t)k].alwaysHit ? 1 : 0;
+                    planes += lvl.boxes[(size_t)k].alwaysHit ? 1 : 0;
                 sc.sortQueues = (sc.flatScan && planes <= 2 && planes < P) ? 1 : 0;
             }
             // two infinite planes with opposite normals (a floor and a ceiling): every ray between them that is not parallel to
@@ -460,7 +437,6 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
                 all = all && dmesh.inArena;
             sc.allInArena = all ? 1 : 0;
         }
-        sc.root = sceneBvh.root;
         sc.numPrims = P;
         sc.numLights = (int)lights.size();
         sc.horizon[0] = desc->sky_horizon.x; sc.horizon[1] = desc->sky_horizon.y; sc.horizon[2] = desc->sky_horizon.z;
