@@ -406,6 +406,16 @@ int tinsel_hip_enable_kernel_timing(tinsel_hip* r, int enable);
 int tinsel_hip_stats_detail(tinsel_hip* r, unsigned long long* out8);
 int tinsel_hip_set_detail_counters(tinsel_hip* r, int enable);
 
+/* Per-pixel cost of path tracing passes [pass_begin, pass_begin + passes) as the reference algorithm counts it:
+ * out[(j*W + i)*4 + {0,1,2,3}] = {rays, internal BVH node visits, triangle tests, primitive tests}, summed over the
+ * passes (uint32, wraps). Pixels a shard does not own are 0. Leaves the accumulator, pass index, stats and tuning as they were.
+ * rays = closest-hit and shadow rays; the four are the quantities of tinsel_hip_stats_detail's [0], [2], [3], [4], counted
+ * on the scene BVH walk (never the flat scan), with the renderer's roulette, probe sampling and arithmetic.  Needs
+ * options->mode == TINSEL_MODE_PATHTRACE and the frame size of the last tinsel_hip_init; kernel "k_cost" in
+ * tinsel_hip_kernel_times. */
+int tinsel_hip_render_cost(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                           uint32_t pass_begin, int passes, uint32_t* out_host);
+
 /* Allocates the per-batch path buffers a later render of `passes` passes at `max_depth` will need, so that the first
  * such call does not pay for hipMalloc (tinsel_hip_render* allocate on demand otherwise). */
 int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth);

@@ -82,6 +82,13 @@ int tinsel_hip_render(tinsel_hip* r, const tinsel_camera* camera, const tinsel_o
     return 0;
 }
 
+int tinsel_hip_render_cost(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                           uint32_t* out_host)
+{
+    lookahead_cancel(r);
+    return render_cost_impl(r, camera, options, pass_begin, passes, out_host);
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -1163,15 +1163,15 @@ int trace_split(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     return 0;
 }
 
-// One batch -- or one overlapped chunk -- of passes fp.passBase .. + fp.numPasses, traced in lane L; the paths' radiance goes to rad[0, slots)
-int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams& cam, FrameParams fp, float4* rad,
-                 bool accumulate = true)
+// The slots of a batch of passes fp.passBase .. + fp.numPasses: fills fp's shard numbering, slot count and per-batch settings.
+// Returns the batch's slot count, 0 if it does not fit the 32-bit slot index.
+size_t batch_frame(const tinsel_hip* r, FrameParams& fp)
 {
     // path slots of this shard per pass and per batch (slot_pixel / slot_of, tn_kernels.h): rank-local numbering
     const size_t perPass = slots_per_pass(r, fp.width, fp.height, &fp.shardTilesX, &fp.shardOwnedTiles);
     const size_t slots = perPass*(size_t)fp.numPasses;
     if (slots >= (size_t)0xffffffffu)
-        return fail("render: batch too large");
+        return 0;
     fp.shardPerPass = (uint32_t)perPass;
     {
         auto magic = [](uint32_t d) { return 0xffffffffu/std::max(1u, d); };      // (tn_kernels.h div_magic)
@@ -1186,6 +1186,16 @@ int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
     fp.rrStart = r->rrStart;
     fp.repack = 0;
     fp.share = 0;
+    return slots;
+}
+
+// One batch -- or one overlapped chunk -- of passes fp.passBase .. + fp.numPasses, traced in lane L; the paths' radiance goes to rad[0, slots)
+int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams& cam, FrameParams fp, float4* rad,
+                 bool accumulate = true)
+{
+    const size_t slots = batch_frame(r, fp);
+    if (!slots)
+        return fail("render: batch too large");
     r->lastPipeline = p.pipeline;
 
     // what every launch of the batch shares
@@ -1225,31 +1235,20 @@ int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
     return launch_accumulate(r, st, fp, rad, r->accum);
 }
 
-// traceOnly: the passes must fit ONE batch; their paths are traced (radiance left in ps.rad, r->lastFp set) but not
-// accumulated -- the caller adds them pass range by pass range (launch_accumulate) into buffers of its choice (look-ahead).
-int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, int passes, hipStream_t st, bool traceOnly = false)
+// return finished timing events to the pool (a render call's kernel times cover that call alone)
+void release_spans(tinsel_hip* r)
 {
-    if (!r || !camera || !options)
-        return fail("render: null argument");
-    if (!r->accum || options->width != r->width || options->height != r->height)
-        return fail("render: options.width/height do not match the last tinsel_hip_init");
-    if (passes < 1)
-        return fail("render: passes must be >= 1");
-    if (r->sceneDirty)
-        return fail("render: a primitive was moved (tinsel_hip_set_primitive_transform): call tinsel_hip_rebuild_scene first");
-    HIP_TRY(hipSetDevice(r->device));
-
-    // return finished timing events to the pool
     for (TimedSpan& s : r->spans)
     {
         r->eventPool.push_back(s.start);
         r->eventPool.push_back(s.stop);
     }
     r->spans.clear();
+}
 
-    CameraParams cam;
-    make_camera(*camera, options->width, options->height, cam);
-
+// The frame of a render call: size, depth, shard, filter (the batch fields: batch_frame)
+FrameParams frame_params(const tinsel_hip* r, const tinsel_options* options)
+{
     FrameParams fp;
     fp.width = options->width;
     fp.height = options->height;
@@ -1266,6 +1265,28 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     fp.clampLen = options->clamp;
     fp.passBase = 0;
     fp.numPasses = 1;
+    return fp;
+}
+
+// traceOnly: the passes must fit ONE batch; their paths are traced (radiance left in ps.rad, r->lastFp set) but not
+// accumulated -- the caller adds them pass range by pass range (launch_accumulate) into buffers of its choice (look-ahead).
+int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, int passes, hipStream_t st, bool traceOnly = false)
+{
+    if (!r || !camera || !options)
+        return fail("render: null argument");
+    if (!r->accum || options->width != r->width || options->height != r->height)
+        return fail("render: options.width/height do not match the last tinsel_hip_init");
+    if (passes < 1)
+        return fail("render: passes must be >= 1");
+    if (r->sceneDirty)
+        return fail("render: a primitive was moved (tinsel_hip_set_primitive_transform): call tinsel_hip_rebuild_scene first");
+    HIP_TRY(hipSetDevice(r->device));
+
+    release_spans(r);
+
+    CameraParams cam;
+    make_camera(*camera, options->width, options->height, cam);
+    FrameParams fp = frame_params(r, options);
 
     const size_t npix = (size_t)fp.width*fp.height;
     const int gridPix = (int)((npix + kBlock - 1)/kBlock);
@@ -1394,6 +1415,102 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
         r->lastFp.accEnd = n;
     }
     r->passIndex += (uint32_t)passes;
+    return 0;
+}
+
+// tinsel_hip_render_cost: k_cost over the passes [passBegin, passBegin + passes), in batches under the megakernel's slot limit.  The seeds
+// are the call's own (pass_seed(passBegin + s), the renderer's table and generator are only read) and so is the map: four planes on the
+// device, interleaved per pixel on the host.  No path state, accumulator, pass index or statistics are touched.
+int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t passBegin, int passes, uint32_t* out)
+{
+    if (!r || !camera || !options || !out)
+        return fail("render_cost: null argument");
+    if (passes < 1)
+        return fail("render_cost: passes must be >= 1");
+    if (options->mode != TINSEL_MODE_PATHTRACE)
+        return fail("render_cost: options.mode must be TINSEL_MODE_PATHTRACE");
+    if (!r->accum || options->width != r->width || options->height != r->height)
+        return fail("render_cost: options.width/height do not match the last tinsel_hip_init");
+    if (r->sceneDirty)
+        return fail("render_cost: a primitive was moved (tinsel_hip_set_primitive_transform): call tinsel_hip_rebuild_scene first");
+    HIP_TRY(hipSetDevice(r->device));
+    release_spans(r);
+
+    const size_t npix = (size_t)r->width*r->height;
+    if (options->max_depth < 1)
+    {
+        memset(out, 0, sizeof(uint32_t)*4*npix);        // no bounce, no ray
+        return 0;
+    }
+
+    // Random(1) advanced passBegin times: from the renderer's generator where it has not gone past passBegin (a copy of it)
+    std::vector<uint32_t> seeds((size_t)passes);
+    {
+        Rng g = Rng::seeded(1u);
+        uint32_t at = 0;
+        if (r->seedRngIndex <= passBegin)
+        {
+            g = r->seedRng;
+            at = r->seedRngIndex;
+        }
+        for (; at < passBegin; ++at)
+            (void)g.rand();
+        for (uint32_t& v : seeds)
+            v = g.rand();
+    }
+
+    struct DeviceBuffers
+    {
+        uint32_t* seeds = nullptr;
+        uint32_t* cost = nullptr;
+        ~DeviceBuffers()
+        {
+            if (seeds) (void)hipFree(seeds);
+            if (cost) (void)hipFree(cost);
+        }
+    } dev;
+    HIP_TRY(hipMalloc((void**)&dev.seeds, sizeof(uint32_t)*seeds.size()));
+    HIP_TRY(hipMalloc((void**)&dev.cost, sizeof(uint32_t)*4*npix));
+    HIP_TRY(hipMemcpy(dev.seeds, seeds.data(), sizeof(uint32_t)*seeds.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dev.cost, 0, sizeof(uint32_t)*4*npix));
+
+    CameraParams cam;
+    make_camera(*camera, options->width, options->height, cam);
+    FrameParams fp = frame_params(r, options);
+
+    const size_t perPass = slots_per_pass(r, fp.width, fp.height);
+    const int perBatch = (int)std::min<size_t>((size_t)passes, std::max<size_t>(1, r->maxBatchSlots/perPass));
+    const hipStream_t st = nullptr;
+    for (int done = 0; done < passes; done += perBatch)
+    {
+        fp.passBase = done;
+        fp.numPasses = std::min(perBatch, passes - done);
+        const size_t slots = batch_frame(r, fp);
+        if (!slots)
+            return fail("render_cost: batch too large");
+
+        // k_mega's launch (render_batch) with counting on: the scene BVH walk, stacks r->stackNeed deep
+        LaunchArgs a;
+        memset(&a, 0, sizeof(a));
+        a.scene = r->scene;
+        a.cam = cam;
+        a.fp = fp;
+        a.passSeeds = dev.seeds;
+        a.stackEntries = r->stackNeed;
+        a.countDetail = 1;
+        a.ldsBytes = (uint32_t)stack_bytes(r);
+        a.cost = dev.cost;
+        a.grid = (int)((slots + kBlock - 1)/kBlock);
+        ScopedTimer t(r, KN_COST, st);
+        launch_path(r, PK_COST, a, st);
+        HIP_TRY(hipGetLastError());
+    }
+
+    std::vector<uint32_t> planes(4*npix);
+    HIP_TRY(hipMemcpy(planes.data(), dev.cost, sizeof(uint32_t)*planes.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < npix; ++k)
+        for (int c = 0; c < 4; ++c)
+            out[k*4 + c] = planes[(size_t)c*npix + k];
     return 0;
 }
 

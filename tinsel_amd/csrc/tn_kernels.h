@@ -9,7 +9,7 @@
 //   tn_walk.h         k_walk / k_walk_rays: the mesh walk of meshes in HBM with ray replacement
 //   tn_swalk.h        k_swalk: the scene-level walk with ray replacement (scenes beyond the flat scan)
 //   tn_accumulate.h   AddSample as an order-preserving gather: k_accumulate, k_accumulate_tiled, k_accumulate_piped
-//   here              k_mega (one lane per whole path: the A/B arm), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
+//   here              k_mega (one lane per whole path: the A/B arm), k_cost (its counters as a per-pixel map), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
 //
 // Every pipeline runs the same per-path arithmetic (tn_integrator.h, tn_bsdf.h, tn_isect.h) and leaves a finished path's radiance in
 // PathState::rad[slot]; all are asserted bitwise equal to each other and to the CPU reference (tests/test_gpu_parity.py).
@@ -27,6 +27,78 @@
 #include "tn_accumulate.h"
 
 namespace tn {
+
+// ---------------------------------------------------------------------------
+// TN_MEGA_PATH: one lane walks the whole ePathTrace path of pass s at pixel (i, j) (render.cpp:230-388) -- the body of k_mega and k_cost,
+// a block in the kernel's own scope (sc, st, cam, fp, passSeeds, s, i, j; counts samples, rays, shadowRays, ctr), then FINISH with the
+// path's radiance in p.rad.  A macro, not a function: spelled out in the kernel, k_mega compiles to the same code it always did.
+#define TN_MEGA_PATH(FINISH)                                                                                         \
+{                                                                                                                    \
+    Rng rng;                                                                                                         \
+    float rx, ry, time;                                                                                              \
+    V3 o, d;                                                                                                         \
+    camera_sample(cam, fp, i, j, passSeeds[fp.passBase + s], rng, rx, ry, time, o, d);                               \
+    samples = 1;                                                                                                     \
+                                                                                                                     \
+    PathRegs p;                                                                                                      \
+    path_begin(p, o, d, time, rng);                                                                                  \
+                                                                                                                     \
+    for (int bounce = 0; bounce < fp.maxDepth; ++bounce)                                                             \
+    {                                                                                                                \
+        float t;                                                                                                     \
+        V3 n;                                                                                                        \
+        const int prim = trace<SceneT<LDS>, LdsStack<kBlock>, COUNT>(sc, st, p.o, p.d, p.time, t, n, ctr);           \
+        rays++;                                                                                                      \
+                                                                                                                     \
+        if (prim < 0)                                                                                                \
+        {                                                                                                            \
+            on_miss(sc, p, bounce);                                                                                  \
+            break;                                                                                                   \
+        }                                                                                                            \
+                                                                                                                     \
+        const Mat mat = load_mat(sc.mats, prim);                                                                     \
+        HitCtx h;                                                                                                    \
+        on_hit_begin(p, mat, t, n, bounce, h, prim);                                                                 \
+                                                                                                                     \
+        /* SampleLights (render.cpp:103-227): draw, trace, and the BSDF terms for the samples that arrive */         \
+        {                                                                                                            \
+            const V3 thrAtNee = p.thr;                                                                               \
+            LightCursor lights;                                                                                      \
+            V3 sum = nee_sum(sc, [&](int k) -> V3 {                                                                  \
+                NeeGeo g;                                                                                            \
+                V3 skyColor;                                                                                         \
+                float skyPdf = 0.0f;                                                                                 \
+                int light = -1;                                                                                      \
+                if (sc.probe.valid && k == 0)                                                                        \
+                    nee_sample_probe(sc, h.p, h.n, p.rng, g, skyColor, skyPdf);                                      \
+                else                                                                                                 \
+                {                                                                                                    \
+                    light = lights.next(sc);                                                                         \
+                    nee_sample_light(sc, h.p, h.n, p.time, light, p.rng, g);                                         \
+                }                                                                                                    \
+                float ts;                                                                                            \
+                V3 nn;                                                                                               \
+                const int hp = trace<SceneT<LDS>, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, ctr);  \
+                rays++;                                                                                              \
+                shadowRays++;                                                                                        \
+                if (light < 0)                                                                                       \
+                    return (hp < 0) ? nee_contrib_probe(mat, h, g.wi, skyColor, skyPdf) : V3(0.0f);                  \
+                if (!nee_light_reached(g, hp, ts))                                                                   \
+                    return V3(0.0f);                                                                                 \
+                return nee_contrib_light(sc, mat, h, g.wi, g.nl, light, hp, ts);                                     \
+            });                                                                                                      \
+            p.rad = p.rad + thrAtNee*sum;                                                                            \
+        }                                                                                                            \
+                                                                                                                     \
+        if (bounce + 1 >= fp.maxDepth)                                                                               \
+            break;                                                                                                   \
+        if (bsdf_step(p, mat, h) != kContinue)                                                                       \
+            break;                                                                                                   \
+        if (fp.rrStart > 0 && bounce + 1 >= fp.rrStart && !roulette_survives(p))                                     \
+            break;                                                                                                   \
+    }                                                                                                                \
+    FINISH;                                                                                                          \
+}
 
 // ---------------------------------------------------------------------------
 // k_mega: the A/B arm -- one lane walks one whole path (render.cpp:230-388), same pieces.
@@ -49,73 +121,7 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_FUSED) void k_mega(DevScene scIn, 
 
     if (live)
     {
-        {
-            Rng rng;
-            float rx, ry, time;
-            V3 o, d;
-            camera_sample(cam, fp, i, j, passSeeds[fp.passBase + s], rng, rx, ry, time, o, d);
-            samples = 1;
-
-            PathRegs p;
-            path_begin(p, o, d, time, rng);
-
-            for (int bounce = 0; bounce < fp.maxDepth; ++bounce)
-            {
-                float t;
-                V3 n;
-                const int prim = trace<SceneT<LDS>, LdsStack<kBlock>, COUNT>(sc, st, p.o, p.d, p.time, t, n, ctr);
-                rays++;
-
-                if (prim < 0)
-                {
-                    on_miss(sc, p, bounce);
-                    break;
-                }
-
-                const Mat mat = load_mat(sc.mats, prim);
-                HitCtx h;
-                on_hit_begin(p, mat, t, n, bounce, h, prim);
-
-                // SampleLights (render.cpp:103-227): draw, trace, and the BSDF terms for the samples that arrive
-                {
-                    const V3 thrAtNee = p.thr;
-                    LightCursor lights;
-                    V3 sum = nee_sum(sc, [&](int k) -> V3 {
-                        NeeGeo g;
-                        V3 skyColor;
-                        float skyPdf = 0.0f;
-                        int light = -1;
-                        if (sc.probe.valid && k == 0)
-                            nee_sample_probe(sc, h.p, h.n, p.rng, g, skyColor, skyPdf);
-                        else
-                        {
-                            light = lights.next(sc);
-                            nee_sample_light(sc, h.p, h.n, p.time, light, p.rng, g);
-                        }
-                        float ts;
-                        V3 nn;
-                        const int hp = trace<SceneT<LDS>, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, ctr);
-                        rays++;
-                        shadowRays++;
-                        if (light < 0)
-                            return (hp < 0) ? nee_contrib_probe(mat, h, g.wi, skyColor, skyPdf) : V3(0.0f);
-                        if (!nee_light_reached(g, hp, ts))
-                            return V3(0.0f);
-                        return nee_contrib_light(sc, mat, h, g.wi, g.nl, light, hp, ts);
-                    });
-                    p.rad = p.rad + thrAtNee*sum;
-                }
-
-                if (bounce + 1 >= fp.maxDepth)
-                    break;
-                if (bsdf_step(p, mat, h) != kContinue)
-                    break;
-                if (fp.rrStart > 0 && bounce + 1 >= fp.rrStart && !roulette_survives(p))
-                    break;
-            }
-
-            ps.rad[slot] = make_float4(p.rad.x, p.rad.y, p.rad.z, 0.0f);
-        }
+        TN_MEGA_PATH(ps.rad[slot] = make_float4(p.rad.x, p.rad.y, p.rad.z, 0.0f))
     }
 
     wave_add_stat(q.stats, 0, rays);
@@ -128,6 +134,41 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_FUSED) void k_mega(DevScene scIn, 
         wave_add_stat(q.stats, 4, ctr.prims);
     }
 }
+
+// ---------------------------------------------------------------------------
+// k_cost: the traversal-cost map (tinsel_hip_render_cost) -- k_mega<true, LDS>'s path of every slot, its counters added to the
+// slot's pixel instead of the radiance: cost[c*npix + pixel] += {rays, internal node visits, triangle tests, primitive tests}[c].
+// Planes of the map, not a pixel's four words side by side: each of the four adds of a wave is one contiguous run (integer sums: any
+// order gives the same map).  Writes nothing else -- no radiance, no q.stats.
+
+template <bool LDS>
+__global__ __launch_bounds__(kBlock, TN_WAVES_FUSED) void k_cost(DevScene scIn, CameraParams cam, FrameParams fp, const uint32_t* __restrict__ passSeeds,
+                                                 int stackEntries, uint32_t* __restrict__ cost)
+{
+    extern __shared__ uint32_t s_stack[];      // [stackEntries][kBlock], sized at launch
+    LdsStack<kBlock> st = { s_stack + threadIdx.x };
+    SceneT<LDS> sc;
+    stage_scene_lds(sc, scIn, s_stack + stackEntries*kBlock + kScanWords);
+
+    const uint32_t idx = blockIdx.x*kBlock + threadIdx.x;
+    int s = 0, i = 0, j = 0;
+    if (!(idx < fp.genCount && slot_pixel(fp, idx, s, i, j)))
+        return;
+    uint32_t rays = 0, shadowRays = 0, samples = 0;
+    TraceCounters ctr = { 0, 0, 0 };
+    constexpr bool COUNT = true;
+    TN_MEGA_PATH((void)0)
+    (void)samples;          // (the map counts no samples: every live lane is one)
+    (void)shadowRays;       // (nor shadow rays apart: they are among `rays`)
+
+    const size_t npix = (size_t)fp.width*fp.height, pix = (size_t)j*fp.width + i;
+    atomicAdd(cost + pix, rays);
+    atomicAdd(cost + npix + pix, ctr.internal);
+    atomicAdd(cost + 2*npix + pix, ctr.tris);
+    atomicAdd(cost + 3*npix + pix, ctr.prims);
+}
+
+#undef TN_MEGA_PATH
 
 // ---------------------------------------------------------------------------
 // k_pass_seeds: passSeed[s] = the (first + s + 1)-th output of Random(1).Rand() (render.cu:1050-1052, 1099), continued on

@@ -17,7 +17,7 @@ namespace tn {
 
 enum PathKernel : int
 {
-    PK_GENERATE = 0, PK_EXTEND, PK_SHADE, PK_SHADOW, PK_BOUNCE, PK_MEGA, PK_WALK, PK_LIGHTS, PK_SWALK_EXTEND, PK_SWALK_SHADOW, PK_STEP,
+    PK_GENERATE = 0, PK_EXTEND, PK_SHADE, PK_SHADOW, PK_BOUNCE, PK_MEGA, PK_WALK, PK_LIGHTS, PK_SWALK_EXTEND, PK_SWALK_SHADOW, PK_STEP, PK_COST,
 };
 
 struct LaunchArgs
@@ -47,6 +47,7 @@ struct LaunchArgs
     int countDetail;                // detail counters on: the COUNT kernel variants
     int grid;
     uint32_t ldsBytes;              // dynamic LDS of the launch
+    uint32_t* cost;                 // PK_COST: the cost map's four planes (k_cost)
 };
 
 inline void launch_path_kernel(int which, const LaunchArgs& a, hipStream_t st)
@@ -93,6 +94,12 @@ inline void launch_path_kernel(int which, const LaunchArgs& a, hipStream_t st)
         break;
     case PK_MEGA:
         TN_LAUNCH2(k_mega, grid, block, a.ldsBytes, st, a.scene, a.ps, a.ctl, a.cam, a.fp, a.passSeeds, a.stackEntries);
+        break;
+    case PK_COST:
+        if (lds)
+            hipLaunchKernelGGL((k_cost<true>), grid, block, a.ldsBytes, st, a.scene, a.cam, a.fp, a.passSeeds, a.stackEntries, a.cost);
+        else
+            hipLaunchKernelGGL((k_cost<false>), grid, block, a.ldsBytes, st, a.scene, a.cam, a.fp, a.passSeeds, a.stackEntries, a.cost);
         break;
 #undef TN_LAUNCH2
     case PK_LIGHTS:

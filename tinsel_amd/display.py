@@ -7,6 +7,9 @@ are byte-identical to the ones the reference produces from the same float image:
   PNG  8-bit RGB, no interlace, filter 0 on every row, ONE IDAT holding a zlib stream of STORED deflate blocks
        of at most 65535 bytes (header 0x08 0x1D), Adler-32, IEND.
   PFM  "PF\\n<W> <H>\\n-<max>\\n" then W*H*3 little-endian floats, rows in the order given.
+
+Beyond it: `cost_heatmap`, the heat map of a traversal-cost map (HipRenderer.render_cost) -- the view the reference names
+eComplexity and never draws.
 """
 import ctypes as C
 import struct
@@ -79,3 +82,37 @@ def pfm_bytes(image):
 def write_pfm(path, image):
     with open(path, "wb") as f:
         f.write(pfm_bytes(image))
+
+
+# cost_heatmap: the channels of a cost map (HipRenderer.render_cost) and the colour ramp it is drawn with.  The ramp is a fixed
+# piecewise-linear "heat" scale, brightness rising with cost: black at 0, red at 1/3, yellow at 2/3, white at 1 (of vmax).
+COST_CHANNELS = ("rays", "nodes", "tris", "prims")
+COST_RAMP = ((0.0, (0.0, 0.0, 0.0)), (1.0/3.0, (1.0, 0.0, 0.0)), (2.0/3.0, (1.0, 1.0, 0.0)), (1.0, (1.0, 1.0, 1.0)))
+
+
+def cost_mean(counts, channel, samples=1):
+    """[H,W] float64: the per-sample mean of one channel (index 0..3 or a COST_CHANNELS name) of an [H,W,4] cost map summed over
+    `samples` passes.  Zero samples: zero everywhere."""
+    c = COST_CHANNELS.index(channel) if isinstance(channel, str) else int(channel)
+    if not 0 <= c < 4:
+        raise ValueError("cost channel %r: want 0..3 or one of %s" % (channel, ", ".join(COST_CHANNELS)))
+    counts = np.asarray(counts)
+    if counts.ndim != 3 or counts.shape[2] != 4:
+        raise ValueError("cost map: want shape (H, W, 4), got %s" % (counts.shape,))
+    v = counts[..., c].astype(np.float64)
+    return v/samples if samples > 0 else np.zeros_like(v)
+
+
+def cost_heatmap(counts, channel, vmax=None, samples=1):
+    """RGBA float32 [H,W,4] (alpha 1) of one channel of a cost map: the per-sample mean (cost_mean) mapped linearly onto COST_RAMP,
+    0 -> black and `vmax` -> white, larger values clamped to white.  `vmax` defaults to the frame's largest mean; a frame with no
+    cost (or vmax <= 0) is black.  `write_png` takes the result as it is."""
+    mean = cost_mean(counts, channel, samples)
+    top = float(mean.max()) if vmax is None else float(vmax)
+    x = np.clip(mean/top, 0.0, 1.0) if top > 0.0 else np.zeros_like(mean)
+    stops = np.array([p for p, _ in COST_RAMP])
+    colours = np.array([rgb for _, rgb in COST_RAMP])
+    out = np.ones(mean.shape + (4,), np.float32)
+    for k in range(3):
+        out[..., k] = np.interp(x, stops, colours[:, k])
+    return out

@@ -2,6 +2,7 @@
 
     python -m tinsel_amd.headless [-spp=N] [-width=W] [-height=H] [-exposure=E] [-maxdepth=D]
                                   [-nlm=RADIUS[,FALLOFF]] [-rr=BOUNCE] [-out=image.png|image.pfm] [-save=state.npz] [-resume=state.npz]
+                                  [-complexity=rays|nodes|tris|prims]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -23,6 +24,10 @@ Conventions kept from main.cpp:
     (tests/test_gpu_display.py) -- and only a frame that differs in more is re-created.  Each frame prints what it cost to get ready.
 Beyond it: `.pfm` output of the normalised linear image (PfmSave layout), and -save / -resume of the accumulator
 (tinsel_hip_write_accum) so a long render can be continued bit-exactly.
+-complexity=CHANNEL draws the reference's eComplexity view (RenderMode, render.h:42-47; main.cpp binds it to key 2 and no
+renderer of the reference draws it): the traversal-cost map of maxSamples path-traced passes (HipRenderer.render_cost) instead of
+the image.  -out gets the heat map of CHANNEL's mean per sample (display.cost_heatmap) as a PNG, or those raw means as a PFM; the
+frame's mean per sample of all four channels is printed.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -33,7 +38,7 @@ import time
 import numpy as np
 
 from . import abi
-from .display import write_pfm, write_png
+from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
 from .renderer import Scene, create_gpu_renderer
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
@@ -42,7 +47,7 @@ FRAME_PASSES = 16          # numSamples of main.cpp:240
 def parse_args(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
-    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "over": {}}
+    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "over": {}}
     for a in argv[1:-1]:
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
@@ -57,6 +62,10 @@ def parse_args(argv):
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
         elif k in ("out", "save", "resume"):
+            cfg[k] = v
+        elif k == "complexity":
+            if v not in COST_CHANNELS:
+                raise SystemExit("-complexity=%s: want one of %s" % (v, "|".join(COST_CHANNELS)))
             cfg[k] = v
         else:
             raise SystemExit("unrecognised option -%s\n%s" % (k, __doc__))
@@ -138,8 +147,26 @@ def batch(cfg):
     return 0
 
 
+def complexity(r, cam, opt, cfg):
+    """-complexity: the cost map of passes [0, maxSamples) instead of the image (tinsel_hip_render_cost)"""
+    ts = time.perf_counter()
+    counts = r.render_cost(cam, opt, 0, opt.max_samples)
+    print("%d complexity: (%.4fms)" % (opt.max_samples, (time.perf_counter() - ts)*1000.0), flush=True)
+    paths = float(opt.width)*opt.height*opt.max_samples
+    print("mean per sample: " + " ".join("%s=%.4f" % (name, counts[..., c].sum(dtype=np.float64)/paths)
+                                         for c, name in enumerate(COST_CHANNELS)))
+    if cfg["out"]:
+        if cfg["out"].endswith(".pfm"):
+            write_pfm(cfg["out"], np.repeat(cost_mean(counts, cfg["complexity"], opt.max_samples)[..., None], 3, axis=2).astype(np.float32))
+        else:
+            write_png(cfg["out"], cost_heatmap(counts, cfg["complexity"], samples=opt.max_samples))
+        print("wrote %s" % cfg["out"])
+
+
 def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
+    if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
+        raise SystemExit("-complexity renders one cost map: no batch mode, -save or -resume")
     if "%" in cfg["file"]:
         return batch(cfg)
     t0 = time.perf_counter()
@@ -152,6 +179,10 @@ def main(argv=None):
         r.set_russian_roulette(over["rr"])       # opt-in; not the reference's behaviour (tinsel_hip.h)
     r.init(opt.width, opt.height)
     print("Created renderer in %fms" % ((time.perf_counter() - t0)*1000.0))
+    if cfg["complexity"]:
+        complexity(r, cam, opt, cfg)
+        r.close()
+        return 0
 
     samples = 0
     if cfg["resume"]:

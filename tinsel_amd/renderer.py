@@ -86,6 +86,7 @@ def load_library():
     L.tinsel_hip_reset_stats.argtypes = [vp]
     L.tinsel_hip_stats_detail.argtypes = [vp, vp]
     L.tinsel_hip_set_detail_counters.argtypes = [vp, ci]
+    L.tinsel_hip_render_cost.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -141,7 +142,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
-    "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
+    "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_render_cost", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
     "tinsel_hip_enable_kernel_timing", "tinsel_hip_set_batch_paths", "tinsel_hip_stack_entries",
     "tinsel_hip_nee_per_path", "tinsel_hip_last_error", "tinsel_pack_open", "tinsel_hip_read_batch_radiance", "tinsel_hip_leaf",
     "tinsel_hip_write_accum", "tinsel_hip_reserve", "tinsel_hip_set_russian_roulette", "tinsel_hip_set_mesh_bvh", "tinsel_hip_present", "tinsel_hip_present_async", "tinsel_hip_present_device_ptr", "tinsel_image_quantize_rgb8",
@@ -450,6 +451,16 @@ class HipRenderer:
 
     def set_detail_counters(self, on):
         _check(self._L.tinsel_hip_set_detail_counters(self._h, int(on)), "tinsel_hip_set_detail_counters")
+
+    def render_cost(self, camera, options, pass_begin=0, passes=1):
+        """Per-pixel traversal cost of path tracing passes [pass_begin, pass_begin + passes): an (H, W, 4) uint32 array of
+        {rays, internal BVH node visits, triangle tests, primitive tests} summed over the passes, as the reference algorithm
+        counts them (the quantities of stats_detail, on the scene BVH walk).  Pixels another shard owns are 0.  Leaves the
+        accumulator, pass index, statistics and tuning as they were (tinsel_hip_render_cost)."""
+        out = np.zeros((options.height, options.width, 4), np.uint32)
+        _check(self._L.tinsel_hip_render_cost(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes),
+                                              out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_cost")
+        return out
 
     def enable_kernel_timing(self, on):
         _check(self._L.tinsel_hip_enable_kernel_timing(self._h, int(on)), "tinsel_hip_enable_kernel_timing")
