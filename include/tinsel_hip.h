@@ -437,6 +437,13 @@ long long tinsel_hip_read_batch_radiance(tinsel_hip* r, float* out_rgbx, unsigne
 int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, int in_stride, const uint32_t* seeds,
                     float* out, int out_stride, const tinsel_camera* camera, int width, int height);
 
+/* Test hook: the tree of mesh primitive `primitive` that is in force now (the reference's or a device-built one,
+ * tinsel_hip_set_mesh_bvh), as the kernels read it: `capacity` >= numInternal 64-B Node64 records (tn_scene.h: both
+ * children's boxes {min.xyz, max.xyz}, then the left and right child refs, leaf bit 31 | triangle index) into `out_nodes`
+ * (may be NULL: meta only).  out_meta[7] = {root ref, numInternal, numTris, stackNeed, topCount, twoLeaves, inArena}.
+ * An arena mesh's tree is read from the arena's copy in HBM.  Synchronises.  Returns numInternal, or -1. */
+int tinsel_hip_mesh_tree(tinsel_hip* r, int primitive, void* out_nodes, int capacity, int* out_meta);
+
 /* Introspection: LDS traversal-stack entries per lane chosen for this scene, NEE rays per bounce. */
 int tinsel_hip_stack_entries(tinsel_hip* r);
 int tinsel_hip_nee_per_path(tinsel_hip* r);

@@ -29,6 +29,17 @@ class BVHNode(C.Structure):
     _fields_ = [("lower", Vec3), ("upper", Vec3), ("left_index", C.c_uint32), ("right_index_leaf", C.c_uint32)]
 
 
+class Node64(C.Structure):
+    """tn_scene.h Node64: one internal node of a mesh tree as the kernels read it (tinsel_hip_mesh_tree) -- both children's boxes,
+    then the child refs (bit 31 set: a leaf, the low bits its triangle index; clear: an internal node's index)"""
+    _fields_ = [("lmin", C.c_float * 3), ("lmax", C.c_float * 3), ("rmin", C.c_float * 3), ("rmax", C.c_float * 3),
+                ("left", C.c_uint32), ("right", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+LEAF_BIT = 0x80000000
+MESH_TREE_META = ("root", "numInternal", "numTris", "stackNeed", "topCount", "twoLeaves", "inArena")
+
+
 class Camera(C.Structure):
     _fields_ = [("position", Vec3), ("rotation", Vec4), ("fov", C.c_float),
                 ("shutter_start", C.c_float), ("shutter_end", C.c_float)]
@@ -168,7 +179,7 @@ FILTER_BOX, FILTER_GAUSSIAN = 0, 1
 GEOM_SPHERE, GEOM_PLANE, GEOM_MESH = 0, 1, 2
 PIPELINE_WAVEFRONT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT_SPLIT, PIPELINE_AUTO, PIPELINE_WAVEFRONT_PAIRED = 0, 1, 2, 3, 4
 
-assert C.sizeof(Transform) == 32 and C.sizeof(BVHNode) == 32 and C.sizeof(Camera) == 40
+assert C.sizeof(Transform) == 32 and C.sizeof(BVHNode) == 32 and C.sizeof(Camera) == 40 and C.sizeof(Node64) == 64
 assert C.sizeof(Material) == 128 and C.sizeof(MeshGeometry) == 64 and C.sizeof(Primitive) == 272
 assert C.sizeof(Filter) == 16 and C.sizeof(Options) == 48 and C.sizeof(PackHeader) == 256
 assert Primitive.geo.offset == 72 and Primitive.material.offset == 136 and Primitive.light_samples.offset == 264

@@ -565,6 +565,27 @@ int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, in
 }
 
 int tinsel_hip_stack_entries(tinsel_hip* r) { return r ? r->stackNeed : 0; }
+
+int tinsel_hip_mesh_tree(tinsel_hip* r, int primitive, void* out_nodes, int capacity, int* out_meta)
+{
+    lookahead_cancel(r);
+    if (!r || !out_meta || capacity < 0 || primitive < 0 || primitive >= r->scene.numPrims || r->primMesh[(size_t)primitive] < 0)
+        return fail("mesh_tree: bad arguments (a mesh primitive and a meta array of 7 ints)");
+    const DevMesh& dm = r->meshesNow[(size_t)r->primMesh[(size_t)primitive]];
+    const int meta[7] = { (int)dm.root, dm.numInternal, dm.numTris, dm.stackNeed, dm.topCount, dm.twoLeaves, dm.inArena };
+    memcpy(out_meta, meta, sizeof(meta));
+    if (!out_nodes)
+        return dm.numInternal;
+    if (capacity < dm.numInternal)
+        return fail("mesh_tree: capacity is smaller than the tree's node count");
+    // an arena mesh's tree as every launch stages it: the arena's copy in HBM
+    const unsigned char* src = dm.inArena ? r->scene.arena + dm.offNodes : reinterpret_cast<const unsigned char*>(dm.nodes);
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (dm.numInternal > 0)
+        HIP_TRY(hipMemcpy(out_nodes, src, sizeof(Node64)*(size_t)dm.numInternal, hipMemcpyDeviceToHost));
+    return dm.numInternal;
+}
 int tinsel_hip_walked_prims(tinsel_hip* r) { return (r && r->walkEnabled) ? r->walkPrims.count : 0; }
 int tinsel_hip_nee_per_path(tinsel_hip* r) { return r ? r->neePerPath : 0; }
 

@@ -247,15 +247,18 @@ __global__ __launch_bounds__(256) void k_ploc_nearest(const int* __restrict__ cl
     const float* src = boxes + (size_t)clusters[i]*6;
     for (int q = 0; q < 6; ++q)
         bi[q] = src[q];
-    float best = 3.0e38f;
+    // every cluster chooses a neighbour, whatever the areas: an area that overflows to inf (or is NaN: 0*inf in a flat box wider than
+    // FLT_MAX) counts as +inf, so the order over (area, index) stays total and its least pair is always mutual -- the round makes progress
+    float best = INFINITY;
     int bestJ = -1;
     const int lo = i - kPlocRadius < 0 ? 0 : i - kPlocRadius, hi = i + kPlocRadius >= c ? c - 1 : i + kPlocRadius;
     for (int j = lo; j <= hi; ++j)
     {
         if (j == i)
             continue;
-        const float a = ploc_area(bi, boxes + (size_t)clusters[j]*6);
-        if (a < best)           // ties: the LOWEST index wins (j ascends), on both sides of a pair -- so mutual choices still exist
+        float a = ploc_area(bi, boxes + (size_t)clusters[j]*6);
+        a = a == a ? a : INFINITY;
+        if (bestJ < 0 || a < best)      // ties: the LOWEST index wins (j ascends), on both sides of a pair -- so mutual choices still exist
         {
             best = a;
             bestJ = j;

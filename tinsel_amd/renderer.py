@@ -103,6 +103,8 @@ def load_library():
     L.tinsel_hip_present_device_ptr.argtypes = [vp]
     L.tinsel_image_quantize_rgb8.argtypes = [vp, ci, ci, vp]
     L.tinsel_hip_stack_entries.argtypes = [vp]
+    if hasattr(L, "tinsel_hip_mesh_tree"):             # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_mesh_tree.argtypes = [vp, ci, vp, ci, C.POINTER(C.c_int)]
     L.tinsel_hip_nee_per_path.argtypes = [vp]
     L.tinsel_hip_walked_prims.argtypes = [vp]
     if hasattr(L, "tinsel_hip_queue_counts"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
@@ -143,7 +145,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
     "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_render_cost", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
-    "tinsel_hip_enable_kernel_timing", "tinsel_hip_set_batch_paths", "tinsel_hip_stack_entries",
+    "tinsel_hip_enable_kernel_timing", "tinsel_hip_set_batch_paths", "tinsel_hip_stack_entries", "tinsel_hip_mesh_tree",
     "tinsel_hip_nee_per_path", "tinsel_hip_last_error", "tinsel_pack_open", "tinsel_hip_read_batch_radiance", "tinsel_hip_leaf",
     "tinsel_hip_write_accum", "tinsel_hip_reserve", "tinsel_hip_set_russian_roulette", "tinsel_hip_set_mesh_bvh", "tinsel_hip_present", "tinsel_hip_present_async", "tinsel_hip_present_device_ptr", "tinsel_image_quantize_rgb8",
     "tinsel_hip_walked_prims", "tinsel_hip_queue_counts", "tinsel_hip_set_lookahead", "tinsel_hip_set_arithmetic", "tinsel_hip_get_arithmetic", "tinsel_hip_refit_mesh", "tinsel_hip_set_probe_sampling",
@@ -523,6 +525,19 @@ class HipRenderer:
     @property
     def stack_entries(self):
         return self._L.tinsel_hip_stack_entries(self._h)
+
+    def mesh_tree(self, prim):
+        """Test hook: the tree of mesh primitive `prim` in force now (tinsel_hip_mesh_tree) -> (Node64 records as a structured
+        array with fields lmin, lmax, rmin, rmax [n,3] float32 and left, right uint32, {meta name: int})"""
+        meta = (C.c_int * 7)()
+        n = self._L.tinsel_hip_mesh_tree(self._h, int(prim), None, 0, meta)
+        _check(0 if n >= 0 else -1, "tinsel_hip_mesh_tree")
+        dt = np.dtype([("lmin", "<f4", 3), ("lmax", "<f4", 3), ("rmin", "<f4", 3), ("rmax", "<f4", 3),
+                       ("left", "<u4"), ("right", "<u4"), ("pad", "<u4", 2)])
+        nodes = np.zeros(n, dt)
+        got = self._L.tinsel_hip_mesh_tree(self._h, int(prim), nodes.ctypes.data_as(C.c_void_p), n, meta)
+        _check(0 if got == n else -1, "tinsel_hip_mesh_tree")
+        return nodes, dict(zip(abi.MESH_TREE_META, list(meta)))
 
     @property
     def nee_per_path(self):
