@@ -15,9 +15,10 @@
 #define tn tn_fast
 #include "tn_launch.h"
 
-extern "C" void tinsel_fast_launch_path_kernel(int which, const void* launchArgs, void* stream)
+// returns 0, or -1 where the launch record names no instance
+extern "C" int tinsel_fast_launch_path_kernel(const void* launchArgs, void* stream)
 {
-    tn_fast::launch_path_kernel(which, *static_cast<const tn_fast::LaunchArgs*>(launchArgs), (hipStream_t)stream);
+    return tn_fast::launch_path_kernel(*static_cast<const tn_fast::LaunchArgs*>(launchArgs), (hipStream_t)stream) ? 0 : -1;
 }
 
 // returns the number of kernels whose dynamic-LDS limit the runtime refused to raise; *first: the first one's name

@@ -42,13 +42,19 @@ int grid_mult(const tinsel_hip* r) { return r->tune.grid_mult > 0 ? r->tune.grid
 // the paired pipeline (tn_paired.h) takes flat-scan scenes without detail counting; anything else asked of it runs the split pipeline
 bool paired_can(const tinsel_hip* r) { return r->scene.flatScan != 0 && !r->countDetail; }
 
-// Which scan variants a scene gets (LaunchArgs::walkedOnly): 1 = every mesh primitive is walked by k_walk -- the lean kernels, compiled without
-// the inline mesh walk; 2 = every mesh primitive is walked OR is a quad (one internal node over two triangles: a lamp, a card), which the scan
-// tests with ray_mesh_two_leaves -- no stack, no loop -- where the arena is staged (glass.tin: sphere and cube walked, the lamp a quad);
-// 0 = some mesh is walked inline: the general kernels.
+// Where a path kernel that stages `staged` bytes of the arena into LDS finds the scene (SceneT, tn_scene.h): all of it in LDS (every mesh
+// rides in the arena), the arena in LDS beside meshes in HBM (MIXED), or in HBM
+enum Residency { RES_HBM, RES_LDS, RES_MIXED };
+Residency residency(const DevScene& sc, uint32_t staged) { return sc.allInArena ? RES_LDS : (staged != 0 && staged == sc.arenaBytes) ? RES_MIXED : RES_HBM; }
+
+// Which scan variants a scene gets (the W1 / W2 instances of tn_launch.h): 1 = every mesh primitive is walked by k_walk -- the lean kernels,
+// compiled without the inline mesh walk; 2 = every mesh primitive is walked OR is a quad (one internal node over two triangles: a lamp, a card),
+// which the scan tests with ray_mesh_two_leaves -- no stack, no loop -- where the arena is staged beside meshes in HBM (glass.tin: sphere and
+// cube walked, the lamp a quad); 0 = some mesh is walked inline: the general kernels.
 int walked_only_level(const tinsel_hip* r)
 {
-    if (!r->walkEnabled || r->walkPrims.count == 0 || r->countDetail || r->scene.allInArena)
+    const Residency res = residency(r->scene, r->scene.arenaLdsBytes);
+    if (!r->walkEnabled || r->walkPrims.count == 0 || r->countDetail || res == RES_LDS)
         return 0;
     int meshPrims = 0, quads = 0;
     for (size_t i = 0; i < r->primMesh.size(); ++i)
@@ -62,8 +68,7 @@ int walked_only_level(const tinsel_hip* r)
     }
     if (meshPrims == r->walkPrims.count)
         return 1;
-    const bool mixedArena = r->scene.arenaLdsBytes != 0 && r->scene.arenaLdsBytes == r->scene.arenaBytes;
-    if (r->tune.quads_in_scan != 0 && mixedArena && meshPrims == r->walkPrims.count + quads)
+    if (r->tune.quads_in_scan != 0 && res == RES_MIXED && meshPrims == r->walkPrims.count + quads)
         return 2;
     return 0;
 }
@@ -206,7 +211,7 @@ size_t stack_bytes(const tinsel_hip* r) { return stack_bytes(r, r->stackNeed); }
 
 // The path kernels exist twice (tn_launch.h): this translation unit's, bit-identical to the CPU oracle, and
 // tinsel_fast.hip's, built under the tolerance contract.  tinsel_hip_set_arithmetic picks the arm.
-extern "C" void tinsel_fast_launch_path_kernel(int which, const void* launchArgs, void* stream);
+extern "C" int tinsel_fast_launch_path_kernel(const void* launchArgs, void* stream);
 extern "C" int tinsel_fast_prepare_path_kernels(int sharedMemLimit, const char** first);
 extern "C" unsigned tinsel_fast_launch_args_size(void);
 
@@ -227,13 +232,11 @@ void prepare_kernels_once(tinsel_hip* r)
     r->pathKernelsPrepared = true;
 }
 
-void launch_path(tinsel_hip* r, int which, const LaunchArgs& a, hipStream_t st)
+int launch_path(tinsel_hip* r, const LaunchArgs& a, hipStream_t st)
 {
     prepare_kernels_once(r);
-    if (r->arith == TINSEL_ARITH_FAST)
-        tinsel_fast_launch_path_kernel(which, &a, st);
-    else
-        launch_path_kernel(which, a, st);
+    const bool ok = r->arith == TINSEL_ARITH_FAST ? tinsel_fast_launch_path_kernel(&a, st) == 0 : launch_path_kernel(a, st);
+    return ok ? 0 : fail("launch: no path-kernel instance " + std::to_string(a.variant));
 }
 
 // What cutting a batch into regions depends on (streaming_grid, cut_regions): plain values, no renderer
@@ -448,8 +451,100 @@ bool plan_bounce(const tinsel_hip* r, int* resident)
     return pools;
 }
 
+// k_walk's launches of a render call (plan_walk): instance, workgroup, workgroups per CU, dynamic LDS, the job's fixed part
+struct WalkPlan
+{
+    int variant = PK_NONE, block = 256, perCU = 1;
+    bool single = false;                // ONE walked primitive: k_walk; else k_walk_rays (a work item is a ray)
+    uint32_t ldsBytes = 0;
+    WalkJob job = {};
+};
+
+// k_swalk's launches (plan_swalk): as WalkPlan, an instance per ray kind, and the arena bytes it stages (its scene.arenaLdsBytes)
+struct SwalkPlan
+{
+    int extend = PK_NONE, shadow = PK_NONE, block = kBlock, perCU = 32;
+    uint32_t ldsBytes = 0, arenaLds = 0;
+    SwalkJob job = {};
+};
+
+// k_walk (tn_walk.h): closest hits of the front rays of a queue against the large meshes in HBM, ahead of the scan kernel.  One 1024-thread
+// workgroup per CU whose LDS holds the traversal stacks and, in what is left of the 160 KB, the top of the walked trees; trees too deep for
+// that (a device-built LBVH of 524k triangles: 48 entries per lane) run 256-thread workgroups without a staged top.
+WalkPlan plan_walk(const tinsel_hip* r)
+{
+    const tinsel_hip_tuning& t = r->tune;
+    WalkPlan w;
+    WalkJob& job = w.job;
+    // (measured and settled, profiles/EXPERIMENTS.md: one resident set of workgroups; a refill once 24 lanes idle; a triangle phase once 8 wait)
+    const int gridMult = t.walk_grid_mult > 0 ? t.walk_grid_mult : 1;
+    job.refillMin = std::min(64, std::max(1, t.walk_refill_min > 0 ? t.walk_refill_min : 24));
+    job.leafMin = std::min(64, std::max(1, t.walk_leaf_min > 0 ? t.walk_leaf_min : 8));
+    job.numPrims = r->walkPrims.count;
+    job.prof = r->walkProf;
+    int entries = 1;
+    for (int k = 0; k < kWalkMaxPrims && k < r->walkPrims.count; ++k)
+    {
+        job.prim[k] = r->walkPrims.prim[k];
+        entries = std::max(entries, r->meshesNow[(size_t)r->walkPrimMesh[k]].stackNeed);
+    }
+    // ONE walked primitive: its tree as kernel-argument scalars (tinsel_hip_tuning::walk_single = 0: per-lane pointers as for several; tests)
+    w.single = r->walkPrims.count == 1 && t.walk_single != 0;
+    // (k_walk_rays keeps one LDS entry per walked primitive behind its control words: tn_walk.h kWalkPrimWords)
+    const size_t ctl = (kWalkCtlWords + (w.single ? 0 : kWalkMaxPrims*kWalkPrimWords))*sizeof(uint32_t);
+    // n stack entries per lane in LDS (tinsel_hip_tuning::walk_lds_stack, default 8; 0: the deepest tree's need, one workgroup per CU), the
+    // rest of the deepest tree's need in HBM, and TWO 1024-thread workgroups per CU (8 waves per SIMD at 64 VGPRs) sharing the CU's
+    // LDS: the 524k-triangle config's k_walk 19.0 -> 16.6 ms per 32 passes (2042 -> 2199 Msamples/s; 6 entries 17.2, 12 entries 16.7),
+    // glass 10.4 -> 9.9; results unchanged (a stack entry is a stack entry wherever it lives)
+    const int ldsStackEnv = t.walk_lds_stack >= 0 ? t.walk_lds_stack : 8;
+    const bool twoPerCU = ldsStackEnv > 0 && !t.walk_block;
+    const int ldsEntries = twoPerCU ? std::min(entries, std::max(1, ldsStackEnv)) : entries;
+    const int rows = w.single ? kWalkLaneRows : kWalkRayRows;      // (+ the per-lane rows, tn_walk.h)
+    const size_t ldsBudget = twoPerCU ? (size_t)r->sharedMemLimit/2 : (size_t)r->sharedMemLimit;
+    const bool big = t.walk_block ? t.walk_block == 1024 : (size_t)(ldsEntries + rows)*1024*sizeof(uint32_t) + ctl + 16384 <= ldsBudget;
+    w.block = big ? 1024 : 256;
+    size_t lds = (size_t)(ldsEntries + rows)*w.block*sizeof(uint32_t) + ctl;
+    if (big)
+    {
+        // what is left of the CU's LDS goes to the tree tops, in primitive order
+        size_t room = (ldsBudget - lds)/sizeof(Node64);
+        for (int k = 0; k < r->walkPrims.count && room > 0; ++k)
+        {
+            const int n = (int)std::min<size_t>(room, (size_t)r->meshesNow[(size_t)r->walkPrimMesh[k]].topCount);
+            job.topCount[k] = n;
+            room -= (size_t)n;
+            lds += (size_t)n*sizeof(Node64);
+        }
+    }
+    w.ldsBytes = (uint32_t)lds;
+    w.perCU = big ? gridMult*(twoPerCU ? 2 : 1) : gridMult*4;
+    job.stackEntries = ldsEntries;
+    job.overflowEntries = entries - ldsEntries;        // (the columns: ensure_walk_overflow)
+    w.variant = w.single ? (!big ? PK_WALK_SINGLE_256 : twoPerCU ? PK_WALK_SINGLE_1024X2 : PK_WALK_SINGLE_1024)
+                         : (!big ? PK_WALK_RAYS_256 : twoPerCU ? PK_WALK_RAYS_1024X2 : PK_WALK_RAYS_1024);
+    return w;
+}
+
+// k_swalk (tn_swalk.h): 1024-thread workgroups with the whole arena beside their stacks where it fits (the whole scene in LDS, or MIXED where a
+// mesh lives in HBM), else 256-thread ones with generic pointers (tinsel_hip_tuning::swalk_lds = 0: always)
+SwalkPlan plan_swalk(const tinsel_hip* r)
+{
+    SwalkPlan s;
+    s.job = { nullptr, nullptr, 0, r->stackNeed, 32, 16 };         // (refill / leaf phase at 32 / 16 lanes: profiles/r03_d_ab_swalk.txt, r03_e_ab_swalk.txt)
+    const size_t bigLds = ((size_t)r->stackNeed*1024 + kSwalkCtlWords)*sizeof(uint32_t) + r->scene.arenaBytes;
+    const bool big = r->tune.swalk_lds != 0 && bigLds <= (size_t)r->sharedMemLimit;
+    const bool allInArena = std::all_of(r->meshesNow.begin(), r->meshesNow.end(), [](const DevMesh& m) { return m.inArena != 0; });
+    s.extend = !big ? PK_SWALK_EXTEND : allInArena ? PK_SWALK_EXTEND_LDS : PK_SWALK_EXTEND_MIXED;
+    s.shadow = !big ? PK_SWALK_SHADOW : allInArena ? PK_SWALK_SHADOW_LDS : PK_SWALK_SHADOW_MIXED;
+    s.block = big ? 1024 : kBlock;
+    s.perCU = big ? 1 : 32;
+    s.arenaLds = big ? r->scene.arenaBytes : r->scene.arenaLdsBytes;
+    s.ldsBytes = (uint32_t)(((size_t)r->stackNeed*s.block + kSwalkCtlWords)*sizeof(uint32_t) + s.arenaLds);
+    return s;
+}
+
 // What a render call's batches run, decided once per call (plan_batch), each field from the ones before it: pipeline, overlap, capacity, k_walk,
-// the scan kernels' stack and LDS, k_swalk, the split pipeline's light and shade launches, k_bounce's pools and resident workgroups.
+// the scan kernels' stack and LDS, k_swalk, k_shade's arena and LDS, k_bounce's pools and resident workgroups, and the instance of every launch.
 // render_impl, ensure_batch / alloc_dense, render_batch and the launch helpers read it; none decides again.
 struct BatchPlan
 {
@@ -463,18 +558,20 @@ struct BatchPlan
     // k_walk (split, paired): its records fit (allocated; `walkRays` rays per position), and it runs (not while the detail counters count the inline walk)
     bool walkRecords = false, walk = false;
     size_t walkRays = 0;
-    // the scan kernels (walked_only_level: their lean variants with the scene-level stack only): variant, stack entries, dynamic LDS
-    int walkedLevel = 0, stackScan = 0;
+    // the scan kernels: stack entries (the scene level's only for the lean variants, walked_only_level), dynamic LDS
+    int stackScan = 0;
     uint32_t ldsTrace = 0;
     // a walk list is allocated (k_walk's, or k_swalk's for scenes the flat scan cannot take): k_seg_prefix bounds the regions
     bool workList = false;
     bool sceneWalk = false;             // k_swalk in the place of k_extend / k_shadow (split)
-    // split: the light samples drawn by k_extend (lightsInMixed: its variant for a staged arena with meshes in HBM); k_shade_sorted;
-    // the arena k_shade stages and the LDS of k_shade and k_lights
-    bool lightsInMixed = false, lightsInExtend = false, shadeSorted = false;
+    // split: the arena k_shade stages, the dynamic LDS of k_shade and k_lights
     uint32_t arenaLdsShade = 0, ldsShade = 0, ldsLights = 0;
     bool pools = false;                 // fused: k_bounce's shading pools (plan_bounce; its resident workgroups are regions.resident)
     RegionSpec regions;                 // how a batch is cut (render_batch bounds it by the lane's arrays)
+    // the instance of each launch (tn_launch.h; PK_NONE: not launched -- k_lights where k_extend draws the light samples)
+    int generate = PK_GENERATE, extend = PK_NONE, shadow = PK_NONE, lights = PK_NONE, shade = PK_NONE, step = PK_NONE, bounce = PK_NONE, mega = PK_NONE;
+    WalkPlan walkPlan;                  // where `walk`
+    SwalkPlan swalkPlan;                // where `sceneWalk`
 };
 
 // perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve)
@@ -524,8 +621,8 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
                     (double)p.capacity*(double)p.walkRays*r->walkPrims.count < 2147483648.0;
     p.walk = p.walkRecords && !r->countDetail;
 
-    p.walkedLevel = p.walk ? walked_only_level(r) : 0;
-    p.stackScan = p.walkedLevel ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
+    const int wl = p.walk ? walked_only_level(r) : 0;          // the lean scan variants (W1 / W2)
+    p.stackScan = wl ? std::max(1, pick_stack(r->sceneStackNeed)) : r->stackNeed;
     p.ldsTrace = (uint32_t)stack_bytes(r, p.stackScan);
 
     p.workList = p.walkRecords || (split && !r->scene.flatScan);
@@ -535,13 +632,12 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     // in the place of k_extend / k_shadow; the detail counters count the inline walks
     p.sceneWalk = split && r->tune.scene_walk != 0 && !r->scene.flatScan && !r->countDetail && !p.walk;
 
-    // the lean k_extend draws the light samples itself (tn_launch.h launches it when walkedOnly and not counting)
-    // ... and so does the variant for a staged arena with meshes in HBM (glass): without the SLP vectoriser it fits 128 VGPRs and
-    // saves k_lights' pass over the path state (k_extend 5.7 + k_lights 7.1 -> 11.2 ms per 32 passes, glass 1366 -> 1425 Msamples/s;
-    // round 2, 170 VGPRs: 29.1 apart, 31.5 together; profiles/r03_k_ab_lights_in_extend.txt)
-    const bool mixedArena = !r->scene.allInArena && r->scene.arenaLdsBytes != 0 && r->scene.arenaLdsBytes == r->scene.arenaBytes;
-    p.lightsInMixed = split && !p.walkedLevel && !r->countDetail && mixedArena && !(r->tune.scene_walk != 0 && !r->scene.flatScan);
-    p.lightsInExtend = p.walkedLevel != 0 || p.lightsInMixed;
+    // the lean k_extend draws the light samples itself, and so does the variant for a staged arena with meshes in HBM (glass): without the
+    // SLP vectoriser it fits 128 VGPRs and saves k_lights' pass over the path state (k_extend 5.7 + k_lights 7.1 -> 11.2 ms per 32 passes,
+    // glass 1366 -> 1425 Msamples/s; round 2, 170 VGPRs: 29.1 apart, 31.5 together; profiles/r03_k_ab_lights_in_extend.txt)
+    const Residency res = residency(r->scene, r->scene.arenaLdsBytes);
+    const bool lightsInMixed = split && !wl && !r->countDetail && res == RES_MIXED && !(r->tune.scene_walk != 0 && !r->scene.flatScan);
+    const bool lightsDrawn = wl != 0 || lightsInMixed;
     // k_shade has no traversal stacks in LDS and reads a material per path: an arena too large to sit beside the stacks of the
     // trace kernels (32 KB) is still staged by it up to 60 KB (many_spheres, 39 KB of primitive and material records: k_shade
     // 7.8 -> 6.7 ms; staged in the trace kernels too it costs them their fourth wave per SIMD, 1380 -> 1280 Msamples/s, and
@@ -555,13 +651,31 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     // pipeline veach 1902 -> 2003, features 1047 -> 1093; it loses in an enclosed scene (glass: no ray leaves, 17.5 -> 19.3 ms) and
     // where k_walk runs (the 524k-triangle config 6.47 -> 6.86 ms) (profiles/r03_g_ab_shade_sorted.txt, r04_e_rates.md).
     // tinsel_hip_tuning::shade_sorted = 0 / 1 forces either arm (A/B, tests).
-    p.shadeSorted = (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !p.walk)) &&
-                    (size_t)p.ldsShade + kShadeListWords*sizeof(uint32_t) <= (size_t)r->sharedMemLimit;
+    const bool sorted = (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !p.walk)) &&
+                        (size_t)p.ldsShade + kShadeListWords*sizeof(uint32_t) <= (size_t)r->sharedMemLimit;
+    if (sorted)
+        p.ldsShade += (uint32_t)(kShadeListWords*sizeof(uint32_t));
 
     int resident = kBounceWaves;
     if (fused)
         p.pools = plan_bounce(r, &resident);
     p.regions = region_spec(r->tune, r->numCUs, r->neePerPath, fused, resident);
+
+    // the instances (tn_launch.h) by where the scene lives; the counting ones have no MIXED form (wl != 0: not counting, not all in LDS)
+    const bool count = r->countDetail, lds = res == RES_LDS, mixed = !count && res == RES_MIXED,
+               mixedShade = !count && residency(r->scene, p.arenaLdsShade) == RES_MIXED;
+    p.extend = wl == 2 ? PK_EXTEND_W2_MIXED : wl && mixed ? PK_EXTEND_W1_MIXED : wl ? PK_EXTEND_W1 : lightsInMixed ? PK_EXTEND_MIXED_LIGHTS :
+               mixed ? PK_EXTEND_MIXED : count ? (lds ? PK_EXTEND_COUNT_LDS : PK_EXTEND_COUNT) : lds ? PK_EXTEND_LDS : PK_EXTEND;
+    p.shadow = wl == 2 ? PK_SHADOW_W2_MIXED : wl && mixed ? PK_SHADOW_W1_MIXED : wl ? PK_SHADOW_W1 :
+               mixed ? PK_SHADOW_MIXED : count ? (lds ? PK_SHADOW_COUNT_LDS : PK_SHADOW_COUNT) : lds ? PK_SHADOW_LDS : PK_SHADOW;
+    p.step = wl == 2 ? PK_STEP_W2_MIXED : wl && mixed ? PK_STEP_W1_MIXED : wl ? PK_STEP_W1 : mixed ? PK_STEP_MIXED : lds ? PK_STEP_LDS : PK_STEP;
+    p.lights = lightsDrawn ? PK_NONE : mixed ? PK_LIGHTS_MIXED : lds ? PK_LIGHTS_LDS : PK_LIGHTS;
+    p.shade = sorted ? (mixedShade ? PK_SHADE_SORTED_MIXED : lds ? PK_SHADE_SORTED_LDS : PK_SHADE_SORTED) : (mixedShade ? PK_SHADE_MIXED : lds ? PK_SHADE_LDS : PK_SHADE);
+    // (the detail-counting variants walk the scene BVH: nothing to defer)
+    p.bounce = count ? (lds ? PK_BOUNCE_COUNT_LDS : PK_BOUNCE_COUNT) : r->scene.deferMeshes ? (lds ? PK_BOUNCE_LDS_DEFER : PK_BOUNCE_DEFER) : lds ? PK_BOUNCE_LDS : PK_BOUNCE;
+    p.mega = count ? (lds ? PK_MEGA_COUNT_LDS : PK_MEGA_COUNT) : lds ? PK_MEGA_LDS : PK_MEGA;
+    p.walkPlan = p.walk ? plan_walk(r) : WalkPlan();
+    p.swalkPlan = p.sceneWalk ? plan_swalk(r) : SwalkPlan();
     return p;
 }
 
@@ -605,8 +719,32 @@ int alloc_dense(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& lane, 
 }
 
 // the batch buffers for a render call's plan: the radiance of p.slots paths, p.lanes lanes of dense state; kept where they hold the plan
+// k_walk's stack entries beyond the LDS ones (WalkJob::overflow): columns for the widest grid of the plan (numCUs x perCU workgroups) in every
+// lane, allocated with the batch: nothing is freed or allocated between the launches of a batch
+int ensure_walk_overflow(tinsel_hip* r, const BatchPlan& p)
+{
+    const WalkPlan& w = p.walkPlan;
+    const size_t need = p.walk ? (size_t)r->numCUs*(size_t)w.perCU*(size_t)w.block*(size_t)w.job.overflowEntries : 0;
+    for (int k = 0; k < p.lanes && need; ++k)
+    {
+        tinsel_hip::DenseLane& L = r->lane[k];
+        if (L.walkOverflowCap >= need)
+            continue;
+        if (L.walkOverflow)
+            (void)hipDeviceSynchronize();       // (another stream's launch may still use the old columns)
+        (void)hipFree(L.walkOverflow);
+        L.walkOverflow = nullptr;
+        L.walkOverflowCap = hipMalloc((void**)&L.walkOverflow, need*sizeof(uint32_t)) == hipSuccess ? need : 0;
+        if (!L.walkOverflowCap)
+            return fail("k_walk: no memory for the stack overflow");
+    }
+    return 0;
+}
+
 int ensure_batch(tinsel_hip* r, const BatchPlan& p, int maxDepth)
 {
+    if (ensure_walk_overflow(r, p))
+        return -1;
     const int K = r->neePerPath;
     const tinsel_hip::DenseLane& lane = r->lane[0];
     if (r->batchSlots >= p.slots && r->batchStateSlots >= p.stateSlots && r->batchLanes >= p.lanes && r->batchNee == K && r->batchDepth >= maxDepth &&
@@ -662,172 +800,77 @@ uint32_t seg_step(uint32_t numRegions)
     return step;
 }
 
-// k_walk (tn_walk.h): closest hits of the front rays of `queue` against the large meshes in HBM, ahead of the scan kernel.
-// One 1024-thread workgroup per CU whose LDS holds the traversal stacks and, in what is left of the 160 KB, the top of
-// the walked trees; trees too deep for that (a device-built LBVH of 524k triangles: 48 entries per lane) run 256-thread
-// workgroups without a staged top.
-// (mixed: the paired pipeline's walk -- K shadow rays + the extension ray of every queued position, tn_paired.h)
-// `slots`: the paths of the batch (or chunk) lane L traces
+// A walk's work list in lane L: k_seg_prefix over the regions, then their front entries (back == null: k_walk's paths / shadow-ray bundles
+// whose ray enters a walked mesh's box) or every live entry, front and back (k_swalk's)
+int work_list(tinsel_hip* r, const tinsel_hip::DenseLane& L, hipStream_t st, const LaunchArgs& a, const uint32_t* front, const uint32_t* back)
+{
+    const SplitState& ss = a.ss;
+    ScopedTimer t(r, KN_SEG, st);
+    if (ss.numRegions > seg_prefix_max_regions(r))
+        return fail("k_seg_prefix: " + std::to_string(ss.numRegions) + " regions do not fit its LDS (tinsel_hip_tuning::grid_mult too large for this device)");
+    hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, front, back, ss.numRegions, seg_step(ss.numRegions), L.segPrefix);
+    if (back)
+        hipLaunchKernelGGL(k_seg_expand_all, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, front, back, (const uint32_t*)L.segPrefix, ss, L.walkList);
+    else
+        hipLaunchKernelGGL(k_seg_expand, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, front, (const uint32_t*)L.segPrefix, ss, L.walkList);
+    return 0;
+}
+
+// k_walk (plan_walk) over the front rays of a queue.  (mixed: the paired pipeline's walk -- K shadow rays + the extension ray of every queued
+// position, tn_paired.h.)  `slots`: the paths of the batch (or chunk) lane L traces
 int launch_walk(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs a, size_t slots, const uint32_t* regionCounts,
                 bool shadowRays, bool mixed = false)
 {
-    // (measured and settled, profiles/EXPERIMENTS.md: one resident set of workgroups; a refill once 24 lanes idle; a triangle phase once 8 wait)
-    const int gridMult = r->tune.walk_grid_mult > 0 ? r->tune.walk_grid_mult : 1, refillMin = r->tune.walk_refill_min > 0 ? r->tune.walk_refill_min : 24, leafMin = r->tune.walk_leaf_min > 0 ? r->tune.walk_leaf_min : 8;
-    const int forceBlock = r->tune.walk_block;
-    prepare_kernels_once(r);
-    // the work list: the front entries of every region (paths / shadow-ray bundles whose ray enters a walked mesh's box)
+    const WalkPlan& w = p.walkPlan;
     const SplitState& ss = a.ss;
-    const uint32_t step = seg_step(ss.numRegions);
-    {
-        ScopedTimer t(r, KN_SEG, st);
-        if (ss.numRegions > seg_prefix_max_regions(r))
-            return fail("k_seg_prefix: " + std::to_string(ss.numRegions) + " regions do not fit its LDS (tinsel_hip_tuning::grid_mult too large for this device)");
-        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, regionCounts, (const uint32_t*)nullptr, ss.numRegions, step, L.segPrefix);
-        hipLaunchKernelGGL(k_seg_expand, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, regionCounts, (const uint32_t*)L.segPrefix, ss, L.walkList);
-    }
+    if (work_list(r, L, st, a, regionCounts, nullptr))
+        return -1;
     WalkJob& job = a.walk;
+    job = w.job;
     job.queue = L.walkList;
     job.frontCount = L.segPrefix + ss.numRegions;
     job.rayO = ss.rayO[a.bounce & 1];
     job.rayD = ss.rayD[a.bounce & 1];
-    job.nee = ss.neeRay;
+    const bool paired = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED;
+    job.nee = paired ? ss.pairRay[a.bounce & 1] : ss.neeRay;
     job.neeStride = ss.capacity;
     job.neeTime = ss.neeTime;
     job.rec = L.walkRec;
     job.neePerPath = shadowRays ? r->neePerPath : 0;
-    job.mixed = 0;
-    if (p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED)
-    {
-        job.nee = ss.pairRay[a.bounce & 1];
-        job.mixed = mixed ? 1 : 0;
-        if (shadowRays && !mixed)
-            job.mixed = 2;          // shadow rays only, their time in the state (tn_walk.h reads rayO[slot].w whenever `mixed` is set)
-    }
-    job.numPrims = r->walkPrims.count;
-    int entries = 1;
-    for (int k = 0; k < kWalkMaxPrims; ++k)
-    {
-        job.prim[k] = k < r->walkPrims.count ? r->walkPrims.prim[k] : 0;
-        job.topCount[k] = 0;
-        if (k < r->walkPrims.count)
-            entries = std::max(entries, r->meshesNow[(size_t)r->walkPrimMesh[k]].stackNeed);
-    }
-    job.stackEntries = entries;
-    job.prof = r->walkProf;
-    job.refillMin = std::min(64, std::max(1, refillMin));
-    job.leafMin = std::min(64, std::max(1, leafMin));
-    // ONE walked primitive: its tree as kernel-argument scalars (tinsel_hip_tuning::walk_single = 0: per-lane pointers as for several; tests)
-    a.walkSingle = (r->walkPrims.count == 1 && r->tune.walk_single != 0) ? 1 : 0;
-
-    // (k_walk_rays keeps one LDS entry per walked primitive behind its control words: tn_walk.h kWalkPrimWords)
-    const size_t ctl = (kWalkCtlWords + (a.walkSingle ? 0 : kWalkMaxPrims*kWalkPrimWords))*sizeof(uint32_t);
-    // n stack entries per lane in LDS (tinsel_hip_tuning::walk_lds_stack, default 8; 0: the deepest tree's need, one workgroup per CU), the
-    // rest of the deepest tree's need in HBM, and TWO 1024-thread workgroups per CU (8 waves per SIMD at 64 VGPRs) sharing the CU's
-    // LDS: the 524k-triangle config's k_walk 19.0 -> 16.6 ms per 32 passes (2042 -> 2199 Msamples/s; 6 entries 17.2, 12 entries 16.7),
-    // glass 10.4 -> 9.9; results unchanged (a stack entry is a stack entry wherever it lives)
-    const int ldsStackEnv = r->tune.walk_lds_stack >= 0 ? r->tune.walk_lds_stack : 8;
-    const bool twoPerCU = ldsStackEnv > 0 && !forceBlock;
-    const int ldsEntries = twoPerCU ? std::min(entries, std::max(1, ldsStackEnv)) : entries;
-    job.stackEntries = ldsEntries;
-    job.overflow = nullptr;
-    job.overflowEntries = 0;
-    const size_t stackBig = (size_t)(ldsEntries + (a.walkSingle ? kWalkLaneRows : kWalkRayRows))*1024*sizeof(uint32_t);     // (+ the per-lane rows, tn_walk.h)
-    const size_t ldsBudget = twoPerCU ? (size_t)r->sharedMemLimit/2 : (size_t)r->sharedMemLimit;
-    const bool big = forceBlock ? forceBlock == 1024 : stackBig + ctl + 16384 <= ldsBudget;
-    const int block = big ? 1024 : 256;
-    size_t lds = (size_t)(ldsEntries + (a.walkSingle ? kWalkLaneRows : kWalkRayRows))*block*sizeof(uint32_t) + ctl;
-    if (big)
-    {
-        // what is left of the CU's LDS goes to the tree tops, in primitive order
-        size_t room = (ldsBudget - lds)/sizeof(Node64);
-        for (int k = 0; k < r->walkPrims.count && room > 0; ++k)
-        {
-            const int n = (int)std::min<size_t>(room, (size_t)r->meshesNow[(size_t)r->walkPrimMesh[k]].topCount);
-            job.topCount[k] = n;
-            room -= (size_t)n;
-            lds += (size_t)n*sizeof(Node64);
-        }
-    }
+    job.mixed = !paired ? 0 : mixed ? 1 : shadowRays ? 2 : 0;      // (2: shadow rays only, their time in the state: tn_walk.h)
+    job.overflow = job.overflowEntries ? L.walkOverflow : nullptr;
     // (a work item is a ray; with several walked primitives a lane keeps its ray as position | k << 27 while primitives are left: tn_walk.h)
     // (k_walk_rays, whatever the number of walked primitives: ADVICE r05)
-    if (!a.walkSingle && (ss.capacity >= (1u << 27) || r->neePerPath >= 32))
+    if (!w.single && (ss.capacity >= (1u << 27) || r->neePerPath >= 32))
         return fail("k_walk_rays: batch too large (>= 2^27 positions) or too many shadow rays per path (>= 32): lower tinsel_hip_tuning::batch_paths");
     const size_t items = slots*(size_t)((shadowRays && r->neePerPath > 1 ? r->neePerPath : 1) + (mixed ? 1 : 0));
-    const int perCU = big ? gridMult*(twoPerCU ? 2 : 1) : gridMult*4;
-    a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + block - 1)/block, (size_t)r->numCUs*(size_t)perCU));
-    a.walkBig = big ? (twoPerCU ? 2 : 1) : 0;
-    a.ldsBytes = (uint32_t)lds;
-    if (ldsEntries < entries)
-    {
-        // the overflow columns are sized for the WIDEST grid this function launches (numCUs x perCU workgroups), once: nothing is freed or
-        // allocated between the launches of a batch
-        const size_t need = (size_t)r->numCUs*(size_t)perCU*(size_t)block*(size_t)(entries - ldsEntries);
-        if (L.walkOverflowCap < need)
-        {
-            if (L.walkOverflow)
-            {
-                (void)hipDeviceSynchronize();       // (another stream's launch may still use the old columns)
-                (void)hipFree(L.walkOverflow);
-            }
-            L.walkOverflow = nullptr;
-            L.walkOverflowCap = 0;
-            if (hipMalloc((void**)&L.walkOverflow, need*sizeof(uint32_t)) == hipSuccess)
-                L.walkOverflowCap = need;
-        }
-        job.overflow = L.walkOverflow;
-        job.overflowEntries = entries - ldsEntries;
-        if (!job.overflow)
-            return fail("k_walk: no memory for the stack overflow");
-    }
+    a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + w.block - 1)/w.block, (size_t)r->numCUs*(size_t)w.perCU));
+    a.variant = w.variant;
+    a.ldsBytes = w.ldsBytes;
     ScopedTimer t(r, KN_WALK, st);
-    launch_path(r, PK_WALK, a, st);
-    return 0;
+    return launch_path(r, a, st);
 }
 
-// k_swalk (tn_swalk.h): the scene-level walk with ray replacement, for scenes the flat scan cannot take.  The list: every live
+// k_swalk (plan_swalk): the scene-level walk with ray replacement, for scenes the flat scan cannot take.  The list: every live
 // entry of every region (front and back), regions in index order -- the workgroups' static ranges are image patches, coherent rays.
-int launch_swalk(tinsel_hip* r, const tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs a, size_t slots, const uint32_t* front, const uint32_t* back,
-                 bool shadowRays)
+int launch_swalk(tinsel_hip* r, const BatchPlan& p, const tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs a, size_t slots, const uint32_t* front,
+                 const uint32_t* back, bool shadowRays)
 {
-    const int refillMin = 32, leafMin = 16;         // (settled: profiles/r03_d_ab_swalk.txt, r03_e_ab_swalk.txt)
-    const bool noLds = r->tune.swalk_lds == 0;
-    const SplitState& ss = a.ss;
-    const uint32_t step = seg_step(ss.numRegions);
-    {
-        ScopedTimer t(r, KN_SEG, st);
-        if (ss.numRegions > seg_prefix_max_regions(r))
-            return fail("k_seg_prefix: " + std::to_string(ss.numRegions) + " regions do not fit its LDS");
-        hipLaunchKernelGGL(k_seg_prefix, dim3(1), dim3(kSegBlock), ss.numRegions*sizeof(uint32_t), st, front, back, ss.numRegions, step, L.segPrefix);
-        hipLaunchKernelGGL(k_seg_expand_all, dim3((unsigned)std::max(1, a.grid)), dim3(kBlock), 0, st, front, back, (const uint32_t*)L.segPrefix, ss, L.walkList);
-    }
+    const SwalkPlan& w = p.swalkPlan;
+    if (work_list(r, L, st, a, front, back))
+        return -1;
     SwalkJob& job = a.swalk;
+    job = w.job;
     job.list = L.walkList;
-    job.count = L.segPrefix + ss.numRegions;
+    job.count = L.segPrefix + a.ss.numRegions;
     job.neePerPath = shadowRays ? r->neePerPath : 0;
-    job.stackEntries = r->stackNeed;
-    job.refillMin = std::min(64, std::max(1, refillMin));
-    job.leafMin = std::min(64, std::max(1, leafMin));
-    // the whole arena beside the stacks of a 1024-thread workgroup?
-    const size_t bigLds = ((size_t)r->stackNeed*1024 + kSwalkCtlWords)*sizeof(uint32_t) + r->scene.arenaBytes;
-    const bool big = !noLds && bigLds <= (size_t)r->sharedMemLimit;
-    bool allInArena = true;
-    for (const DevMesh& dm : r->meshesNow)
-        allInArena = allInArena && dm.inArena;
-    a.swalkMode = big ? (allInArena ? 1 : 2) : 0;
-    const int block = big ? 1024 : kBlock;
-    const int gridMult = big ? 1 : 32;
     const size_t items = slots*(size_t)(shadowRays && r->neePerPath > 1 ? r->neePerPath : 1);
-    a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + block - 1)/block, (size_t)r->numCUs*(size_t)gridMult));
-    if (big)
-    {
-        a.scene.arenaLdsBytes = a.scene.arenaBytes;
-        a.ldsBytes = (uint32_t)bigLds;
-    }
-    else
-        a.ldsBytes = (uint32_t)(((size_t)r->stackNeed*kBlock + kSwalkCtlWords)*sizeof(uint32_t) + r->scene.arenaLdsBytes);
+    a.grid = (int)std::max<size_t>(1, std::min<size_t>((items + w.block - 1)/w.block, (size_t)r->numCUs*(size_t)w.perCU));
+    a.scene.arenaLdsBytes = w.arenaLds;
+    a.ldsBytes = w.ldsBytes;
+    a.variant = shadowRays ? w.shadow : w.extend;
     ScopedTimer t(r, shadowRays ? KN_SHADOW : KN_EXTEND, st);
-    launch_path(r, shadowRays ? PK_SWALK_SHADOW : PK_SWALK_EXTEND, a, st);
-    return 0;
+    return launch_path(r, a, st);
 }
 
 void launch_normals(tinsel_hip* r, hipStream_t st, int grid, const CameraParams& cam, const FrameParams& fp)
@@ -1002,8 +1045,9 @@ int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L
         return -1;
     ScopedTimer t(r, KN_GENERATE, st);
     a.grid = *grid;
-    launch_path(r, PK_GENERATE, a, st);
-    return 0;
+    a.variant = p.generate;
+    a.ldsBytes = 0;
+    return launch_path(r, a, st);
 }
 
 // region groups, longest first (k_region_order, tn_kernels.h), by the live entries of the regions' fronts and backs
@@ -1038,16 +1082,15 @@ int trace_fused(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     a.bounce = 0;
     a.bounceEnd = a.fp.maxDepth;
     a.order = nullptr;
+    a.variant = p.bounce;
     ScopedTimer t(r, KN_BOUNCE, st);
-    launch_path(r, PK_BOUNCE, a, st);
-    return 0;
+    return launch_path(r, a, st);
 }
 
 // the paired pipeline: ONE k_walk and ONE streaming kernel per bounce (tn_paired.h): walk { shadow rays of bounce b - 1, extension rays of bounce b }, then k_step(b)
 int trace_paired(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots)
 {
     int grid = 0;
-    a.walkedOnly = p.walkedLevel;
     if (cut_and_generate(r, p, L, st, a, slots, &grid))
         return -1;
     const size_t W = a.ss.numRegions;
@@ -1075,9 +1118,11 @@ int trace_paired(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
         }
         ScopedTimer t(r, KN_STEP, st);
         a.grid = grid;
+        a.variant = p.step;
         a.ldsBytes = p.ldsTrace;
         a.stackEntries = p.stackScan;
-        launch_path(r, PK_STEP, a, st);
+        if (launch_path(r, a, st))
+            return -1;
     }
     return 0;
 }
@@ -1086,9 +1131,6 @@ int trace_paired(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
 int trace_split(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, LaunchArgs& a, size_t slots)
 {
     int grid = 0;
-    const uint32_t arenaLdsTrace = r->scene.arenaLdsBytes;
-    a.walkedOnly = p.walkedLevel;
-    a.lightsInExtend = p.lightsInMixed ? 1 : 0;
     if (cut_and_generate(r, p, L, st, a, slots, &grid))
         return -1;
     const size_t W = a.ss.numRegions;
@@ -1111,29 +1153,33 @@ int trace_split(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
             return -1;
         if (p.sceneWalk)
         {
-            if (launch_swalk(r, L, st, a, slots, L.ss.segFront + (size_t)bounce*W, L.ss.segBack + (size_t)bounce*W, false))
+            if (launch_swalk(r, p, L, st, a, slots, L.ss.segFront + (size_t)bounce*W, L.ss.segBack + (size_t)bounce*W, false))
                 return -1;
         }
         else
         {
             ScopedTimer t(r, KN_EXTEND, st);
+            a.variant = p.extend;
             a.ldsBytes = p.ldsTrace;
             a.stackEntries = p.stackScan;
-            launch_path(r, PK_EXTEND, a, st);
+            if (launch_path(r, a, st))
+                return -1;
         }
         if (r->neePerPath > 0)
         {
-            if (!p.lightsInExtend)
+            if (p.lights != PK_NONE)
             {
                 ScopedTimer t(r, KN_LIGHTS, st);
+                a.variant = p.lights;
                 a.ldsBytes = p.ldsLights;
-                launch_path(r, PK_LIGHTS, a, st);
+                if (launch_path(r, a, st))
+                    return -1;
             }
             if (p.walk && launch_walk(r, p, L, st, a, slots, L.ss.neeFront + (size_t)bounce*W, true))
                 return -1;
             if (p.sceneWalk)
             {
-                if (launch_swalk(r, L, st, a, slots, L.ss.neeFront + (size_t)bounce*W, L.ss.neeBack + (size_t)bounce*W, true))
+                if (launch_swalk(r, p, L, st, a, slots, L.ss.neeFront + (size_t)bounce*W, L.ss.neeBack + (size_t)bounce*W, true))
                     return -1;
             }
             else
@@ -1144,20 +1190,23 @@ int trace_split(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
                     a.order = L.regionOrderNee;
                 }
                 ScopedTimer t(r, KN_SHADOW, st);
+                a.variant = p.shadow;
                 a.ldsBytes = p.ldsTrace;
                 a.stackEntries = p.stackScan;
-                launch_path(r, PK_SHADOW, a, st);
+                if (launch_path(r, a, st))
+                    return -1;
                 a.order = pathOrder;
             }
         }
         {
             ScopedTimer t(r, KN_SHADE, st);
-            a.shadeSorted = p.shadeSorted ? 1 : 0;
-            a.ldsBytes = p.ldsShade + (p.shadeSorted ? (uint32_t)(kShadeListWords*sizeof(uint32_t)) : 0u);
-            a.stackEntries = p.stackScan;
-            a.scene.arenaLdsBytes = p.arenaLdsShade;
-            launch_path(r, PK_SHADE, a, st);
-            a.scene.arenaLdsBytes = arenaLdsTrace;
+            LaunchArgs s = a;
+            s.variant = p.shade;
+            s.ldsBytes = p.ldsShade;
+            s.stackEntries = p.stackScan;
+            s.scene.arenaLdsBytes = p.arenaLdsShade;
+            if (launch_path(r, s, st))
+                return -1;
         }
     }
     return 0;
@@ -1211,13 +1260,14 @@ int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
     a.walkPrims = (uint32_t)r->walkPrims.count;
     a.bins = r->binPrims;
     a.stackEntries = r->stackNeed;
-    a.countDetail = r->countDetail ? 1 : 0;
     a.ldsBytes = (uint32_t)stack_bytes(r);
     if (p.pipeline == TINSEL_PIPELINE_MEGAKERNEL)
     {
         ScopedTimer t(r, KN_MEGA, st);
         a.grid = (int)std::max<size_t>(1, (slots + kBlock - 1)/kBlock);
-        launch_path(r, PK_MEGA, a, st);
+        a.variant = p.mega;
+        if (launch_path(r, a, st))
+            return -1;
     }
     else
     {
@@ -1497,12 +1547,13 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
         a.fp = fp;
         a.passSeeds = dev.seeds;
         a.stackEntries = r->stackNeed;
-        a.countDetail = 1;
         a.ldsBytes = (uint32_t)stack_bytes(r);
         a.cost = dev.cost;
         a.grid = (int)((slots + kBlock - 1)/kBlock);
+        a.variant = residency(r->scene, r->scene.arenaLdsBytes) == RES_LDS ? PK_COST_LDS : PK_COST;
         ScopedTimer t(r, KN_COST, st);
-        launch_path(r, PK_COST, a, st);
+        if (launch_path(r, a, st))
+            return -1;
         HIP_TRY(hipGetLastError());
     }
 

@@ -7,24 +7,88 @@
 //                                          the opt-in tolerance arm (tinsel_hip_set_arithmetic), like the reference's
 //                                          own `-O3 -ffast-math` / `-use_fast_math` builds (makefile:4, tinsel.vcxproj:134).
 // Both include this header (the second one with `tn` renamed), so the two arms differ in arithmetic only: same kernels,
-// same queues, same launch geometry.  The host fills a LaunchArgs per launch and hands it to launch_path_kernel of the
-// arm in force.
+// same queues, same launch geometry.  The host plans the instance of every launch (plan_batch), fills a LaunchArgs per launch
+// and hands it to launch_path_kernel of the arm in force, which launches entry `variant` of the list below.
 #pragma once
 
 #include "tn_kernels.h"
 
 namespace tn {
 
+// Every path-kernel instance the host launches: id, workgroup, 1 where create raises its dynamic-LDS limit, arguments, instance (in code-object
+// order).  COUNT: detail counters; LDS: the whole scene in LDS; MIXED: the arena staged, meshes in HBM; W1 / W2: walked_only_level.
+#define TN_PATH_KERNELS(X)                                                                                          \
+    X(PK_GENERATE,              kBlock, 0, GENERATE, k_generate)                                                    \
+    X(PK_EXTEND_W2_MIXED,       kBlock, 0, EXTEND,   k_extend<false, true, 2, true>)                                \
+    X(PK_EXTEND_W1_MIXED,       kBlock, 0, EXTEND,   k_extend<false, true, 1, true>)                                \
+    X(PK_EXTEND_W1,             kBlock, 0, EXTEND,   k_extend<false, false, 1>)                                     \
+    X(PK_EXTEND_MIXED_LIGHTS,   kBlock, 0, EXTEND,   k_extend<false, true, 0, true, true>)                          \
+    X(PK_EXTEND_MIXED,          kBlock, 0, EXTEND,   k_extend<false, true, 0, true>)                                \
+    X(PK_EXTEND_COUNT_LDS,      kBlock, 0, EXTEND,   k_extend<true, true>)                                          \
+    X(PK_EXTEND_COUNT,          kBlock, 0, EXTEND,   k_extend<true, false>)                                         \
+    X(PK_EXTEND_LDS,            kBlock, 0, EXTEND,   k_extend<false, true>)                                         \
+    X(PK_EXTEND,                kBlock, 0, EXTEND,   k_extend<false, false>)                                        \
+    X(PK_SHADOW_W2_MIXED,       kBlock, 0, SHADOW,   k_shadow<false, true, 2, true>)                                \
+    X(PK_SHADOW_W1_MIXED,       kBlock, 0, SHADOW,   k_shadow<false, true, 1, true>)                                \
+    X(PK_SHADOW_W1,             kBlock, 0, SHADOW,   k_shadow<false, false, 1>)                                     \
+    X(PK_SHADOW_MIXED,          kBlock, 0, SHADOW,   k_shadow<false, true, 0, true>)                                \
+    X(PK_SHADOW_COUNT_LDS,      kBlock, 0, SHADOW,   k_shadow<true, true>)                                          \
+    X(PK_SHADOW_COUNT,          kBlock, 0, SHADOW,   k_shadow<true, false>)                                         \
+    X(PK_SHADOW_LDS,            kBlock, 0, SHADOW,   k_shadow<false, true>)                                         \
+    X(PK_SHADOW,                kBlock, 0, SHADOW,   k_shadow<false, false>)                                        \
+    X(PK_MEGA_COUNT_LDS,        kBlock, 0, MEGA,     k_mega<true, true>)                                            \
+    X(PK_MEGA_COUNT,            kBlock, 0, MEGA,     k_mega<true, false>)                                           \
+    X(PK_MEGA_LDS,              kBlock, 0, MEGA,     k_mega<false, true>)                                           \
+    X(PK_MEGA,                  kBlock, 0, MEGA,     k_mega<false, false>)                                          \
+    X(PK_COST_LDS,              kBlock, 0, COST,     k_cost<true>)                                                  \
+    X(PK_COST,                  kBlock, 0, COST,     k_cost<false>)                                                 \
+    X(PK_LIGHTS_MIXED,          kBlock, 0, LIGHTS,   k_lights<true, true>)                                          \
+    X(PK_LIGHTS_LDS,            kBlock, 0, LIGHTS,   k_lights<true>)                                                \
+    X(PK_LIGHTS,                kBlock, 0, LIGHTS,   k_lights<false>)                                               \
+    X(PK_SHADE_SORTED_MIXED,    kBlock, 1, SHADE,    k_shade_sorted<true, true>)                                    \
+    X(PK_SHADE_SORTED_LDS,      kBlock, 1, SHADE,    k_shade_sorted<true>)                                          \
+    X(PK_SHADE_SORTED,          kBlock, 1, SHADE,    k_shade_sorted<false>)                                         \
+    X(PK_SHADE_MIXED,           kBlock, 0, SHADE,    k_shade<true, true>)                                           \
+    X(PK_SHADE_LDS,             kBlock, 0, SHADE,    k_shade<true>)                                                 \
+    X(PK_SHADE,                 kBlock, 0, SHADE,    k_shade<false>)                                                \
+    X(PK_BOUNCE_COUNT_LDS,      kBlock, 1, BOUNCE,   k_bounce<true, true, false>)                                   \
+    X(PK_BOUNCE_COUNT,          kBlock, 1, BOUNCE,   k_bounce<true, false, false>)                                  \
+    X(PK_BOUNCE_LDS_DEFER,      kBlock, 1, BOUNCE,   k_bounce<false, true, true>)                                   \
+    X(PK_BOUNCE_DEFER,          kBlock, 1, BOUNCE,   k_bounce<false, false, true>)                                  \
+    X(PK_BOUNCE_LDS,            kBlock, 1, BOUNCE,   k_bounce<false, true, false>)                                  \
+    X(PK_BOUNCE,                kBlock, 1, BOUNCE,   k_bounce<false, false, false>)                                 \
+    X(PK_STEP_W2_MIXED,         kBlock, 0, STEP,     k_step<true, 2, true>)                                         \
+    X(PK_STEP_W1_MIXED,         kBlock, 0, STEP,     k_step<true, 1, true>)                                         \
+    X(PK_STEP_W1,               kBlock, 0, STEP,     k_step<false, 1, false>)                                       \
+    X(PK_STEP_MIXED,            kBlock, 0, STEP,     k_step<true, 0, true>)                                         \
+    X(PK_STEP_LDS,              kBlock, 0, STEP,     k_step<true, 0, false>)                                        \
+    X(PK_STEP,                  kBlock, 0, STEP,     k_step<false, 0, false>)                                       \
+    X(PK_SWALK_SHADOW_LDS,      1024,   1, SWALK,    k_swalk<true, 1024, 1>)                                        \
+    X(PK_SWALK_SHADOW_MIXED,    1024,   1, SWALK,    k_swalk<true, 1024, 2>)                                        \
+    X(PK_SWALK_SHADOW,          kBlock, 1, SWALK,    k_swalk<true, 256, 0>)                                         \
+    X(PK_SWALK_EXTEND_LDS,      1024,   1, SWALK,    k_swalk<false, 1024, 1>)                                       \
+    X(PK_SWALK_EXTEND_MIXED,    1024,   1, SWALK,    k_swalk<false, 1024, 2>)                                       \
+    X(PK_SWALK_EXTEND,          kBlock, 1, SWALK,    k_swalk<false, 256, 0>)                                        \
+    X(PK_WALK_SINGLE_1024X2,    1024,   1, WALK,     k_walk<1024, 8, kWalkSingle>)                                  \
+    X(PK_WALK_SINGLE_1024,      1024,   1, WALK,     k_walk<1024, 4, kWalkSingle>)                                  \
+    X(PK_WALK_SINGLE_256,       256,    1, WALK,     k_walk<256, 5, kWalkSingle>)                                   \
+    X(PK_WALK_RAYS_1024X2,      1024,   1, WALK,     k_walk_rays<1024, 8>)                                          \
+    X(PK_WALK_RAYS_1024,        1024,   1, WALK,     k_walk_rays<1024, 4>)                                          \
+    X(PK_WALK_RAYS_256,         256,    1, WALK,     k_walk_rays<256, 5>)
+
 enum PathKernel : int
 {
-    PK_GENERATE = 0, PK_EXTEND, PK_SHADE, PK_SHADOW, PK_BOUNCE, PK_MEGA, PK_WALK, PK_LIGHTS, PK_SWALK_EXTEND, PK_SWALK_SHADOW, PK_STEP, PK_COST,
+    PK_NONE = 0,                    // not launched (and what a zeroed LaunchArgs names: no instance)
+#define TN_ID(ID, BLOCK, PREP, ARGS, ...) ID,
+    TN_PATH_KERNELS(TN_ID)
+#undef TN_ID
 };
 
 struct LaunchArgs
 {
-    DevScene scene;
+    DevScene scene;                 // (scene.arenaLdsBytes: the arena bytes the launched kernel stages)
     PathState ps;
-    SplitState ss;                  // the wavefront pipelines' dense state (PK_BOUNCE; PK_GENERATE .. PK_SHADE)
+    SplitState ss;                  // the wavefront pipelines' dense state
     QueueCtl ctl;
     CameraParams cam;
     FrameParams fp;
@@ -33,155 +97,45 @@ struct LaunchArgs
     uint32_t walkPrims;
     const uint32_t* order;          // region groups, longest first (k_region_order; null: in index order)
     BinPrims bins;                  // primitives whose leaf-box test sorts the queues
-    WalkJob walk;                   // PK_WALK
-    SwalkJob swalk;                 // PK_SWALK_*
-    int swalkMode;                  // PK_SWALK_*: 0 = 256-thread workgroups, generic pointers; 1 / 2 = 1024-thread workgroups, arena in LDS (2: meshes in HBM too)
-    int walkBig;                    // PK_WALK: 1 = 1024-thread workgroups with an LDS-resident tree top (2: two of them per CU, short LDS stacks), 0 = 256-thread ones
-    int walkSingle;                 // PK_WALK: ONE walked primitive: k_walk<.., kWalkSingle>; else k_walk_rays (tn_walk.h)
-    int shadeSorted;                // PK_SHADE: k_shade_sorted (paths taken class by class) instead of k_shade
-    int lightsInExtend;             // PK_EXTEND, arena staged + meshes in HBM: the variant that draws the light samples too (A/B)
-    int walkedOnly;                 // PK_EXTEND / PK_SHADOW / PK_STEP: every mesh of the scene is walked by k_walk (2: or is a quad tested in the scan) -> the lean scan variants
+    WalkJob walk;                   // k_walk
+    SwalkJob swalk;                 // k_swalk
+    int variant;                    // the instance launched (PathKernel)
     int bounce;
-    int bounceEnd;                  // PK_BOUNCE: the launch covers the bounces [bounce, bounceEnd)
+    int bounceEnd;                  // k_bounce: the launch covers the bounces [bounce, bounceEnd)
     int stackEntries;
-    int countDetail;                // detail counters on: the COUNT kernel variants
     int grid;
     uint32_t ldsBytes;              // dynamic LDS of the launch
-    uint32_t* cost;                 // PK_COST: the cost map's four planes (k_cost)
+    uint32_t* cost;                 // k_cost: the cost map's four planes
 };
 
-inline void launch_path_kernel(int which, const LaunchArgs& a, hipStream_t st)
+#define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
+#define TN_ARGS_EXTEND   a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order
+#define TN_ARGS_SHADOW   a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order
+#define TN_ARGS_MEGA     a.scene, a.ps, a.ctl, a.cam, a.fp, a.passSeeds, a.stackEntries
+#define TN_ARGS_COST     a.scene, a.cam, a.fp, a.passSeeds, a.stackEntries, a.cost
+#define TN_ARGS_LIGHTS   a.scene, a.ss, a.bounce, a.bins, a.order
+#define TN_ARGS_SHADE    a.scene, a.ss, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.bins, a.order
+#define TN_ARGS_BOUNCE   BounceKernargs{ a.scene, a.ss, a.ctl, a.bounce, a.bounceEnd, a.stackEntries, a.cam, a.fp, a.passSeeds }
+#define TN_ARGS_STEP     a.scene, a.ss, a.ctl, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order
+#define TN_ARGS_SWALK    a.scene, a.ss, a.ctl, a.bounce, a.swalk
+#define TN_ARGS_WALK     a.scene, a.walk
+
+// false: a.variant is not in the list (nothing is launched)
+inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)
 {
-    const dim3 grid((unsigned)a.grid), block(kBlock);
-    const bool lds = a.scene.allInArena != 0, count = a.countDetail != 0;
-    // the arena is staged whole but some meshes live in HBM: SceneT's MIXED mode (scene records at compile-time LDS addresses)
-    const bool mixed = !lds && !count && a.scene.arenaLdsBytes != 0 && a.scene.arenaLdsBytes == a.scene.arenaBytes;
-    switch (which)
+    switch (a.variant)
     {
-    case PK_GENERATE:
-        hipLaunchKernelGGL(k_generate, grid, block, 0, st, a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins);
-        break;
-    case PK_EXTEND:
-#define TN_LAUNCH2(KERNEL, ...)                                                                                        \
-        do {                                                                                                           \
-            if (count) { if (lds) hipLaunchKernelGGL((KERNEL<true, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<true, false>), __VA_ARGS__); } \
-            else       { if (lds) hipLaunchKernelGGL((KERNEL<false, true>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<false, false>), __VA_ARGS__); } \
-        } while (0)
-        if (a.walkedOnly == 2 && mixed)
-            hipLaunchKernelGGL((k_extend<false, true, 2, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        else if (a.walkedOnly && mixed)
-            hipLaunchKernelGGL((k_extend<false, true, 1, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        else if (a.walkedOnly && !count && !lds)
-            hipLaunchKernelGGL((k_extend<false, false, 1>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        else if (mixed && a.lightsInExtend)
-            hipLaunchKernelGGL((k_extend<false, true, 0, true, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        else if (mixed)
-            hipLaunchKernelGGL((k_extend<false, true, 0, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        else
-            TN_LAUNCH2(k_extend, grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order);
-        break;
-    case PK_SHADOW:
-        if (a.walkedOnly == 2 && mixed)
-            hipLaunchKernelGGL((k_shadow<false, true, 2, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order);
-        else if (a.walkedOnly && mixed)
-            hipLaunchKernelGGL((k_shadow<false, true, 1, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order);
-        else if (a.walkedOnly && !count && !lds)
-            hipLaunchKernelGGL((k_shadow<false, false, 1>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order);
-        else if (mixed)
-            hipLaunchKernelGGL((k_shadow<false, true, 0, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order);
-        else
-            TN_LAUNCH2(k_shadow, grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.stackEntries, a.walkRec, a.walkPrims, a.order);
-        break;
-    case PK_MEGA:
-        TN_LAUNCH2(k_mega, grid, block, a.ldsBytes, st, a.scene, a.ps, a.ctl, a.cam, a.fp, a.passSeeds, a.stackEntries);
-        break;
-    case PK_COST:
-        if (lds)
-            hipLaunchKernelGGL((k_cost<true>), grid, block, a.ldsBytes, st, a.scene, a.cam, a.fp, a.passSeeds, a.stackEntries, a.cost);
-        else
-            hipLaunchKernelGGL((k_cost<false>), grid, block, a.ldsBytes, st, a.scene, a.cam, a.fp, a.passSeeds, a.stackEntries, a.cost);
-        break;
-#undef TN_LAUNCH2
-    case PK_LIGHTS:
-        if (mixed)
-            hipLaunchKernelGGL((k_lights<true, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.bins, a.order);
-        else if (lds)
-            hipLaunchKernelGGL((k_lights<true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.bins, a.order);
-        else
-            hipLaunchKernelGGL((k_lights<false>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.bins, a.order);
-        break;
-    case PK_SHADE:
-#define TN_LAUNCH_SHADE(KERNEL)                                                                                        \
-        do {                                                                                                           \
-            if (mixed) hipLaunchKernelGGL((KERNEL<true, true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.bins, a.order); \
-            else if (lds) hipLaunchKernelGGL((KERNEL<true>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.bins, a.order); \
-            else hipLaunchKernelGGL((KERNEL<false>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.bins, a.order); \
-        } while (0)
-        if (a.shadeSorted) TN_LAUNCH_SHADE(k_shade_sorted); else TN_LAUNCH_SHADE(k_shade);
-#undef TN_LAUNCH_SHADE
-        break;
-    case PK_BOUNCE:
-#define TN_LAUNCH_BOUNCE(DEFER)                                                                                        \
-        do {                                                                                                           \
-            if (count) { if (lds) hipLaunchKernelGGL((k_bounce<true, true, false>), grid, block, a.ldsBytes, st, ka); \
-                         else hipLaunchKernelGGL((k_bounce<true, false, false>), grid, block, a.ldsBytes, st, ka); } \
-            else       { if (lds) hipLaunchKernelGGL((k_bounce<false, true, DEFER>), grid, block, a.ldsBytes, st, ka); \
-                         else hipLaunchKernelGGL((k_bounce<false, false, DEFER>), grid, block, a.ldsBytes, st, ka); } \
-        } while (0)
-        {
-            const BounceKernargs ka = { a.scene, a.ss, a.ctl, a.bounce, a.bounceEnd, a.stackEntries, a.cam, a.fp, a.passSeeds };
-            // (the detail-counting variants walk the scene BVH: nothing to defer)
-            if (a.scene.deferMeshes)
-                TN_LAUNCH_BOUNCE(true);
-            else
-                TN_LAUNCH_BOUNCE(false);
-        }
-#undef TN_LAUNCH_BOUNCE
-        break;
-    case PK_STEP:
-        // (LDS, WONLY, MIXED) as k_extend's variants: every mesh walked + arena staged / every mesh walked, generic pointers / arena staged, some
-        // meshes inline / whole scene in LDS / generic pointers
-#define TN_LAUNCH_STEP(L, W, M) hipLaunchKernelGGL((k_step<L, W, M>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order)
-        if (a.walkedOnly == 2 && mixed) TN_LAUNCH_STEP(true, 2, true);
-        else if (a.walkedOnly && mixed) TN_LAUNCH_STEP(true, 1, true);
-        else if (a.walkedOnly && !lds) TN_LAUNCH_STEP(false, 1, false);
-        else if (mixed) TN_LAUNCH_STEP(true, 0, true);
-        else if (lds) TN_LAUNCH_STEP(true, 0, false);
-        else TN_LAUNCH_STEP(false, 0, false);
-#undef TN_LAUNCH_STEP
-        break;
-    case PK_SWALK_EXTEND:
-    case PK_SWALK_SHADOW:
-#define TN_LAUNCH_SWALK(SH)                                                                                            \
-        do {                                                                                                           \
-            if (a.swalkMode == 1) hipLaunchKernelGGL((k_swalk<SH, 1024, 1>), grid, dim3(1024), a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.swalk); \
-            else if (a.swalkMode == 2) hipLaunchKernelGGL((k_swalk<SH, 1024, 2>), grid, dim3(1024), a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.swalk); \
-            else hipLaunchKernelGGL((k_swalk<SH, 256, 0>), grid, block, a.ldsBytes, st, a.scene, a.ss, a.ctl, a.bounce, a.swalk); \
-        } while (0)
-        if (which == PK_SWALK_SHADOW) TN_LAUNCH_SWALK(true); else TN_LAUNCH_SWALK(false);
-#undef TN_LAUNCH_SWALK
-        break;
-    case PK_WALK:
-        // ONE walked primitive: k_walk (its tree as kernel-argument scalars); several: k_walk_rays (a work item is a ray)
-#define TN_LAUNCH_WALK(KERNEL, ...)                                                                                    \
-        do {                                                                                                           \
-            if (a.walkBig == 2) hipLaunchKernelGGL((KERNEL<1024, 8 __VA_ARGS__>), grid, dim3(1024), a.ldsBytes, st, a.scene, a.walk); \
-            else if (a.walkBig) hipLaunchKernelGGL((KERNEL<1024, 4 __VA_ARGS__>), grid, dim3(1024), a.ldsBytes, st, a.scene, a.walk); \
-            else hipLaunchKernelGGL((KERNEL<256, 5 __VA_ARGS__>), grid, dim3(256), a.ldsBytes, st, a.scene, a.walk);      \
-        } while (0)
-#define TN_COMMA ,
-        if (a.walkSingle) TN_LAUNCH_WALK(k_walk, TN_COMMA kWalkSingle); else TN_LAUNCH_WALK(k_walk_rays, );
-#undef TN_COMMA
-#undef TN_LAUNCH_WALK
-        break;
+#define TN_LAUNCH(ID, BLOCK, PREP, ARGS, ...)                                                                          \
+    case ID: hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)a.grid), dim3(BLOCK), a.ldsBytes, st, TN_ARGS_##ARGS); return true;
+        TN_PATH_KERNELS(TN_LAUNCH)
+#undef TN_LAUNCH
     default:
-        break;
+        return false;
     }
 }
 
-// k_walk (tree tops), k_swalk, k_shade_sorted and k_bounce (shading pools beside a staged arena) ask for more dynamic LDS than the default
-// launch limit allows: every variant's limit is raised ONCE, at create, and every result is checked -- a device that grants less fails there
-// with the kernel's name instead of at some later launch with a generic error.
+// The entries marked 1 above (k_walk's tree tops, k_swalk, k_shade_sorted, k_bounce's pools beside a staged arena) ask for more dynamic LDS than
+// the default launch limit: raised ONCE, at create, every result checked -- a device that grants less fails there with the kernel's name.
 struct PrepReport
 {
     int refused = 0;                // attributes the runtime refused
@@ -203,7 +157,6 @@ inline void prep_lds(const void* kernel, const char* name, int bytes, PrepReport
 inline PrepReport prepare_path_kernels(int sharedMemLimit)
 {
     PrepReport rep;
-#define TN_PREP(...) prep_lds((const void*)__VA_ARGS__, #__VA_ARGS__, sharedMemLimit, rep)
     // (k_seg_prefix has static LDS too)
     {
         PrepReport seg;
@@ -211,13 +164,8 @@ inline PrepReport prepare_path_kernels(int sharedMemLimit)
         rep.segPrefixLds = seg.refused ? (sharedMemLimit < 65536 ? sharedMemLimit : 65536) - 1024 : sharedMemLimit - 1024;
         if (seg.refused) { rep.refused += 1; rep.first = rep.first ? rep.first : "k_seg_prefix"; }
     }
-    TN_PREP(k_walk_rays<1024, 4>); TN_PREP(k_walk_rays<1024, 8>); TN_PREP(k_walk_rays<256, 5>);
-    TN_PREP(k_walk<1024, 4, kWalkSingle>); TN_PREP(k_walk<1024, 8, kWalkSingle>); TN_PREP(k_walk<256, 5, kWalkSingle>);
-    TN_PREP(k_shade_sorted<true, true>); TN_PREP(k_shade_sorted<true>); TN_PREP(k_shade_sorted<false>);
-    TN_PREP(k_swalk<false, 1024, 1>); TN_PREP(k_swalk<false, 1024, 2>); TN_PREP(k_swalk<false, 256, 0>);
-    TN_PREP(k_swalk<true, 1024, 1>); TN_PREP(k_swalk<true, 1024, 2>); TN_PREP(k_swalk<true, 256, 0>);
-    TN_PREP(k_bounce<true, true, false>); TN_PREP(k_bounce<true, false, false>);
-    TN_PREP(k_bounce<false, true, false>); TN_PREP(k_bounce<false, false, false>); TN_PREP(k_bounce<false, true, true>); TN_PREP(k_bounce<false, false, true>);
+#define TN_PREP(ID, BLOCK, PREP, ARGS, ...) if (PREP) prep_lds((const void*)__VA_ARGS__, #__VA_ARGS__, sharedMemLimit, rep);
+    TN_PATH_KERNELS(TN_PREP)
 #undef TN_PREP
     return rep;
 }
