@@ -416,6 +416,30 @@ int tinsel_hip_set_detail_counters(tinsel_hip* r, int enable);
 int tinsel_hip_render_cost(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
                            uint32_t pass_begin, int passes, uint32_t* out_host);
 
+/* Ray queries on the resident scene: the reference's Trace() (render.cpp:17-62) for rays the caller chooses.
+ * TINSEL_QUERY_CLOSEST: the smallest t > 0 over the primitives the ray reaches (an exact tie: the one the scene BVH walk meets first),
+ * that primitive's index and its normal turned towards the ray, FaceForward(n, -direction); a miss is t = FLT_MAX, primitive = -1,
+ * normal (0, 0, 0); tmax is ignored.  TINSEL_QUERY_OCCLUDED: 1 iff some primitive gives 0 < t < tmax (strict; tmax = +inf: any hit;
+ * NaN or non-positive: never).  `time` is the pose of moving primitives, as a path's shutter time; `direction` is used as given.
+ * The scene is the one in force (rebuild_scene, refit_mesh, set_mesh_bvh, set_arithmetic).  A query leaves the accumulator, pass index,
+ * statistics, tuning, look-ahead and shard as they were, needs no tinsel_hip_init and ignores the shard; kernel "k_query" in
+ * tinsel_hip_kernel_times (with kernel timing on, a query starts a new record like a render call does: the spans of the call before it
+ * are dropped).  Bad arguments return -1 and launch nothing.  The host entries keep their staging buffers until tinsel_hip_destroy:
+ * at most 64 MB for tinsel_hip_trace_rays, width*height*32 bytes up to 128 MB for tinsel_hip_trace_camera (larger frames go in several launches). */
+typedef struct tinsel_ray     { float ox, oy, oz, time;  float dx, dy, dz, tmax; } tinsel_ray;
+typedef struct tinsel_ray_hit { float t; int32_t primitive; float nx, ny, nz; uint32_t reserved[3]; } tinsel_ray_hit;
+
+#define TINSEL_QUERY_CLOSEST  0   /* out: tinsel_ray_hit[n] */
+#define TINSEL_QUERY_OCCLUDED 1   /* out: uint32_t[n], 1 or 0 */
+
+/* host arrays, any 0 <= n <= 2^31 - 1 (staged through device buffers the renderer keeps, in chunks); returns when `out_host` is written */
+int tinsel_hip_trace_rays(tinsel_hip* r, int mode, long long n, const tinsel_ray* rays_host, void* out_host);
+/* device arrays, 16-byte aligned, not overlapping; enqueued on `stream` (NULL: the default stream, where the renderer works), not waited for */
+int tinsel_hip_trace_rays_device(tinsel_hip* r, int mode, long long n, const tinsel_ray* rays_dev, void* out_dev, void* stream);
+/* TINSEL_QUERY_CLOSEST of GenerateRay(i, j) for every pixel of a width x height frame (raster x = i, y = j, no jitter: the rays of
+ * TINSEL_MODE_NORMALS), generated on the device; out_host[j*width + i] */
+int tinsel_hip_trace_camera(tinsel_hip* r, const tinsel_camera* camera, int width, int height, float time, tinsel_ray_hit* out_host);
+
 /* Allocates the per-batch path buffers a later render of `passes` passes at `max_depth` will need, so that the first
  * such call does not pay for hipMalloc (tinsel_hip_render* allocate on demand otherwise). */
 int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth);
@@ -603,6 +627,8 @@ static_assert(sizeof(tinsel_options) == 48, "Options");
 static_assert(offsetof(tinsel_options, max_depth) == 40, "Options.maxDepth");
 static_assert(sizeof(tinsel_pack_header) == 256, "pack header");
 static_assert(sizeof(tinsel_hip_tuning) == 120, "tuning");
+static_assert(sizeof(tinsel_ray) == 32, "ray");
+static_assert(sizeof(tinsel_ray_hit) == 32, "ray hit");
 #endif
 
 #endif /* TINSEL_HIP_H */

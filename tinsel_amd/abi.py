@@ -122,6 +122,24 @@ class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_float), ("busy_ms", C.c_float)]
 
 
+class Ray(C.Structure):
+    """tinsel_ray: origin, the time that poses moving primitives, direction (used as given), tmax (occlusion queries)"""
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("time", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("tmax", C.c_float)]
+
+
+class RayHit(C.Structure):
+    """tinsel_ray_hit: closest t > 0, its primitive (-1: a miss, t = FLT_MAX), the normal turned towards the ray"""
+    _fields_ = [("t", C.c_float), ("primitive", C.c_int32), ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
+# the same records as numpy dtypes: an (n, 8) float32 array viewed as RAY_DTYPE is a tinsel_ray[n]
+RAY_DTYPE = [("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("time", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("tmax", "<f4")]
+RAY_HIT_DTYPE = [("t", "<f4"), ("primitive", "<i4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("reserved", "<u4", (3,))]
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
+
+
 class KernelTimeV1(C.Structure):
     """tinsel_kernel_time as libraries built before round 4 wrote it (no busy_ms): renderer.HipRenderer.kernel_times"""
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_float)]
@@ -182,4 +200,5 @@ PIPELINE_WAVEFRONT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT_SPLIT, PIPELINE_AUTO
 assert C.sizeof(Transform) == 32 and C.sizeof(BVHNode) == 32 and C.sizeof(Camera) == 40 and C.sizeof(Node64) == 64
 assert C.sizeof(Material) == 128 and C.sizeof(MeshGeometry) == 64 and C.sizeof(Primitive) == 272
 assert C.sizeof(Filter) == 16 and C.sizeof(Options) == 48 and C.sizeof(PackHeader) == 256
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert Primitive.geo.offset == 72 and Primitive.material.offset == 136 and Primitive.light_samples.offset == 264

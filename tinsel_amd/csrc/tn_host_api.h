@@ -89,6 +89,74 @@ int tinsel_hip_render_cost(tinsel_hip* r, const tinsel_camera* camera, const tin
     return render_cost_impl(r, camera, options, pass_begin, passes, out_host);
 }
 
+// Ray queries (tn_query.h, tn_host_query.h).  Nothing of the renderer's state is written and look-ahead work in flight is left alone: a query
+// only reads the scene, like the kernels that may be running beside it.
+static int query_args(tinsel_hip* r, int mode, long long n, const void* rays, const void* out, const char* who)
+{
+    if (!r || !rays || !out || n < 0 || n > 0x7fffffffll || (mode != TINSEL_QUERY_CLOSEST && mode != TINSEL_QUERY_OCCLUDED))
+        return fail(std::string(who) + ": bad arguments (a renderer, TINSEL_QUERY_CLOSEST or TINSEL_QUERY_OCCLUDED, 0 <= n < 2^31, two arrays)");
+    return 0;
+}
+
+int tinsel_hip_trace_rays_device(tinsel_hip* r, int mode, long long n, const tinsel_ray* rays_dev, void* out_dev, void* stream)
+{
+    if (query_args(r, mode, n, rays_dev, out_dev, "trace_rays_device"))
+        return -1;
+    const uintptr_t a = (uintptr_t)rays_dev, b = (uintptr_t)out_dev;
+    const uintptr_t aBytes = (uintptr_t)n*sizeof(tinsel_ray), bBytes = (uintptr_t)n*(mode == TINSEL_QUERY_CLOSEST ? sizeof(tinsel_ray_hit) : sizeof(uint32_t));
+    if ((a & 15u) || (b & 15u))
+        return fail("trace_rays_device: the arrays must be 16-byte aligned");
+    if (a < b + bBytes && b < a + aBytes)
+        return fail("trace_rays_device: the arrays overlap");
+    if (query_ready(r, "trace_rays_device"))
+        return -1;
+    if (n == 0)
+        return 0;
+    return launch_query(r, mode, (size_t)n, rays_dev, out_dev, nullptr, 0, 0.0f, (hipStream_t)stream);
+}
+
+int tinsel_hip_trace_rays(tinsel_hip* r, int mode, long long n, const tinsel_ray* rays_host, void* out_host)
+{
+    if (query_args(r, mode, n, rays_host, out_host, "trace_rays") || query_ready(r, "trace_rays"))
+        return -1;
+    const size_t outStride = mode == TINSEL_QUERY_CLOSEST ? sizeof(tinsel_ray_hit) : sizeof(uint32_t);
+    const size_t chunk = std::min<size_t>((size_t)n, kQueryChunk);
+    if (chunk == 0)
+        return 0;
+    if (query_buffer(r->queryRaysDev, r->queryRaysCap, chunk*sizeof(tinsel_ray)) || query_buffer(r->queryOutDev, r->queryOutCap, chunk*outStride))
+        return -1;
+    for (size_t done = 0; done < (size_t)n; done += chunk)
+    {
+        const size_t m = std::min(chunk, (size_t)n - done);
+        HIP_TRY(hipMemcpy(r->queryRaysDev, rays_host + done, m*sizeof(tinsel_ray), hipMemcpyHostToDevice));
+        if (launch_query(r, mode, m, r->queryRaysDev, r->queryOutDev, nullptr, 0, 0.0f, nullptr))
+            return -1;
+        HIP_TRY(hipMemcpy((unsigned char*)out_host + done*outStride, r->queryOutDev, m*outStride, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int tinsel_hip_trace_camera(tinsel_hip* r, const tinsel_camera* camera, int width, int height, float time, tinsel_ray_hit* out_host)
+{
+    if (!r || !camera || !out_host || width <= 0 || height <= 0 || (long long)width*height > 0x7fffffffll)
+        return fail("trace_camera: bad arguments (a renderer, a camera, a positive frame size, an array of width*height records)");
+    if (query_ready(r, "trace_camera"))
+        return -1;
+    const size_t n = (size_t)width*height, chunk = std::min(n, kQueryCameraChunk);
+    if (query_buffer(r->queryOutDev, r->queryOutCap, chunk*sizeof(tinsel_ray_hit)))
+        return -1;
+    CameraParams cam;
+    make_camera(*camera, width, height, cam);
+    for (size_t done = 0; done < n; done += chunk)
+    {
+        const size_t m = std::min(chunk, n - done);
+        if (launch_query(r, kQueryCamera, m, nullptr, r->queryOutDev, &cam, width, time, nullptr, (uint32_t)done))
+            return -1;
+        HIP_TRY(hipMemcpy(out_host + done, r->queryOutDev, m*sizeof(tinsel_ray_hit), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

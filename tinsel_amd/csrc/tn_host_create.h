@@ -547,6 +547,11 @@ void tinsel_hip_destroy(tinsel_hip* r)
     if (r->passSeedsDev) (void)hipFree(r->passSeedsDev);
     if (r->passSeedsReady) (void)hipEventDestroy(r->passSeedsReady);
     if (r->statsDev) (void)hipFree(r->statsDev);
+    if (r->queryRaysDev) (void)hipFree(r->queryRaysDev);
+    if (r->queryOutDev) (void)hipFree(r->queryOutDev);
+    if (r->queryCursorDev) (void)hipFree(r->queryCursorDev);
+    for (hipEvent_t e : r->queryCursorDone)
+        if (e) (void)hipEventDestroy(e);
     for (TimedSpan& s : r->spans)
     {
         (void)hipEventDestroy(s.start);

@@ -323,8 +323,8 @@ struct DeviceArena
 };
 
 const char* kKernelNames[] = { "k_generate", "k_extend", "k_shade", "k_shadow", "k_accumulate", "k_mega", "k_normals", "k_bounce",
-                               "k_present", "k_nlm_means", "k_nlm", "k_walk", "k_lights", "k_seg", "k_step", "k_cost" };
-enum { KN_GENERATE = 0, KN_EXTEND, KN_SHADE, KN_SHADOW, KN_ACCUMULATE, KN_MEGA, KN_NORMALS, KN_BOUNCE, KN_PRESENT, KN_NLM_MEANS, KN_NLM, KN_WALK, KN_LIGHTS, KN_SEG, KN_STEP, KN_COST, KN_COUNT };
+                               "k_present", "k_nlm_means", "k_nlm", "k_walk", "k_lights", "k_seg", "k_step", "k_cost", "k_query" };
+enum { KN_GENERATE = 0, KN_EXTEND, KN_SHADE, KN_SHADOW, KN_ACCUMULATE, KN_MEGA, KN_NORMALS, KN_BOUNCE, KN_PRESENT, KN_NLM_MEANS, KN_NLM, KN_WALK, KN_LIGHTS, KN_SEG, KN_STEP, KN_COST, KN_QUERY, KN_COUNT };
 
 struct TimedSpan { int kernel; hipEvent_t start, stop; };
 

@@ -1,0 +1,131 @@
+// tn_host_query.h -- ray queries on the resident scene: the plan of k_query's launch, the launch, the host entries' staging buffers
+// (part of the library's one host translation unit: included by tinsel_hip.hip, in this order, never on its own)
+#pragma once
+
+namespace {
+
+// rays per chunk of the host entry: 32 MB of rays + 32 MB of records on the device, whatever n is
+constexpr size_t kQueryChunk = (size_t)1 << 20;
+
+// rays per launch of tinsel_hip_trace_camera (a 128 MB record buffer the renderer keeps; a 1920 x 1080 frame is one launch)
+constexpr size_t kQueryCameraChunk = (size_t)1 << 22;
+
+// k_query's launch for one mode on the scene in force (tn_query.h): the instance by residency -- the whole scene staged (LDS), or generic
+// pointers over the bytes scene.arenaLdsBytes says with the other meshes in HBM, as k_normals / k_cost -- workgroups of kBlock, stacks at the
+// scene's planned depth, and the ARM, by what was measured on 2^22 incoherent rays (profiles/r07_ray_query.md):
+//   k_query          one ray per lane, trace<> as the path kernels run it: closest hits on flat-scan scenes (ajax_standin_96 0.383 ms against
+//                    0.423, glass 0.353 against 0.480: the wave-uniform scan beats a divergent walk over a handful of primitives), every
+//                    camera frame (coherent rays), occlusion where the whole scene sits in LDS;
+//   k_query_refill   persistent workgroups with ray replacement on the scene BVH walk: scenes beyond the flat scan (many_spheres closest
+//                    0.358 -> 0.245 ms, occluded 0.150 -> 0.133) and occlusion on flat-scan scenes with meshes in HBM (ajax_standin_96
+//                    0.348 -> 0.196 ms: the walk stops at the first hit below tmax, the scan runs every mesh walk to its end).
+struct QueryPlan
+{
+    int variant = PK_NONE;
+    int block = kBlock;
+    int stackEntries = 0;
+    uint32_t arenaLds = 0;          // arena bytes the kernel stages
+    uint32_t ldsBytes = 0;
+    int persistent = 0;             // > 0: k_query_refill, that many workgroups at most, each taking rays until none is left
+    int grid(size_t n) const
+    {
+        const size_t g = (n + (size_t)block - 1)/(size_t)block;
+        return (int)(persistent > 0 ? std::min<size_t>(g, (size_t)persistent) : g);
+    }
+};
+
+QueryPlan plan_query(const tinsel_hip* r, int mode)
+{
+    static const int kPlain[3][2] = { { PK_QUERY_CLOSEST, PK_QUERY_CLOSEST_LDS }, { PK_QUERY_OCCLUDED, PK_QUERY_OCCLUDED_LDS },
+                                      { PK_QUERY_CAMERA, PK_QUERY_CAMERA_LDS } };
+    static const int kRefill[2][2] = { { PK_QUERYR_CLOSEST, PK_QUERYR_CLOSEST_LDS }, { PK_QUERYR_OCCLUDED, PK_QUERYR_OCCLUDED_LDS } };
+    const int lds = residency(r->scene, r->scene.arenaLdsBytes) == RES_LDS ? 1 : 0;
+    const bool refill = mode != kQueryCamera && (r->scene.flatScan == 0 || (mode == kQueryOccluded && !lds));
+    QueryPlan p;
+    p.variant = refill ? kRefill[mode][lds] : kPlain[mode][lds];
+    p.stackEntries = r->stackNeed;
+    p.arenaLds = r->scene.arenaLdsBytes;
+    p.ldsBytes = (uint32_t)stack_bytes(r);
+    p.persistent = refill ? r->numCUs*TN_WAVES_TRACE : 0;       // (a workgroup is one wave per SIMD: TN_WAVES_TRACE of them fill a CU)
+    return p;
+}
+
+// enqueues k_query over n rays (device pointers) on st; mode: QueryMode
+int launch_query(tinsel_hip* r, int mode, size_t n, const void* rays, void* out, const CameraParams* cam, int width, float time, hipStream_t st,
+                 uint32_t first = 0)
+{
+    const QueryPlan plan = plan_query(r, mode);
+    LaunchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene = r->scene;
+    a.scene.arenaLdsBytes = plan.arenaLds;
+    if (cam)
+        a.cam = *cam;
+    a.query.rays = rays;
+    a.query.out = out;
+    a.query.n = (uint32_t)n;
+    a.query.width = width;
+    a.query.time = time;
+    a.query.first = first;
+    hipEvent_t* slotDone = nullptr;
+    if (plan.persistent > 0)
+    {
+        // A cursor word of this launch's own, out of a ring: queries on different streams may run side by side (the device entry does not
+        // wait), so they cannot share one.  The word is zeroed on THIS stream in front of the kernel; before a slot is used again, this
+        // stream waits for the launch that had it last.
+        if (!r->queryCursorDev)
+        {
+            HIP_TRY(hipMalloc((void**)&r->queryCursorDev, sizeof(uint32_t)*tinsel_hip::kQueryCursors));
+            for (hipEvent_t& e : r->queryCursorDone)
+                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        const uint32_t slot = r->queryCursorNext++ % tinsel_hip::kQueryCursors;
+        slotDone = &r->queryCursorDone[slot];
+        if (r->queryCursorUsed[slot])
+            HIP_TRY(hipStreamWaitEvent(st, *slotDone, 0));
+        r->queryCursorUsed[slot] = true;
+        HIP_TRY(hipMemsetAsync(r->queryCursorDev + slot, 0, sizeof(uint32_t), st));
+        a.query.cursor = r->queryCursorDev + slot;
+    }
+    a.stackEntries = plan.stackEntries;
+    a.ldsBytes = plan.ldsBytes;
+    a.grid = plan.grid(n);
+    a.variant = plan.variant;
+    {
+        ScopedTimer t(r, KN_QUERY, st);
+        if (launch_path(r, a, st))
+            return -1;
+    }
+    HIP_TRY(hipGetLastError());
+    if (slotDone)
+        HIP_TRY(hipEventRecord(*slotDone, st));
+    return 0;
+}
+
+int query_ready(tinsel_hip* r, const char* who)
+{
+    if (r->sceneDirty)
+        return fail(std::string(who) + ": a primitive was moved (tinsel_hip_set_primitive_transform): call tinsel_hip_rebuild_scene first");
+    HIP_TRY(hipSetDevice(r->device));
+    if (r->timing)
+        release_spans(r);           // (as a render call: tinsel_hip_kernel_times reports the most recent call's kernels)
+    return 0;
+}
+
+int query_buffer(void*& buf, size_t& cap, size_t bytes)
+{
+    if (cap >= bytes)
+        return 0;
+    if (buf)
+    {
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(buf);
+    }
+    buf = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(&buf, bytes));
+    cap = bytes;
+    return 0;
+}
+
+} // namespace

@@ -134,6 +134,16 @@ struct tinsel_hip
     hipEvent_t passSeedsReady = nullptr;    // recorded behind the launch that wrote the table, on passSeedsStream
     hipStream_t passSeedsStream = nullptr;
     unsigned long long* statsDev = nullptr;
+    // ray queries (tinsel_hip_trace_rays / tinsel_hip_trace_camera): the host entries' chunk buffers, grown on demand, freed with the renderer
+    void* queryRaysDev = nullptr;
+    void* queryOutDev = nullptr;
+    size_t queryRaysCap = 0, queryOutCap = 0;   // bytes
+    // k_query_refill's cursors: a ring of words, one per launch, and per word the event behind the launch that used it last (launch_query)
+    static constexpr uint32_t kQueryCursors = 64;
+    uint32_t* queryCursorDev = nullptr;
+    hipEvent_t queryCursorDone[kQueryCursors] = {};
+    bool queryCursorUsed[kQueryCursors] = {};
+    uint32_t queryCursorNext = 0;
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)

@@ -74,7 +74,17 @@ namespace tn {
     X(PK_WALK_SINGLE_256,       256,    1, WALK,     k_walk<256, 5, kWalkSingle>)                                   \
     X(PK_WALK_RAYS_1024X2,      1024,   1, WALK,     k_walk_rays<1024, 8>)                                          \
     X(PK_WALK_RAYS_1024,        1024,   1, WALK,     k_walk_rays<1024, 4>)                                          \
-    X(PK_WALK_RAYS_256,         256,    1, WALK,     k_walk_rays<256, 5>)
+    X(PK_WALK_RAYS_256,         256,    1, WALK,     k_walk_rays<256, 5>)                                           \
+    X(PK_QUERY_CLOSEST_LDS,     kBlock, 0, QUERY,    k_query<kQueryClosest, true>)                                  \
+    X(PK_QUERY_CLOSEST,         kBlock, 0, QUERY,    k_query<kQueryClosest, false>)                                 \
+    X(PK_QUERY_OCCLUDED_LDS,    kBlock, 0, QUERY,    k_query<kQueryOccluded, true>)                                 \
+    X(PK_QUERY_OCCLUDED,        kBlock, 0, QUERY,    k_query<kQueryOccluded, false>)                                \
+    X(PK_QUERY_CAMERA_LDS,      kBlock, 0, QUERY,    k_query<kQueryCamera, true>)                                   \
+    X(PK_QUERY_CAMERA,          kBlock, 0, QUERY,    k_query<kQueryCamera, false>)                                  \
+    X(PK_QUERYR_CLOSEST_LDS,    kBlock, 0, QUERY,    k_query_refill<kQueryClosest, true>)                           \
+    X(PK_QUERYR_CLOSEST,        kBlock, 0, QUERY,    k_query_refill<kQueryClosest, false>)                          \
+    X(PK_QUERYR_OCCLUDED_LDS,   kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, true>)                          \
+    X(PK_QUERYR_OCCLUDED,       kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, false>)
 
 enum PathKernel : int
 {
@@ -106,6 +116,7 @@ struct LaunchArgs
     int grid;
     uint32_t ldsBytes;              // dynamic LDS of the launch
     uint32_t* cost;                 // k_cost: the cost map's four planes
+    QueryJob query;                 // k_query
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -119,6 +130,7 @@ struct LaunchArgs
 #define TN_ARGS_STEP     a.scene, a.ss, a.ctl, a.bounce, a.fp.maxDepth, a.fp.rrStart, a.stackEntries, a.walkRec, a.walkPrims, a.bins, a.order
 #define TN_ARGS_SWALK    a.scene, a.ss, a.ctl, a.bounce, a.swalk
 #define TN_ARGS_WALK     a.scene, a.walk
+#define TN_ARGS_QUERY    a.scene, a.query, a.cam, a.stackEntries
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

@@ -2,7 +2,7 @@
 
     python -m tinsel_amd.headless [-spp=N] [-width=W] [-height=H] [-exposure=E] [-maxdepth=D]
                                   [-nlm=RADIUS[,FALLOFF]] [-rr=BOUNCE] [-out=image.png|image.pfm] [-save=state.npz] [-resume=state.npz]
-                                  [-complexity=rays|nodes|tris|prims]
+                                  [-complexity=rays|nodes|tris|prims] [-firsthit=buffers.npz]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -28,6 +28,9 @@ Beyond it: `.pfm` output of the normalised linear image (PfmSave layout), and -s
 renderer of the reference draws it): the traversal-cost map of maxSamples path-traced passes (HipRenderer.render_cost) instead of
 the image.  -out gets the heat map of CHANNEL's mean per sample (display.cost_heatmap) as a PNG, or those raw means as a PFM; the
 frame's mean per sample of all four channels is printed.
+-firsthit=FILE.npz writes the first-hit buffers of the scene's camera at the frame size (HipRenderer.first_hit: `t` [H, W], `primitive`
+[H, W], -1 where the ray leaves the scene, `normal` [H, W, 3] turned towards the camera; the pose of time 1, as the normals view) and
+exits without rendering: what a denoiser or a compositor reads beside the image.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -47,7 +50,7 @@ FRAME_PASSES = 16          # numSamples of main.cpp:240
 def parse_args(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
-    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "over": {}}
+    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "over": {}}
     for a in argv[1:-1]:
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
@@ -61,7 +64,7 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume"):
+        elif k in ("out", "save", "resume", "firsthit"):
             cfg[k] = v
         elif k == "complexity":
             if v not in COST_CHANNELS:
@@ -167,6 +170,8 @@ def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
     if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
         raise SystemExit("-complexity renders one cost map: no batch mode, -save or -resume")
+    if cfg["firsthit"] and ("%" in cfg["file"] or cfg["complexity"]):
+        raise SystemExit("-firsthit writes one frame's buffers: no batch mode, no -complexity")
     if "%" in cfg["file"]:
         return batch(cfg)
     t0 = time.perf_counter()
@@ -175,6 +180,12 @@ def main(argv=None):
     over = cfg["over"]
 
     r = create_gpu_renderer(scene)
+    if cfg["firsthit"]:
+        t, primitive, normal = r.first_hit(cam, opt.width, opt.height)
+        r.close()
+        np.savez(cfg["firsthit"], t=t, primitive=primitive, normal=normal)
+        print("wrote %s: %dx%d, %d pixels hit" % (cfg["firsthit"], opt.width, opt.height, int((primitive >= 0).sum())))
+        return 0
     if over.get("rr", 0) > 0:
         r.set_russian_roulette(over["rr"])       # opt-in; not the reference's behaviour (tinsel_hip.h)
     r.init(opt.width, opt.height)

@@ -87,6 +87,9 @@ def load_library():
     L.tinsel_hip_stats_detail.argtypes = [vp, vp]
     L.tinsel_hip_set_detail_counters.argtypes = [vp, ci]
     L.tinsel_hip_render_cost.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, vp]
+    L.tinsel_hip_trace_rays.argtypes = [vp, ci, C.c_longlong, vp, vp]
+    L.tinsel_hip_trace_rays_device.argtypes = [vp, ci, C.c_longlong, vp, vp, vp]
+    L.tinsel_hip_trace_camera.argtypes = [vp, C.POINTER(abi.Camera), ci, ci, cf, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -155,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_selftest_arith", "tinsel_hip_selftest_sort", "tinsel_hip_selftest_scan", "tinsel_hip_plan_regions",
     "tinsel_hip_tuning_init", "tinsel_hip_create_tuned", "tinsel_hip_set_tuning", "tinsel_hip_get_tuning", "tinsel_hip_group_create_tuned",
     "tinsel_hip_comm_unique_id", "tinsel_hip_comm_init", "tinsel_hip_comm_size", "tinsel_hip_comm_reduce_accum",
+    "tinsel_hip_trace_rays", "tinsel_hip_trace_rays_device", "tinsel_hip_trace_camera",
 ]
 
 
@@ -463,6 +467,54 @@ class HipRenderer:
         _check(self._L.tinsel_hip_render_cost(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes),
                                               out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_cost")
         return out
+
+    def trace_rays(self, rays, mode="closest"):
+        """Ray queries on the resident scene (tinsel_hip_trace_rays*): `rays` is an (n, 8) float32 array of
+        (origin xyz, time, direction xyz, tmax) -- a numpy array (host entry; returns numpy) or a contiguous torch tensor on this
+        renderer's device (device entry on torch's current stream, not waited for; returns a torch tensor).
+        mode "closest": a record array of abi.RAY_HIT_DTYPE (t, primitive, nx, ny, nz; a miss: FLT_MAX, -1, 0) -- from torch an
+        (n, 8) float32 tensor holding the same 32-byte records; "occluded": uint32 (torch: int32) 1 / 0 for `0 < t < tmax`.
+        Leaves the accumulator, pass index, statistics and tuning as they were; needs no init()."""
+        modes = {"closest": abi.QUERY_CLOSEST, "occluded": abi.QUERY_OCCLUDED, abi.QUERY_CLOSEST: abi.QUERY_CLOSEST, abi.QUERY_OCCLUDED: abi.QUERY_OCCLUDED}
+        if mode not in modes:
+            raise ValueError("trace_rays: mode is 'closest' or 'occluded'")
+        m = modes[mode]
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "data_ptr"):
+            import torch
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+                raise ValueError("trace_rays: a contiguous (n, 8) float32 tensor on the GPU is expected")
+            if rays.device.index != self.device:
+                raise ValueError("trace_rays: the tensor is on %s, the renderer on device %d" % (rays.device, self.device))
+            n = int(rays.shape[0])
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device) if m == abi.QUERY_CLOSEST else \
+                torch.empty((n,), dtype=torch.int32, device=rays.device)
+            if n:
+                stream = torch.cuda.current_stream(rays.device).cuda_stream
+                _check(self._L.tinsel_hip_trace_rays_device(self._h, m, n, rays.data_ptr(), out.data_ptr(), stream), "tinsel_hip_trace_rays_device")
+            return out
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("trace_rays: an (n, 8) float32 array is expected")
+        n = rays.shape[0]
+        out = np.zeros(n, abi.RAY_HIT_DTYPE) if m == abi.QUERY_CLOSEST else np.zeros(n, np.uint32)
+        # (an empty array's data pointer may be null: hand the library addresses it can check)
+        keep_r, keep_o = (rays, out) if n else (np.zeros((1, 8), np.float32), np.zeros(1, out.dtype))
+        _check(self._L.tinsel_hip_trace_rays(self._h, m, n, keep_r.ctypes.data_as(C.c_void_p), keep_o.ctypes.data_as(C.c_void_p)), "tinsel_hip_trace_rays")
+        return out
+
+    def trace_camera(self, camera, width, height, time=1.0):
+        """tinsel_hip_trace_camera: the closest hit of GenerateRay(i, j) of every pixel (no jitter), an [H, W] record array of abi.RAY_HIT_DTYPE"""
+        out = np.zeros((int(height), int(width)), abi.RAY_HIT_DTYPE)
+        _check(self._L.tinsel_hip_trace_camera(self._h, C.byref(camera), int(width), int(height), float(time), out.ctypes.data_as(C.c_void_p)),
+               "tinsel_hip_trace_camera")
+        return out
+
+    def first_hit(self, camera, width, height, time=1.0):
+        """The first-hit buffers of a frame: (t [H, W] float32 -- FLT_MAX at a miss, primitive [H, W] int32 -- -1 at a miss,
+        normal [H, W, 3] float32 turned towards the camera -- 0 at a miss), from trace_camera."""
+        rec = self.trace_camera(camera, width, height, time)
+        normal = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1)
+        return np.ascontiguousarray(rec["t"]), np.ascontiguousarray(rec["primitive"]), normal
 
     def enable_kernel_timing(self, on):
         _check(self._L.tinsel_hip_enable_kernel_timing(self._h, int(on)), "tinsel_hip_enable_kernel_timing")
