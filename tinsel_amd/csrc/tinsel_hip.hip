@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -62,6 +63,7 @@ int fail(const std::string& msg)
 } // namespace
 
 // The host side by concern, one translation unit (the kernels and everything above are shared):
+#include "tn_host_own.h"          // DevBuf, DevPool, Stream, Event, PinnedOutput: the only file that allocates or frees
 #include "tn_host_layout.h"       // BVH re-layout, arena
 #include "tn_host_state.h"        // struct tinsel_hip
 #include "tn_host_batch.h"        // launches, grids and regions, render_batch / render_impl

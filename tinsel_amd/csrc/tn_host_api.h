@@ -12,11 +12,10 @@ int tinsel_hip_init(tinsel_hip* r, int width, int height)
         return fail("init: bad arguments");
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipDeviceSynchronize());
-    if (r->accum && r->accumOwned)
-        (void)hipFree(r->accum);
     r->accum = nullptr;
-    r->accumOwned = true;
-    HIP_TRY(hipMalloc((void**)&r->accum, sizeof(float4)*(size_t)width*height));
+    if (r->accumOwn.alloc((size_t)width*height))
+        return -1;
+    r->accum = r->accumOwn.get();
     HIP_TRY(hipMemset(r->accum, 0, sizeof(float4)*(size_t)width*height));
     HIP_TRY(hipStreamSynchronize(nullptr));     // before anything is accumulated on another (non-blocking) stream: see ensure_batch
     r->width = width;
@@ -32,10 +31,8 @@ int tinsel_hip_init_external(tinsel_hip* r, int width, int height, float* device
         return fail("init_external: bad arguments");
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipDeviceSynchronize());
-    if (r->accum && r->accumOwned)
-        (void)hipFree(r->accum);
-    r->accum = (float4*)device_accum;
-    r->accumOwned = false;
+    r->accumOwn.reset();
+    r->accum = (float4*)device_accum;       // the caller's: a view, never freed here
     HIP_TRY(hipMemset(r->accum, 0, sizeof(float4)*(size_t)width*height));
     HIP_TRY(hipStreamSynchronize(nullptr));
     r->width = width;
@@ -55,14 +52,10 @@ int tinsel_hip_set_lookahead(tinsel_hip* r, int enable)
         return fail("set_lookahead: null");
     if (!enable)
         lookahead_cancel(r);
-    if (enable != TINSEL_LOOKAHEAD_PIN_OUTPUT && r->pinnedPtr)
+    if (enable != TINSEL_LOOKAHEAD_PIN_OUTPUT && r->pinned.held())
     {
         (void)hipSetDevice(r->device);
-        if (r->copyStream)
-            (void)hipStreamSynchronize(r->copyStream);
-        (void)hipHostUnregister(r->pinnedPtr);
-        r->pinnedPtr = nullptr;
-        r->pinnedBytes = 0;
+        r->pinned.release(r->copyStream);
     }
     r->lookahead = enable == TINSEL_LOOKAHEAD_PIN_OUTPUT ? TINSEL_LOOKAHEAD_PIN_OUTPUT : (enable ? TINSEL_LOOKAHEAD_ON : TINSEL_LOOKAHEAD_OFF);
     return 0;
@@ -70,7 +63,7 @@ int tinsel_hip_set_lookahead(tinsel_hip* r, int enable)
 
 int tinsel_hip_render(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, float* out_rgba, int passes)
 {
-    if (r && r->lookahead && out_rgba && camera && options && r->accum && r->accumOwned && passes >= 1 &&
+    if (r && r->lookahead && out_rgba && camera && options && r->accum && r->accumOwn && passes >= 1 &&
         options->width == r->width && options->height == r->height)
         return lookahead_render(r, camera, options, out_rgba, passes);
     lookahead_cancel(r);
@@ -123,15 +116,17 @@ int tinsel_hip_trace_rays(tinsel_hip* r, int mode, long long n, const tinsel_ray
     const size_t chunk = std::min<size_t>((size_t)n, kQueryChunk);
     if (chunk == 0)
         return 0;
-    if (query_buffer(r->queryRaysDev, r->queryRaysCap, chunk*sizeof(tinsel_ray)) || query_buffer(r->queryOutDev, r->queryOutCap, chunk*outStride))
+    if (query_buffer(r->queryRaysDev, chunk*sizeof(tinsel_ray)) || query_buffer(r->queryOutDev, chunk*outStride))
         return -1;
+    unsigned char* const raysDev = r->queryRaysDev.get();
+    unsigned char* const outDev = r->queryOutDev.get();
     for (size_t done = 0; done < (size_t)n; done += chunk)
     {
         const size_t m = std::min(chunk, (size_t)n - done);
-        HIP_TRY(hipMemcpy(r->queryRaysDev, rays_host + done, m*sizeof(tinsel_ray), hipMemcpyHostToDevice));
-        if (launch_query(r, mode, m, r->queryRaysDev, r->queryOutDev, nullptr, 0, 0.0f, nullptr))
+        HIP_TRY(hipMemcpy(raysDev, rays_host + done, m*sizeof(tinsel_ray), hipMemcpyHostToDevice));
+        if (launch_query(r, mode, m, raysDev, outDev, nullptr, 0, 0.0f, nullptr))
             return -1;
-        HIP_TRY(hipMemcpy((unsigned char*)out_host + done*outStride, r->queryOutDev, m*outStride, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy((unsigned char*)out_host + done*outStride, outDev, m*outStride, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -143,16 +138,16 @@ int tinsel_hip_trace_camera(tinsel_hip* r, const tinsel_camera* camera, int widt
     if (query_ready(r, "trace_camera"))
         return -1;
     const size_t n = (size_t)width*height, chunk = std::min(n, kQueryCameraChunk);
-    if (query_buffer(r->queryOutDev, r->queryOutCap, chunk*sizeof(tinsel_ray_hit)))
+    if (query_buffer(r->queryOutDev, chunk*sizeof(tinsel_ray_hit)))
         return -1;
     CameraParams cam;
     make_camera(*camera, width, height, cam);
     for (size_t done = 0; done < n; done += chunk)
     {
         const size_t m = std::min(chunk, n - done);
-        if (launch_query(r, kQueryCamera, m, nullptr, r->queryOutDev, &cam, width, time, nullptr, (uint32_t)done))
+        if (launch_query(r, kQueryCamera, m, nullptr, r->queryOutDev.get(), &cam, width, time, nullptr, (uint32_t)done))
             return -1;
-        HIP_TRY(hipMemcpy(out_host + done, r->queryOutDev, m*sizeof(tinsel_ray_hit), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_host + done, r->queryOutDev.get(), m*sizeof(tinsel_ray_hit), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -182,41 +177,37 @@ int tinsel_hip_present_async(tinsel_hip* r, const tinsel_options* options, int n
         r->presented = r->accum;        // main.cpp:258: the other modes present the raw pixels
         return 0;
     }
-    if (r->displayPixels != n)
+    if (r->display[0].count() != n)
     {
         HIP_TRY(hipDeviceSynchronize());
-        for (float4*& d : r->display)
-        {
-            if (d) (void)hipFree(d);
-            d = nullptr;
-        }
-        r->displayPixels = 0;
+        for (DevBuf<float4>& d : r->display)
+            d.reset();
     }
     const int needed = nlm_width ? 3 : 1;
     for (int i = 0; i < needed; ++i)
-        if (!r->display[i])
-            HIP_TRY(hipMalloc((void**)&r->display[i], sizeof(float4)*n));
-    r->displayPixels = n;
+        if (r->display[i].grow(n))
+            return -1;
+    float4* const display[3] = { r->display[0].get(), r->display[1].get(), r->display[2].get() };
 
     {
         ScopedTimer t(r, KN_PRESENT, st);
-        hipLaunchKernelGGL(k_present, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, r->accum, r->display[0], (int)n,
+        hipLaunchKernelGGL(k_present, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, r->accum, display[0], (int)n,
                            options->exposure, options->limit);
     }
-    r->presented = r->display[0];
+    r->presented = display[0];
     if (nlm_width)
     {
         const dim3 grid((r->width + 15)/16, (r->height + 15)/16);
         {
             ScopedTimer t(r, KN_NLM_MEANS, st);
-            hipLaunchKernelGGL(k_nlm_means, grid, dim3(256), 0, st, r->display[0], r->display[1], r->width, r->height, nlm_width);
+            hipLaunchKernelGGL(k_nlm_means, grid, dim3(256), 0, st, display[0], display[1], r->width, r->height, nlm_width);
         }
         {
             ScopedTimer t(r, KN_NLM, st);
-            hipLaunchKernelGGL(k_nlm, grid, dim3(256), 0, st, r->display[0], r->display[1], r->display[2], r->width, r->height,
+            hipLaunchKernelGGL(k_nlm, grid, dim3(256), 0, st, display[0], display[1], display[2], r->width, r->height,
                                nlm_falloff, nlm_width);
         }
-        r->presented = r->display[2];
+        r->presented = display[2];
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -317,10 +308,12 @@ int tinsel_hip_set_probe_sampling(tinsel_hip* r, int mode)
         const float one = 2.0f;         // r2 <= 1 < 2: always keep
         for (uint32_t k : large) table[k] = make_uint2(__builtin_bit_cast(uint32_t, one), k);
         for (uint32_t k : small) table[k] = make_uint2(__builtin_bit_cast(uint32_t, one), k);
-        HIP_TRY(hipMalloc((void**)&r->probeAlias, sizeof(uint2)*n));
-        HIP_TRY(hipMemcpy(r->probeAlias, table.data(), sizeof(uint2)*n, hipMemcpyHostToDevice));
+        DevBuf<uint2> alias;
+        if (alias.upload(table.data(), n))
+            return -1;
+        r->probeAlias = std::move(alias);
     }
-    r->scene.probe.alias = r->probeAlias;
+    r->scene.probe.alias = r->probeAlias.get();
     return 0;
 }
 
@@ -400,7 +393,7 @@ static int read_stats(tinsel_hip* r, unsigned long long* out8)
     std::vector<unsigned long long> shards((size_t)kStatShards*kStatWords);
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(shards.data(), r->statsDev, sizeof(unsigned long long)*shards.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(shards.data(), r->statsDev.get(), sizeof(unsigned long long)*shards.size(), hipMemcpyDeviceToHost));
     for (int w = 0; w < kStatWords; ++w)
         out8[w] = 0;
     for (int b = 0; b < kStatShards; ++b)
@@ -444,7 +437,7 @@ void tinsel_hip_reset_stats(tinsel_hip* r)
         return;
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
-    (void)hipMemset(r->statsDev, 0, sizeof(unsigned long long)*kStatShards*kStatWords);
+    (void)hipMemset(r->statsDev.get(), 0, sizeof(unsigned long long)*kStatShards*kStatWords);
     (void)hipStreamSynchronize(nullptr);
     r->gpuSeconds = 0.0;
 }
@@ -601,35 +594,25 @@ int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, in
         (index < 0 || index >= r->scene.numPrims))
         return fail("leaf: primitive index out of range");
     HIP_TRY(hipSetDevice(r->device));
-    float* dIn = nullptr;
-    uint32_t* dSeeds = nullptr;
-    float* dOut = nullptr;
-    int rc = 0;
+    DevBuf<float> dIn, dOut;
+    DevBuf<uint32_t> dSeeds;
     CameraParams cam;
     memset(&cam, 0, sizeof(cam));
     if (camera && width > 0 && height > 0)
         make_camera(*camera, width, height, cam);
-    do {
-        if (in && in_stride > 0)
-        {
-            if (hipMalloc((void**)&dIn, sizeof(float)*(size_t)n*in_stride) != hipSuccess ||
-                hipMemcpy(dIn, in, sizeof(float)*(size_t)n*in_stride, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("leaf: input upload failed"); break; }
-        }
-        if (seeds)
-        {
-            if (hipMalloc((void**)&dSeeds, sizeof(uint32_t)*(size_t)n) != hipSuccess ||
-                hipMemcpy(dSeeds, seeds, sizeof(uint32_t)*(size_t)n, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("leaf: seed upload failed"); break; }
-        }
-        if (hipMalloc((void**)&dOut, sizeof(float)*(size_t)n*out_stride) != hipSuccess) { rc = fail("leaf: output allocation failed"); break; }
-        hipLaunchKernelGGL(k_leaf, dim3((n + kBlock - 1)/kBlock), dim3(kBlock), stack_bytes(r), nullptr, r->scene, op, index, n, dIn, in_stride,
-                           dSeeds, dOut, out_stride, cam, r->stackNeed);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { rc = fail("leaf: kernel failed"); break; }
-        if (hipMemcpy(out, dOut, sizeof(float)*(size_t)n*out_stride, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail("leaf: download failed"); break; }
-    } while (0);
-    if (dIn) (void)hipFree(dIn);
-    if (dSeeds) (void)hipFree(dSeeds);
-    if (dOut) (void)hipFree(dOut);
-    return rc;
+    if (in && in_stride > 0 && dIn.upload(in, (size_t)n*in_stride))
+        return fail("leaf: input upload failed");
+    if (seeds && dSeeds.upload(seeds, (size_t)n))
+        return fail("leaf: seed upload failed");
+    if (dOut.alloc((size_t)n*out_stride))
+        return fail("leaf: output allocation failed");
+    hipLaunchKernelGGL(k_leaf, dim3((n + kBlock - 1)/kBlock), dim3(kBlock), stack_bytes(r), nullptr, r->scene, op, index, n, dIn.get(), in_stride,
+                       dSeeds.get(), dOut.get(), out_stride, cam, r->stackNeed);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess)
+        return fail("leaf: kernel failed");
+    if (hipMemcpy(out, dOut.get(), sizeof(float)*(size_t)n*out_stride, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("leaf: download failed");
+    return 0;
 }
 
 int tinsel_hip_stack_entries(tinsel_hip* r) { return r ? r->stackNeed : 0; }
@@ -721,14 +704,14 @@ int tinsel_hip_selftest_arith(int device_index, int op, int variant, unsigned lo
     if (variant < 0)
         variant = op == 0 ? kRcpVariant : op == 1 ? kSqrtVariant : kRsqrtVariant;      // what this library is built with
     HIP_TRY(hipSetDevice(device_index));
-    unsigned long long* counts = nullptr;
-    uint32_t* first = nullptr;
-    HIP_TRY(hipMalloc((void**)&counts, 260*sizeof(unsigned long long)));
-    if (hipMalloc((void**)&first, sizeof(uint32_t)) != hipSuccess)
-    {
-        (void)hipFree(counts);
+    DevBuf<unsigned long long> countsDev;
+    DevBuf<uint32_t> firstDev;
+    if (countsDev.alloc(260))
+        return -1;
+    if (firstDev.alloc(1))
         return fail("selftest_arith: allocation failed");
-    }
+    unsigned long long* const counts = countsDev.get();
+    uint32_t* const first = firstDev.get();
     (void)hipMemset(counts, 0, 260*sizeof(unsigned long long));
     (void)hipMemset(first, 0xff, sizeof(uint32_t));
     bool known = true;
@@ -747,16 +730,13 @@ int tinsel_hip_selftest_arith(int device_index, int op, int variant, unsigned lo
     case 203: launch_selftest_arith<2, 3>(counts, first); break;
     default: known = false; break;
     }
-    int rc = 0;
     if (!known)
-        rc = fail("selftest_arith: unknown variant");
-    else if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess ||
+        return fail("selftest_arith: unknown variant");
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess ||
              hipMemcpy(out_counts, counts, 260*sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
              hipMemcpy(out_first_bad, first, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail("selftest_arith: kernel failed");
-    (void)hipFree(counts);
-    (void)hipFree(first);
-    return rc;
+        return fail("selftest_arith: kernel failed");
+    return 0;
 }
 
 // The library's own sort and scan (tn_sort.h: the device BVH builder's) on caller data: keys[0, n) sorted in place by their bits
@@ -766,22 +746,16 @@ int tinsel_hip_selftest_sort(int device_index, unsigned long long* keys, unsigne
     if (!keys || n == 0 || n >= (1ull << 31) || begin_bit < 0 || end_bit > 64 || begin_bit >= end_bit || (begin_bit & 7) || (end_bit & 7))
         return fail("selftest_sort: bad arguments");
     HIP_TRY(hipSetDevice(device_index));
-    unsigned long long *a = nullptr, *b = nullptr;
-    int* scratch = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&a, n*8) != hipSuccess || hipMalloc((void**)&b, n*8) != hipSuccess ||
-        hipMalloc((void**)&scratch, sort_scratch_ints((size_t)n)*sizeof(int)) != hipSuccess)
-        rc = fail("selftest_sort: allocation failed");
-    else if (hipMemcpy(a, keys, n*8, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail("selftest_sort: upload failed");
-    else
-    {
-        radix_sort_keys(a, b, (size_t)n, begin_bit, end_bit, scratch, nullptr);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(keys, b, n*8, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail("selftest_sort: kernels failed");
-    }
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(scratch);
-    return rc;
+    DevBuf<unsigned long long> a, b;
+    DevBuf<int> scratch;
+    if (a.alloc((size_t)n) || b.alloc((size_t)n) || scratch.alloc(sort_scratch_ints((size_t)n)))
+        return fail("selftest_sort: allocation failed");
+    if (hipMemcpy(a.get(), keys, n*8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail("selftest_sort: upload failed");
+    radix_sort_keys(a.get(), b.get(), (size_t)n, begin_bit, end_bit, scratch.get(), nullptr);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(keys, b.get(), n*8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("selftest_sort: kernels failed");
+    return 0;
 }
 
 int tinsel_hip_selftest_scan(int device_index, const int* in, int* out, unsigned long long n)
@@ -789,20 +763,15 @@ int tinsel_hip_selftest_scan(int device_index, const int* in, int* out, unsigned
     if (!in || !out || n == 0 || n >= (1ull << 31))
         return fail("selftest_scan: bad arguments");
     HIP_TRY(hipSetDevice(device_index));
-    int *a = nullptr, *scratch = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&a, n*sizeof(int)) != hipSuccess || hipMalloc((void**)&scratch, scan_scratch_ints((size_t)n)*sizeof(int)) != hipSuccess)
-        rc = fail("selftest_scan: allocation failed");
-    else if (hipMemcpy(a, in, n*sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail("selftest_scan: upload failed");
-    else
-    {
-        exclusive_scan(a, a, (size_t)n, scratch, nullptr);         // (in place, as the builder's radix passes use it)
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(out, a, n*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail("selftest_scan: kernels failed");
-    }
-    (void)hipFree(a); (void)hipFree(scratch);
-    return rc;
+    DevBuf<int> a, scratch;
+    if (a.alloc((size_t)n) || scratch.alloc(scan_scratch_ints((size_t)n)))
+        return fail("selftest_scan: allocation failed");
+    if (hipMemcpy(a.get(), in, n*sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return fail("selftest_scan: upload failed");
+    exclusive_scan(a.get(), a.get(), (size_t)n, scratch.get(), nullptr);         // (in place, as the builder's radix passes use it)
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(out, a.get(), n*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("selftest_scan: kernels failed");
+    return 0;
 }
 
 int tinsel_hip_ubench(int device_index, int kind, unsigned long long bytes, int steps, double* out_ms, double* out_units)
@@ -812,17 +781,18 @@ int tinsel_hip_ubench(int device_index, int kind, unsigned long long bytes, int 
     HIP_TRY(hipSetDevice(device_index));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device_index));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    if (e0.create(true) || e1.create(true))
+        return -1;
     float ms = 0.0f;
     int rc = 0;
     if (kind == 0)
     {
         const size_t n = (size_t)bytes/sizeof(float4);
-        float4 *in = nullptr, *out = nullptr;
-        if (hipMalloc((void**)&in, n*sizeof(float4)) != hipSuccess || hipMalloc((void**)&out, n*sizeof(float4)) != hipSuccess ||
-            hipMemset(in, 0x3c, n*sizeof(float4)) != hipSuccess)
+        DevBuf<float4> inDev, outDev;
+        float4* const in = inDev.alloc(n) ? nullptr : inDev.get();
+        float4* const out = outDev.alloc(n) ? nullptr : outDev.get();
+        if (!in || !out || hipMemset(in, 0x3c, n*sizeof(float4)) != hipSuccess)
             rc = fail("ubench: allocation failed");
         else
         {
@@ -858,8 +828,6 @@ int tinsel_hip_ubench(int device_index, int kind, unsigned long long bytes, int 
             ms = best;
             *out_units = 2.0*(double)(n*sizeof(float4));
         }
-        if (in) (void)hipFree(in);
-        if (out) (void)hipFree(out);
     }
     else
     {
@@ -869,9 +837,11 @@ int tinsel_hip_ubench(int device_index, int kind, unsigned long long bytes, int 
         if (steps < 1)
             steps = 64;
         const unsigned grid = (unsigned)prop.multiProcessorCount*16u;       // 4 workgroups x 4 waves per SIMD-quad: 16 waves per CU
-        float4* recs = nullptr;
-        float* out = nullptr;
-        if (hipMalloc((void**)&recs, (size_t)nrec*64) != hipSuccess || hipMalloc((void**)&out, (size_t)grid*256*sizeof(float)) != hipSuccess)
+        DevBuf<float4> recsDev;         // (a record is four float4)
+        DevBuf<float> outDev;
+        float4* const recs = recsDev.alloc((size_t)nrec*4) ? nullptr : recsDev.get();
+        float* const out = outDev.alloc((size_t)grid*256) ? nullptr : outDev.get();
+        if (!recs || !out)
             rc = fail("ubench: allocation failed");
         else
         {
@@ -890,11 +860,7 @@ int tinsel_hip_ubench(int device_index, int kind, unsigned long long bytes, int 
             (void)hipEventElapsedTime(&ms, e0, e1);
             *out_units = (double)grid*256.0*(double)steps;
         }
-        if (recs) (void)hipFree(recs);
-        if (out) (void)hipFree(out);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *out_ms = (double)ms;
     return rc;
 }

@@ -6,32 +6,15 @@ namespace {
 
 void free_batch(tinsel_hip* r)
 {
-    for (void* p : r->batchAllocs)
-        (void)hipFree(p);
-    r->batchAllocs.clear();
+    r->batchMem.release();
     for (tinsel_hip::DenseLane& lane : r->lane)
-    {
-        tinsel_hip::DenseLane fresh;
-        fresh.walkOverflow = lane.walkOverflow;
-        fresh.walkOverflowCap = lane.walkOverflowCap;
-        lane = fresh;
-    }
+        lane = tinsel_hip::DenseLane();
     r->batchPipeline = -1;
     r->batchSlots = 0;
     r->batchStateSlots = 0;
     r->batchLanes = 1;
     r->batchNee = -1;
     r->batchDepth = -1;
-}
-
-template <class T>
-int batch_alloc(tinsel_hip* r, T** out, size_t count)
-{
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(T)*(count ? count : 1)));
-    r->batchAllocs.push_back(d);
-    *out = (T*)d;
-    return 0;
 }
 
 // blocks per CU of the streaming kernels' fixed grid.  Swept 4..256 on every config: 32 is best everywhere (finer static
@@ -157,16 +140,17 @@ void make_camera(const tinsel_camera& c, int width, int height, CameraParams& ou
     out.shutterEnd = c.shutter_end;
 }
 
-hipEvent_t get_event(tinsel_hip* r)
+// a timing event out of the pool (a new one where the pool is empty)
+Event get_event(tinsel_hip* r)
 {
+    Event e;
     if (!r->eventPool.empty())
     {
-        hipEvent_t e = r->eventPool.back();
+        e = std::move(r->eventPool.back());
         r->eventPool.pop_back();
-        return e;
     }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
+    else
+        (void)e.create(true);
     return e;
 }
 
@@ -191,7 +175,7 @@ struct ScopedTimer
         if (on)
         {
             (void)hipEventRecord(span.stop, stream);
-            r->spans.push_back(span);
+            r->spans.push_back(std::move(span));
         }
     }
 };
@@ -481,7 +465,7 @@ WalkPlan plan_walk(const tinsel_hip* r)
     job.refillMin = std::min(64, std::max(1, t.walk_refill_min > 0 ? t.walk_refill_min : 24));
     job.leafMin = std::min(64, std::max(1, t.walk_leaf_min > 0 ? t.walk_leaf_min : 8));
     job.numPrims = r->walkPrims.count;
-    job.prof = r->walkProf;
+    job.prof = r->walkProf.get();
     int entries = 1;
     for (int k = 0; k < kWalkMaxPrims && k < r->walkPrims.count; ++k)
     {
@@ -688,11 +672,11 @@ int alloc_dense(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& lane, 
     SplitState& ss = lane.ss;
     memset(&ss, 0, sizeof(ss));
     for (int b = 0; b < 2; ++b)
-        if (batch_alloc(r, &ss.rayO[b], cap) || batch_alloc(r, &ss.rayD[b], cap) || batch_alloc(r, &ss.thr[b], cap) ||
-            batch_alloc(r, &ss.rad[b], cap) || batch_alloc(r, &ss.rngId[b], cap))
+        if (r->batchMem.alloc(&ss.rayO[b], cap) || r->batchMem.alloc(&ss.rayD[b], cap) || r->batchMem.alloc(&ss.thr[b], cap) ||
+            r->batchMem.alloc(&ss.rad[b], cap) || r->batchMem.alloc(&ss.rngId[b], cap))
             return -1;
-    if (batch_alloc(r, &ss.segFront, maxRegions*((size_t)maxDepth + 2)) || batch_alloc(r, &ss.segBack, maxRegions*((size_t)maxDepth + 2)) ||
-        batch_alloc(r, &lane.regionOrder, maxRegions/(kBlock/kWave)) || batch_alloc(r, &lane.regionOrderNee, maxRegions/(kBlock/kWave)))
+    if (r->batchMem.alloc(&ss.segFront, maxRegions*((size_t)maxDepth + 2)) || r->batchMem.alloc(&ss.segBack, maxRegions*((size_t)maxDepth + 2)) ||
+        r->batchMem.alloc(&lane.regionOrder, maxRegions/(kBlock/kWave)) || r->batchMem.alloc(&lane.regionOrderNee, maxRegions/(kBlock/kWave)))
         return -1;
     ss.capacity = (uint32_t)cap;
     ss.neePerPath = (int32_t)K;
@@ -702,18 +686,18 @@ int alloc_dense(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& lane, 
     {
         // the K pending light samples of every path, by position, double-buffered like the state (tn_paired.h)
         for (int b = 0; b < 2; ++b)
-            if (batch_alloc(r, &ss.pairThr[b], K ? cap : 1) || batch_alloc(r, &ss.pairRay[b], cap*K*2) || batch_alloc(r, &ss.pairPend[b], K > 1 ? cap*K*2 : cap))     // (sample k's two records at (2k, 2k + 1)*cap; sample 0 has no second one)
+            if (r->batchMem.alloc(&ss.pairThr[b], K ? cap : 1) || r->batchMem.alloc(&ss.pairRay[b], cap*K*2) || r->batchMem.alloc(&ss.pairPend[b], K > 1 ? cap*K*2 : cap))     // (sample k's two records at (2k, 2k + 1)*cap; sample 0 has no second one)
                 return -1;
     }
     if (p.pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT)
-        if (batch_alloc(r, &ss.hit, cap) || batch_alloc(r, &ss.hitPrim, cap) || batch_alloc(r, &ss.pathNee, K ? cap : 1) ||
-            batch_alloc(r, &ss.neeRay, cap*K*2) || batch_alloc(r, &ss.neeSky, r->scene.probe.valid ? cap : 1) ||
-            batch_alloc(r, &ss.neeTime, K ? cap : 1) || batch_alloc(r, &ss.neeRes, cap*K) ||
-            batch_alloc(r, &ss.neeFront, maxRegions*(size_t)maxDepth) || batch_alloc(r, &ss.neeBack, maxRegions*(size_t)maxDepth))
+        if (r->batchMem.alloc(&ss.hit, cap) || r->batchMem.alloc(&ss.hitPrim, cap) || r->batchMem.alloc(&ss.pathNee, K ? cap : 1) ||
+            r->batchMem.alloc(&ss.neeRay, cap*K*2) || r->batchMem.alloc(&ss.neeSky, r->scene.probe.valid ? cap : 1) ||
+            r->batchMem.alloc(&ss.neeTime, K ? cap : 1) || r->batchMem.alloc(&ss.neeRes, cap*K) ||
+            r->batchMem.alloc(&ss.neeFront, maxRegions*(size_t)maxDepth) || r->batchMem.alloc(&ss.neeBack, maxRegions*(size_t)maxDepth))
             return -1;
-    if (p.walkRecords && batch_alloc(r, &lane.walkRec, cap*p.walkRays*(size_t)r->walkPrims.count*2))
+    if (p.walkRecords && r->batchMem.alloc(&lane.walkRec, cap*p.walkRays*(size_t)r->walkPrims.count*2))
         return -1;
-    if (p.workList && (batch_alloc(r, &lane.walkList, cap) || batch_alloc(r, &lane.segPrefix, maxRegions + 1)))
+    if (p.workList && (r->batchMem.alloc(&lane.walkList, cap) || r->batchMem.alloc(&lane.segPrefix, maxRegions + 1)))
         return -1;
     return 0;
 }
@@ -727,15 +711,12 @@ int ensure_walk_overflow(tinsel_hip* r, const BatchPlan& p)
     const size_t need = p.walk ? (size_t)r->numCUs*(size_t)w.perCU*(size_t)w.block*(size_t)w.job.overflowEntries : 0;
     for (int k = 0; k < p.lanes && need; ++k)
     {
-        tinsel_hip::DenseLane& L = r->lane[k];
-        if (L.walkOverflowCap >= need)
+        DevBuf<uint32_t>& columns = r->walkOverflow[k];
+        if (columns.count() >= need)
             continue;
-        if (L.walkOverflow)
+        if (columns)
             (void)hipDeviceSynchronize();       // (another stream's launch may still use the old columns)
-        (void)hipFree(L.walkOverflow);
-        L.walkOverflow = nullptr;
-        L.walkOverflowCap = hipMalloc((void**)&L.walkOverflow, need*sizeof(uint32_t)) == hipSuccess ? need : 0;
-        if (!L.walkOverflowCap)
+        if (columns.alloc(need))
             return fail("k_walk: no memory for the stack overflow");
     }
     return 0;
@@ -755,7 +736,7 @@ int ensure_batch(tinsel_hip* r, const BatchPlan& p, int maxDepth)
     // the radiance of finished paths by slot is what every pipeline hands to the accumulate kernels
     PathState& ps = r->ps;
     memset(&ps, 0, sizeof(ps));
-    if (batch_alloc(r, &ps.rad, p.slots))
+    if (r->batchMem.alloc(&ps.rad, p.slots))
         return -1;
     if (p.pipeline != TINSEL_PIPELINE_MEGAKERNEL)
         for (int k = 0; k < p.lanes; ++k)
@@ -769,7 +750,7 @@ int ensure_batch(tinsel_hip* r, const BatchPlan& p, int maxDepth)
     // radiance a kernel had already written.  Allocation path only.)
     HIP_TRY(hipStreamSynchronize(nullptr));
 
-    r->ctl.stats = r->statsDev;
+    r->ctl.stats = r->statsDev.get();
     r->batchSlots = p.slots;
     r->batchStateSlots = p.stateSlots;
     r->batchLanes = p.lanes;
@@ -838,7 +819,7 @@ int launch_walk(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     job.rec = L.walkRec;
     job.neePerPath = shadowRays ? r->neePerPath : 0;
     job.mixed = !paired ? 0 : mixed ? 1 : shadowRays ? 2 : 0;      // (2: shadow rays only, their time in the state: tn_walk.h)
-    job.overflow = job.overflowEntries ? L.walkOverflow : nullptr;
+    job.overflow = job.overflowEntries ? r->walkOverflow[&L - r->lane].get() : nullptr;
     // (a work item is a ray; with several walked primitives a lane keeps its ray as position | k << 27 while primitives are left: tn_walk.h)
     // (k_walk_rays, whatever the number of walked primitives: ADVICE r05)
     if (!w.single && (ss.capacity >= (1u << 27) || r->neePerPath >= 32))
@@ -916,15 +897,12 @@ int accumulate_tile_list(tinsel_hip* r, const FrameParams& fp)
     std::vector<int> list;
     for (const auto& w : weighted)
         list.push_back(w.second);
+    DevBuf<int> tiles;
+    if (tiles.upload(list.data(), list.size()))
+        return -1;
     if (r->accTilesDev)
-    {
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(r->accTilesDev);
-        r->accTilesDev = nullptr;
-    }
-    HIP_TRY(hipMalloc((void**)&r->accTilesDev, sizeof(int)*(list.empty() ? 1 : list.size())));
-    if (!list.empty())
-        HIP_TRY(hipMemcpy(r->accTilesDev, list.data(), sizeof(int)*list.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());        // (a launch in flight may still read the previous list)
+    r->accTilesDev = std::move(tiles);
     r->accTilesCount = (int)list.size();
     memcpy(r->accTilesKey, key, sizeof(key));
     return 0;
@@ -969,7 +947,7 @@ int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, floa
         {
             if (accumulate_tile_list(r, fp))
                 return -1;
-            tileList = r->accTilesDev;
+            tileList = r->accTilesDev.get();
             tiles = r->accTilesCount;
         }
         if (tiles > 0)
@@ -1290,8 +1268,8 @@ void release_spans(tinsel_hip* r)
 {
     for (TimedSpan& s : r->spans)
     {
-        r->eventPool.push_back(s.start);
-        r->eventPool.push_back(s.stop);
+        r->eventPool.push_back(std::move(s.start));
+        r->eventPool.push_back(std::move(s.stop));
     }
     r->spans.clear();
 }
@@ -1374,18 +1352,10 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
         if (r->passSeedsDev)
             HIP_TRY(hipDeviceSynchronize());
         const size_t want = (size_t)passes + kSeedsAhead;
-        if (r->passSeedsCap < want)
-        {
-            if (r->passSeedsDev)
-                (void)hipFree(r->passSeedsDev);
-            r->passSeedsDev = nullptr;
-            r->passSeedsCap = r->passSeedsCount = 0;
-            HIP_TRY(hipMalloc((void**)&r->passSeedsDev, sizeof(uint32_t)*want));
-            r->passSeedsCap = want;
-        }
-        if (!r->passSeedsReady)
-            HIP_TRY(hipEventCreateWithFlags(&r->passSeedsReady, hipEventDisableTiming));
-        hipLaunchKernelGGL(k_pass_seeds, dim3(1), dim3(1), 0, st, r->seedRng.s1, r->seedRng.s2, (int)want, r->passSeedsDev);
+        r->passSeedsCount = 0;
+        if (r->passSeedsDev.grow(want) || r->passSeedsReady.create())
+            return -1;
+        hipLaunchKernelGGL(k_pass_seeds, dim3(1), dim3(1), 0, st, r->seedRng.s1, r->seedRng.s2, (int)want, r->passSeedsDev.get());
         HIP_TRY(hipEventRecord(r->passSeedsReady, st));
         r->passSeedsBase = r->passIndex;
         r->passSeedsCount = want;
@@ -1393,7 +1363,7 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     }
     else if (st != r->passSeedsStream)
         HIP_TRY(hipStreamWaitEvent(st, r->passSeedsReady, 0));
-    r->passSeeds = r->passSeedsDev + (r->passIndex - r->passSeedsBase);
+    r->passSeeds = r->passSeedsDev.get() + (r->passIndex - r->passSeedsBase);
 
     const size_t perPass = slots_per_pass(r, fp.width, fp.height);
     int perBatch = (int)std::max<size_t>(1, batch_slots(r)/perPass);
@@ -1406,14 +1376,14 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
 
     if (traceOnly && perBatch < passes)
         return fail("render: look-ahead batch does not fit");
-    if (plan.lanes == 2 && !r->laneStream)
+    if (plan.lanes == 2 && !r->laneSync.stream)
     {
-        HIP_TRY(hipStreamCreateWithFlags(&r->laneStream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&r->laneFork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&r->laneJoin, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k)
-            HIP_TRY(hipEventCreateWithFlags(&r->accDone[k], hipEventDisableTiming));
+        tinsel_hip::LaneSync sync;
+        if (sync.create())
+            return -1;
+        r->laneSync = std::move(sync);
     }
+    const tinsel_hip::LaneSync& sync = r->laneSync;
     for (int done = 0; done < passes; done += perBatch)
     {
         const int n = std::min(perBatch, passes - done);
@@ -1430,31 +1400,31 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
         }
         // the overlapped chunks (plan_batch): chunk c in lane c on its own stream, its radiance at its passes' slots
         const int first = std::min(plan.chunkPasses, (n + 1)/2);
-        HIP_TRY(hipEventRecord(r->laneFork, st));                       // whatever the caller's stream holds comes first
-        HIP_TRY(hipStreamWaitEvent(r->laneStream, r->laneFork, 0));
+        HIP_TRY(hipEventRecord(sync.fork, st));                       // whatever the caller's stream holds comes first
+        HIP_TRY(hipStreamWaitEvent(sync.stream, sync.fork, 0));
         int rc = 0;
         for (int c = 0; c < 2 && !rc; ++c)
         {
-            hipStream_t s = c ? r->laneStream : st;
+            hipStream_t s = c ? sync.stream : st;
             float4* const rad = r->ps.rad + (size_t)(c ? first : 0)*perPass;
             fp.passBase = done + (c ? first : 0);
             fp.numPasses = c ? n - first : first;
             r->lastLane = c;
             rc = render_batch(r, plan, r->lane[c], s, cam, fp, rad, false);
             if (!rc && c)
-                rc = hipStreamWaitEvent(s, r->accDone[0], 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
+                rc = hipStreamWaitEvent(s, sync.accDone, 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
             if (!rc)
                 rc = launch_accumulate(r, s, r->lastFp, rad, r->accum);
             if (!rc)
-                rc = hipEventRecord(c ? r->laneJoin : r->accDone[0], s) == hipSuccess ? 0 : fail("render: hipEventRecord");
+                rc = hipEventRecord(c ? sync.join : sync.accDone, s) == hipSuccess ? 0 : fail("render: hipEventRecord");
         }
         if (!rc)
-            rc = hipStreamWaitEvent(st, r->laneJoin, 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
+            rc = hipStreamWaitEvent(st, sync.join, 0) == hipSuccess ? 0 : fail("render: hipStreamWaitEvent");
         if (rc)
         {
             // kernels already enqueued on the second stream still run over the path state and the accumulator: nothing the caller does
             // next (another render on another stream, init, destroy) may overtake them (lookahead_cancel does the same)
-            (void)hipStreamSynchronize(r->laneStream);
+            (void)hipStreamSynchronize(sync.stream);
             return -1;
         }
         // (r->lastFp: the whole batch, its radiance at ps.rad)
@@ -1509,20 +1479,11 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
             v = g.rand();
     }
 
-    struct DeviceBuffers
-    {
-        uint32_t* seeds = nullptr;
-        uint32_t* cost = nullptr;
-        ~DeviceBuffers()
-        {
-            if (seeds) (void)hipFree(seeds);
-            if (cost) (void)hipFree(cost);
-        }
-    } dev;
-    HIP_TRY(hipMalloc((void**)&dev.seeds, sizeof(uint32_t)*seeds.size()));
-    HIP_TRY(hipMalloc((void**)&dev.cost, sizeof(uint32_t)*4*npix));
-    HIP_TRY(hipMemcpy(dev.seeds, seeds.data(), sizeof(uint32_t)*seeds.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(dev.cost, 0, sizeof(uint32_t)*4*npix));
+    DevBuf<uint32_t> seedsDev, costDev;
+    if (seedsDev.alloc(seeds.size()) || costDev.alloc(4*npix))
+        return -1;
+    HIP_TRY(hipMemcpy(seedsDev.get(), seeds.data(), sizeof(uint32_t)*seeds.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(costDev.get(), 0, sizeof(uint32_t)*4*npix));
 
     CameraParams cam;
     make_camera(*camera, options->width, options->height, cam);
@@ -1545,10 +1506,10 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
         a.scene = r->scene;
         a.cam = cam;
         a.fp = fp;
-        a.passSeeds = dev.seeds;
+        a.passSeeds = seedsDev.get();
         a.stackEntries = r->stackNeed;
         a.ldsBytes = (uint32_t)stack_bytes(r);
-        a.cost = dev.cost;
+        a.cost = costDev.get();
         a.grid = (int)((slots + kBlock - 1)/kBlock);
         a.variant = residency(r->scene, r->scene.arenaLdsBytes) == RES_LDS ? PK_COST_LDS : PK_COST;
         ScopedTimer t(r, KN_COST, st);
@@ -1558,7 +1519,7 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     }
 
     std::vector<uint32_t> planes(4*npix);
-    HIP_TRY(hipMemcpy(planes.data(), dev.cost, sizeof(uint32_t)*planes.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(planes.data(), costDev.get(), sizeof(uint32_t)*planes.size(), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < npix; ++k)
         for (int c = 0; c < 4; ++c)
             out[k*4 + c] = planes[(size_t)c*npix + k];

@@ -108,7 +108,7 @@ struct GroupMember
 {
     tinsel_hip* r = nullptr;
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     ncclComm_t comm = nullptr;
     std::thread thread;
     int rc = 0;
@@ -123,22 +123,28 @@ struct tinsel_hip_group
     bool oneDevice = false;         // validation: all members on device 0, device-local sum instead of RCCL
     bool solo = true;               // one member used directly: no threads, no reduce, total aliases its accumulator
     int width = 0, height = 0;
-    float4* total = nullptr;        // on member 0's device; == member 0's accumulator when there is one member
+    // The reduced frame, on member 0's device: a VIEW.  Of sums.total where there are several members; of member 0's accumulator where there
+    // is one (solo: set at Init and read only as "Init has run" -- every solo call goes to the member itself; never freed by the group).
+    float4* total = nullptr;
+    // total / totalNext (below) and the copy stream: all or none (tinsel_hip_group_init makes them in a local)
+    struct Sums
+    {
+        DevBuf<float4> total, next;
+        Stream copyStream;
+        int create(size_t pixels) { return total.alloc(pixels) || next.alloc(pixels) || copyStream.create() ? -1 : 0; }
+    } sums;
 
     // Look-ahead for the reference's call pattern at N members (tinsel_hip_group_set_lookahead): after a read-back every
     // member keeps a queue of speculated calls (lookahead_extend: one batch of `depth` calls of ITS shard, one snapshot per
     // call) and the NEXT call's snapshots are reduced into `totalNext` while this call's `total` crosses PCIe.  A matching
     // call then only waits for that job, swaps the buffers and copies.
     int lookahead = TINSEL_LOOKAHEAD_OFF;
-    float4* totalNext = nullptr;
     bool aheadInFlight = false;     // a GJ_AHEAD job has been posted and not yet waited for
     bool aheadValid = false;        // every member holds a snapshot of the call described below (and totalNext its reduced sum)
     tinsel_camera aheadCamera;
     tinsel_options aheadOptions;
     int aheadPasses = 0;
-    hipStream_t copyStream = nullptr;   // on member 0's device
-    void* pinnedPtr = nullptr;
-    size_t pinnedBytes = 0;
+    PinnedOutput pinned;
 
     // job hand-off: the caller posts (job, epoch), every worker runs it for its member and reports
     std::mutex mu;
@@ -211,7 +217,7 @@ void group_worker(tinsel_hip_group* g, int rank)
                     rc = fail("group: look-ahead wait failed");
                 else
                 {
-                    rc = rccl_reduce_accum(m.comm, shot.buf, g->totalNext, (size_t)g->width*g->height, 0, m.stream, "group look-ahead");
+                    rc = rccl_reduce_accum(m.comm, shot.buf.get(), g->sums.next.get(), (size_t)g->width*g->height, 0, m.stream, "group look-ahead");
                 }
             }
         }
@@ -281,14 +287,10 @@ void group_ahead_drop(tinsel_hip_group* g)
 
 void group_unpin(tinsel_hip_group* g)
 {
-    if (!g->pinnedPtr)
+    if (!g->pinned.held())
         return;
     (void)hipSetDevice(g->members[0].device);
-    if (g->copyStream)
-        (void)hipStreamSynchronize(g->copyStream);
-    (void)hipHostUnregister(g->pinnedPtr);
-    g->pinnedPtr = nullptr;
-    g->pinnedBytes = 0;
+    g->pinned.release(g->sums.copyStream);
 }
 
 // total = sum of the members' accumulators, on member 0's device (the workers must be idle: group_ahead_join)
@@ -337,15 +339,6 @@ void tinsel_hip_group_destroy(tinsel_hip_group* g)
         (void)hipSetDevice(m.device);
         if (m.comm && g_rccl.CommDestroy)
             (void)g_rccl.CommDestroy(m.comm);
-        if (m.stream)
-            (void)hipStreamDestroy(m.stream);
-    }
-    if (!g->solo && !g->members.empty())
-    {
-        (void)hipSetDevice(g->members[0].device);
-        if (g->total) (void)hipFree(g->total);
-        if (g->totalNext) (void)hipFree(g->totalNext);
-        if (g->copyStream) (void)hipStreamDestroy(g->copyStream);
     }
     for (GroupMember& m : g->members)
         tinsel_hip_destroy(m.r);
@@ -391,7 +384,7 @@ tinsel_hip_group* tinsel_hip_group_create_tuned(const tinsel_scene_desc* scene, 
         m.device = g->oneDevice ? 0 : k;
         m.r = tinsel_hip_create_tuned(scene, m.device, tuning);
         if (!m.r || tinsel_hip_set_shard(m.r, k, n, tile) || hipSetDevice(m.device) != hipSuccess ||
-            hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking) != hipSuccess)
+            m.stream.create())
         {
             if (m.r)
                 fail("group_create: member " + std::to_string(k) + " could not be set up");
@@ -445,17 +438,15 @@ int tinsel_hip_group_init(tinsel_hip_group* g, int width, int height)
     if (group_run(g, GJ_INIT))
         return -1;
     HIP_TRY(hipSetDevice(g->members[0].device));
-    if (g->total)
-        (void)hipFree(g->total);
-    if (g->totalNext)
-        (void)hipFree(g->totalNext);
-    g->total = g->totalNext = nullptr;
-    HIP_TRY(hipMalloc((void**)&g->total, sizeof(float4)*(size_t)width*height));
-    HIP_TRY(hipMalloc((void**)&g->totalNext, sizeof(float4)*(size_t)width*height));
-    HIP_TRY(hipMemset(g->total, 0, sizeof(float4)*(size_t)width*height));
+    g->total = nullptr;
+    g->sums = tinsel_hip_group::Sums();
+    tinsel_hip_group::Sums sums;
+    if (sums.create((size_t)width*height))
+        return -1;
+    HIP_TRY(hipMemset(sums.total.get(), 0, sizeof(float4)*(size_t)width*height));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if (!g->copyStream)
-        HIP_TRY(hipStreamCreateWithFlags(&g->copyStream, hipStreamNonBlocking));
+    g->sums = std::move(sums);
+    g->total = g->sums.total.get();
     return 0;
 }
 
@@ -506,7 +497,10 @@ int tinsel_hip_group_render(tinsel_hip_group* g, const tinsel_camera* camera, co
                 return -1;
         }
         else
-            std::swap(g->total, g->totalNext);
+        {
+            g->sums.total.swap(g->sums.next);
+            g->total = g->sums.total.get();
+        }
     }
     else
     {
@@ -532,18 +526,7 @@ int tinsel_hip_group_render(tinsel_hip_group* g, const tinsel_camera* camera, co
     //    `depth` calls at a time), its snapshots reduced into totalNext -- per call the caller waits for one reduce (already
     //    done, as a rule) and one copy.  Page-locking the caller's array is an explicit opt-in, as for one device.
     const bool pin = g->lookahead == TINSEL_LOOKAHEAD_PIN_OUTPUT;
-    if (g->pinnedPtr && (!pin || g->pinnedPtr != (void*)out_rgba || g->pinnedBytes != bytes))
-        group_unpin(g);
-    if (pin && !g->pinnedPtr)
-    {
-        if (hipHostRegister(out_rgba, bytes, hipHostRegisterDefault) == hipSuccess)
-        {
-            g->pinnedPtr = out_rgba;
-            g->pinnedBytes = bytes;
-        }
-        else
-            (void)hipGetLastError();
-    }
+    (void)g->pinned.want(out_rgba, bytes, pin, g->sums.copyStream);
     auto post_ahead = [&] {
         g->aheadCamera = *camera;
         g->aheadOptions = *options;
@@ -571,7 +554,8 @@ int tinsel_hip_group_present(tinsel_hip_group* g, const tinsel_options* options,
     if (group_reduce(g))
         return -1;
     // the display stage of member 0 on the reduced frame
-    float4* own = r0->accum;
+    // member 0's accumulator view is LENT the reduced frame for this one call and handed back on every path (its owner is not touched)
+    float4* const own = r0->accum;
     r0->accum = g->total;
     const int rc = tinsel_hip_present(r0, options, nlm_width, nlm_falloff, out_rgba);
     r0->accum = own;

@@ -296,36 +296,10 @@ constexpr int kInlineMaxTris = 7;               // ... of a scene that has a mes
 constexpr int kWalkTopNodes = 2048;             // internal nodes of a mesh in HBM numbered breadth-first (128 KB: more than LDS can take)
 constexpr size_t kArenaLdsLimit = 32768;        // arenas up to this size are staged into LDS by the kernels
 
-struct DeviceArena
-{
-    std::vector<void*> allocs;
-
-    template <class T>
-    T* upload(const T* host, size_t count)
-    {
-        if (count == 0)
-            return nullptr;
-        void* d = nullptr;
-        if (hipMalloc(&d, sizeof(T)*count) != hipSuccess)
-            return nullptr;
-        allocs.push_back(d);
-        if (hipMemcpy(d, host, sizeof(T)*count, hipMemcpyHostToDevice) != hipSuccess)
-            return nullptr;
-        return (T*)d;
-    }
-
-    void release()
-    {
-        for (void* p : allocs)
-            (void)hipFree(p);
-        allocs.clear();
-    }
-};
-
 const char* kKernelNames[] = { "k_generate", "k_extend", "k_shade", "k_shadow", "k_accumulate", "k_mega", "k_normals", "k_bounce",
                                "k_present", "k_nlm_means", "k_nlm", "k_walk", "k_lights", "k_seg", "k_step", "k_cost", "k_query" };
 enum { KN_GENERATE = 0, KN_EXTEND, KN_SHADE, KN_SHADOW, KN_ACCUMULATE, KN_MEGA, KN_NORMALS, KN_BOUNCE, KN_PRESENT, KN_NLM_MEANS, KN_NLM, KN_WALK, KN_LIGHTS, KN_SEG, KN_STEP, KN_COST, KN_QUERY, KN_COUNT };
 
-struct TimedSpan { int kernel; hipEvent_t start, stop; };
+struct TimedSpan { int kernel; Event start, stop; };
 
 } // namespace

@@ -26,8 +26,8 @@ void lookahead_cancel(tinsel_hip* r)
         (void)hipStreamSynchronize(r->workStream);
     for (tinsel_hip::SpecShot& shot : r->specQueue)
     {
-        r->specFree.push_back(shot.buf);
-        r->eventPool.push_back(shot.ready);
+        r->specFree.push_back(std::move(shot.buf));
+        r->eventPool.push_back(std::move(shot.ready));
     }
     r->specQueue.clear();
 }
@@ -35,10 +35,8 @@ void lookahead_cancel(tinsel_hip* r)
 void lookahead_release(tinsel_hip* r)
 {
     lookahead_cancel(r);
-    for (float4* b : r->specFree)
-        (void)hipFree(b);
     r->specFree.clear();
-    if (r->pinnedPtr) { (void)hipHostUnregister(r->pinnedPtr); r->pinnedPtr = nullptr; r->pinnedBytes = 0; }
+    r->pinned.release(nullptr);
 }
 
 // Speculate `depth` more calls: ONE batch of depth x passes passes is traced (as efficient as the resident path's batches),
@@ -52,26 +50,28 @@ int lookahead_extend(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     r->passIndex = committed;
     if (rc)
         return -1;
-    const float4* src = r->specQueue.empty() ? r->accum : r->specQueue.back().buf;
+    const float4* src = r->specQueue.empty() ? r->accum : r->specQueue.back().buf.get();
     for (int j = 0; j < depth; ++j)
     {
-        float4* dst = nullptr;
+        // the shot owns its buffer and event from here on: a failure below frees them (the caller cancels, which waits for the work stream)
+        tinsel_hip::SpecShot shot;
         if (!r->specFree.empty())
         {
-            dst = r->specFree.back();
+            shot.buf = std::move(r->specFree.back());
             r->specFree.pop_back();
         }
-        else
-            HIP_TRY(hipMalloc((void**)&dst, bytes));
+        if (!shot.buf && shot.buf.alloc((size_t)r->width*r->height))
+            return -1;
+        float4* const dst = shot.buf.get();
         HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, r->workStream));
         FrameParams fp = r->lastFp;
         fp.accBegin = j*passes;
         fp.accEnd = (j + 1)*passes;
         if (launch_accumulate(r, r->workStream, fp, r->ps.rad, dst))
             return -1;
-        tinsel_hip::SpecShot shot = { dst, get_event(r) };
+        shot.ready = get_event(r);
         HIP_TRY(hipEventRecord(shot.ready, r->workStream));
-        r->specQueue.push_back(shot);
+        r->specQueue.push_back(std::move(shot));
         src = dst;
     }
     r->specNextPass += (uint32_t)(passes*depth);
@@ -92,23 +92,26 @@ int lookahead_depth(const tinsel_hip* r, int passes)
 int lookahead_streams(tinsel_hip* r)
 {
     HIP_TRY(hipSetDevice(r->device));
-    if (!r->workStream)
-    {
-        HIP_TRY(hipStreamCreateWithFlags(&r->workStream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&r->copyStream, hipStreamNonBlocking));
-    }
+    if (r->workStream)
+        return 0;
+    Stream work, copy;
+    if (work.create() || copy.create())
+        return -1;
+    r->workStream = std::move(work);
+    r->copyStream = std::move(copy);
     return 0;
 }
 
 // the front of the speculation queue becomes the running sum (the caller has checked that it is this call's)
 int lookahead_commit(tinsel_hip* r, int passes)
 {
-    tinsel_hip::SpecShot shot = r->specQueue.front();
+    HIP_TRY(hipEventSynchronize(r->specQueue.front().ready));
+    tinsel_hip::SpecShot shot = std::move(r->specQueue.front());
     r->specQueue.pop_front();
-    HIP_TRY(hipEventSynchronize(shot.ready));
-    r->eventPool.push_back(shot.ready);
-    r->specFree.push_back(r->accum);        // the previous running sum: copied out by the previous call, copied from by this shot
-    r->accum = shot.buf;
+    r->eventPool.push_back(std::move(shot.ready));
+    r->specFree.push_back(std::move(r->accumOwn));      // the previous running sum: copied out by the previous call, copied from by this shot
+    r->accumOwn = std::move(shot.buf);
+    r->accum = r->accumOwn.get();
     r->passIndex += (uint32_t)passes;
     return 0;
 }
@@ -145,23 +148,7 @@ int lookahead_render(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     //    caller guarantees the array outlives the renderer or the next Init): registered in place, the copy is asynchronous
     //    and starts first.
     const bool pin = r->lookahead == TINSEL_LOOKAHEAD_PIN_OUTPUT;
-    if (r->pinnedPtr && (!pin || r->pinnedPtr != (void*)out_rgba || r->pinnedBytes != bytes))
-    {
-        (void)hipHostUnregister(r->pinnedPtr);
-        r->pinnedPtr = nullptr;
-        r->pinnedBytes = 0;
-    }
-    if (pin && !r->pinnedPtr)
-    {
-        if (hipHostRegister(out_rgba, bytes, hipHostRegisterDefault) == hipSuccess)
-        {
-            r->pinnedPtr = out_rgba;
-            r->pinnedBytes = bytes;
-        }
-        else
-            (void)hipGetLastError();        // pageable copy below: still correct
-    }
-    const bool asyncCopy = r->pinnedPtr != nullptr;
+    const bool asyncCopy = r->pinned.want(out_rgba, bytes, pin, nullptr);      // (refused: the pageable copy below is still correct)
     if (asyncCopy)
         HIP_TRY(hipMemcpyAsync(out_rgba, r->accum, bytes, hipMemcpyDeviceToHost, r->copyStream));
 

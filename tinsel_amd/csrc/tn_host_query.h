@@ -67,25 +67,27 @@ int launch_query(tinsel_hip* r, int mode, size_t n, const void* rays, void* out,
     a.query.width = width;
     a.query.time = time;
     a.query.first = first;
-    hipEvent_t* slotDone = nullptr;
+    hipEvent_t slotDone = nullptr;
     if (plan.persistent > 0)
     {
         // A cursor word of this launch's own, out of a ring: queries on different streams may run side by side (the device entry does not
         // wait), so they cannot share one.  The word is zeroed on THIS stream in front of the kernel; before a slot is used again, this
         // stream waits for the launch that had it last.
-        if (!r->queryCursorDev)
+        if (!r->queryCursors)
         {
-            HIP_TRY(hipMalloc((void**)&r->queryCursorDev, sizeof(uint32_t)*tinsel_hip::kQueryCursors));
-            for (hipEvent_t& e : r->queryCursorDone)
-                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            std::unique_ptr<tinsel_hip::QueryCursors> ring(new tinsel_hip::QueryCursors());
+            if (ring->create())
+                return -1;
+            r->queryCursors = std::move(ring);
         }
-        const uint32_t slot = r->queryCursorNext++ % tinsel_hip::kQueryCursors;
-        slotDone = &r->queryCursorDone[slot];
-        if (r->queryCursorUsed[slot])
-            HIP_TRY(hipStreamWaitEvent(st, *slotDone, 0));
-        r->queryCursorUsed[slot] = true;
-        HIP_TRY(hipMemsetAsync(r->queryCursorDev + slot, 0, sizeof(uint32_t), st));
-        a.query.cursor = r->queryCursorDev + slot;
+        tinsel_hip::QueryCursors& ring = *r->queryCursors;
+        const uint32_t slot = ring.next++ % tinsel_hip::kQueryCursors;
+        slotDone = ring.done[slot];
+        if (ring.used[slot])
+            HIP_TRY(hipStreamWaitEvent(st, slotDone, 0));
+        ring.used[slot] = true;
+        HIP_TRY(hipMemsetAsync(ring.words.get() + slot, 0, sizeof(uint32_t), st));
+        a.query.cursor = ring.words.get() + slot;
     }
     a.stackEntries = plan.stackEntries;
     a.ldsBytes = plan.ldsBytes;
@@ -98,7 +100,7 @@ int launch_query(tinsel_hip* r, int mode, size_t n, const void* rays, void* out,
     }
     HIP_TRY(hipGetLastError());
     if (slotDone)
-        HIP_TRY(hipEventRecord(*slotDone, st));
+        HIP_TRY(hipEventRecord(slotDone, st));
     return 0;
 }
 
@@ -112,20 +114,11 @@ int query_ready(tinsel_hip* r, const char* who)
     return 0;
 }
 
-int query_buffer(void*& buf, size_t& cap, size_t bytes)
+int query_buffer(DevBuf<unsigned char>& buf, size_t bytes)
 {
-    if (cap >= bytes)
-        return 0;
-    if (buf)
-    {
+    if (buf && buf.count() < bytes)
         HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(buf);
-    }
-    buf = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&buf, bytes));
-    cap = bytes;
-    return 0;
+    return buf.grow(bytes);
 }
 
 } // namespace

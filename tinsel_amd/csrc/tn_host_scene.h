@@ -166,28 +166,18 @@ int fitting_stack(const tinsel_hip* r, int sceneNeed, const std::vector<DevMesh>
 template <class Build>
 int timed_build(double* ms, Build&& build)
 {
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    if (e0.create(true) || e1.create(true))
+        return -1;
     (void)hipEventRecord(e0, nullptr);
     const int rc = build();
     (void)hipEventRecord(e1, nullptr);
     (void)hipEventSynchronize(e1);
     float t = 0.0f;
     (void)hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (!rc && ms)
         *ms = t;
     return rc;
-}
-
-// frees the device-built trees lbvhAllocs[first, last) and drops them from the list
-void free_lbvh_allocs(tinsel_hip* r, size_t first, size_t last)
-{
-    for (size_t k = first; k < last; ++k)
-        (void)hipFree(r->lbvhAllocs[k]);
-    r->lbvhAllocs.erase(r->lbvhAllocs.begin() + (long)first, r->lbvhAllocs.begin() + (long)last);
 }
 
 // PrimitiveArea of mesh primitive p as it is now, area*endTransform.s (intersection.h:843-847), and its reciprocal into p's Mat128 in the arena
@@ -216,28 +206,24 @@ int tinsel_hip_set_mesh_bvh(tinsel_hip* r, int mode, double* build_ms)
         *build_ms = 0.0;
 
     std::vector<DevMesh> next = r->meshesRef;
-    const size_t prevAllocs = r->lbvhAllocs.size();
+    DevPool built;          // the new generation of trees: dropped on every failure below (a failed build's too), which keeps what was there
     const int rc = mode == TINSEL_BVH_REFERENCE ? 0 : timed_build(build_ms, [&] {
         int rc = 0;
         for (size_t m = 0; m < next.size() && !rc; ++m)
             if (!next[m].inArena && next[m].numTris >= 2)       // LDS-resident meshes keep their (tiny) reference trees
-                rc = build_device_bvh(r, r->meshesRef[m], next[m], mode);
+                rc = build_device_bvh(built, r->meshesRef[m], next[m], mode);
         return rc;
     });
     const int stack = rc ? -1 : fitting_stack(r, r->sceneStackNeed, next);
     if (stack < 0)
-    {
-        // keep what was there: drop the trees just built (a failed build's too)
-        free_lbvh_allocs(r, prevAllocs, r->lbvhAllocs.size());
         return rc ? rc : fail("set_mesh_bvh: tree too deep for the LDS traversal stack (previous trees kept)");
-    }
     if (!next.empty())
         HIP_TRY(hipMemcpy((void*)r->scene.meshes, next.data(), sizeof(DevMesh)*next.size(), hipMemcpyHostToDevice));
     r->meshesNow = next;
     r->stackNeed = stack;
     r->bvhMode = mode;
     // the previous generation of device-built trees is unreachable now (a per-frame rebuild must not grow)
-    free_lbvh_allocs(r, 0, prevAllocs);
+    r->lbvhTrees = std::move(built);
     return 0;
 }
 
@@ -257,34 +243,27 @@ int tinsel_hip_refit_mesh(tinsel_hip* r, int primitive, const float* positions_x
 
     const int numTris = dm.numTris;
     const int numNodes = numTris - 1;           // one triangle per leaf: internal nodes
-    float* posDev = nullptr;
-    float* own = nullptr;
-    int* gen = nullptr;
-    int rc = 0;
-    do {
-        if (hipMalloc((void**)&posDev, sizeof(float)*3*(size_t)num_vertices) != hipSuccess ||
-            hipMemcpy(posDev, positions_xyz, sizeof(float)*3*(size_t)num_vertices, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("refit_mesh: upload failed"); break; }
-        hipLaunchKernelGGL(k_refit_tris, dim3((unsigned)((numTris + 255)/256)), dim3(256), 0, nullptr, const_cast<Tri48*>(dm.tris), numTris, posDev);
-        if (normals_xyz && hipMemcpy(const_cast<float*>(dm.normals), normals_xyz, sizeof(float)*3*(size_t)num_vertices, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("refit_mesh: normals upload failed"); break; }
+    {
+        DevBuf<float> posDev, own;
+        DevBuf<int> gen;
+        if (posDev.upload(positions_xyz, 3*(size_t)num_vertices))
+            return fail("refit_mesh: upload failed");
+        hipLaunchKernelGGL(k_refit_tris, dim3((unsigned)((numTris + 255)/256)), dim3(256), 0, nullptr, const_cast<Tri48*>(dm.tris), numTris, posDev.get());
+        if (normals_xyz && hipMemcpy(const_cast<float*>(dm.normals), normals_xyz, sizeof(float)*3*(size_t)num_vertices, hipMemcpyHostToDevice) != hipSuccess)
+            return fail("refit_mesh: normals upload failed");
         if (numNodes > 0)
         {
-            if (hipMalloc((void**)&own, sizeof(float)*6*(size_t)numNodes) != hipSuccess || hipMalloc((void**)&gen, sizeof(int)*(size_t)numNodes) != hipSuccess)
-            { rc = fail("refit_mesh: device allocation failed"); break; }
+            if (own.alloc(6*(size_t)numNodes) || gen.alloc((size_t)numNodes))
+                return fail("refit_mesh: device allocation failed");
             // the tree in use and, when a device-built one is, the reference's too (switching back must not find stale boxes)
             const DevMesh* trees[2] = { &dm, r->meshesRef[(size_t)mi].nodes != dm.nodes ? &r->meshesRef[(size_t)mi] : nullptr };
             for (const DevMesh* tree : trees)
-                if (tree && !rc)
-                    rc = refit_device_bvh(*tree, dm.tris, own, gen);
-            if (rc)
-                break;
+                if (tree && refit_device_bvh(*tree, dm.tris, own.get(), gen.get()))
+                    return -1;
         }
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { rc = fail("refit_mesh: kernels failed"); break; }
-    } while (false);
-    if (posDev) (void)hipFree(posDev);
-    if (own) (void)hipFree(own);
-    if (gen) (void)hipFree(gen);
-    if (rc)
-        return rc;
+        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess)
+            return fail("refit_mesh: kernels failed");
+    }
 
     // Mesh::RebuildCDF (mesh.cpp:340-368) in the reference's own serial fp32 order, then PrimitiveArea of every instance
     const std::vector<int32_t>& idx = r->meshIndices[(size_t)mi];
@@ -401,25 +380,22 @@ int tinsel_hip_rebuild_scene(tinsel_hip* r, int mode, const tinsel_bvh_node* nod
                 T.bx = hi[(size_t)i].x; T.by = hi[(size_t)i].y; T.bz = hi[(size_t)i].z; T.i1 = i;
                 T.cx = lo[(size_t)i].x; T.cy = lo[(size_t)i].y; T.cz = lo[(size_t)i].z; T.i2 = i;
             }
-            Tri48* itemsDev = nullptr;
-            HIP_TRY(hipMalloc((void**)&itemsDev, sizeof(Tri48)*(size_t)P));
+            DevBuf<Tri48> itemsDev;
+            DevPool tree;               // the builder's own allocation for this tree: the arena takes a copy
+            if (itemsDev.alloc((size_t)P))
+                return -1;
             std::vector<Node64> built((size_t)P - 1);
             DevMesh fake, out;
             memset(&fake, 0, sizeof(fake));
-            fake.tris = itemsDev;
+            fake.tris = itemsDev.get();
             fake.numTris = P;
             fake.inArena = 1;           // (no bottom-level records for this one)
-            const size_t allocsBefore = r->lbvhAllocs.size();
-            int rc = hipMemcpy(itemsDev, items.data(), sizeof(Tri48)*(size_t)P, hipMemcpyHostToDevice) == hipSuccess ? 0 : fail("rebuild_scene: upload failed");
-            if (!rc)
-                rc = timed_build(build_ms, [&] { return build_device_bvh(r, fake, out, TINSEL_BVH_PLOC); });
-            if (!rc && hipMemcpy(built.data(), out.nodes, sizeof(Node64)*((size_t)P - 1), hipMemcpyDeviceToHost) != hipSuccess)
-                rc = fail("rebuild_scene: read-back failed");
-            // the builder's own allocation for this tree: the arena takes a copy
-            free_lbvh_allocs(r, allocsBefore, r->lbvhAllocs.size());
-            (void)hipFree(itemsDev);
-            if (rc)
-                return rc;
+            if (hipMemcpy(itemsDev.get(), items.data(), sizeof(Tri48)*(size_t)P, hipMemcpyHostToDevice) != hipSuccess)
+                return fail("rebuild_scene: upload failed");
+            if (timed_build(build_ms, [&] { return build_device_bvh(tree, fake, out, TINSEL_BVH_PLOC); }))
+                return -1;
+            if (hipMemcpy(built.data(), out.nodes, sizeof(Node64)*((size_t)P - 1), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail("rebuild_scene: read-back failed");
             // root box: the union of its children's
             const Node64& rt = built[0];
             ref.reserve((size_t)2*P - 1);

@@ -38,7 +38,7 @@ struct tinsel_hip
     int numCUs = 256;
     tinsel_hip_tuning tune = tuning_defaults();     // (tinsel_hip_create_tuned / tinsel_hip_set_tuning; nothing is read from the environment)
 
-    DeviceArena sceneMem;
+    DevPool sceneMem;                   // every upload of the scene: the arena, the meshes in HBM, the probe
     DevScene scene;
     int stackNeed = 16;
     int neePerPath = 0;
@@ -72,27 +72,29 @@ struct tinsel_hip
     bool sceneEnclosed = false;         // two planes face each other: (practically) no ray leaves the scene (k_bounce's shading pools stay off)
     int bvhMode = TINSEL_BVH_REFERENCE;
     int rrStart = 0;                    // > 0: Russian roulette from this bounce on (opt-in)
-    std::vector<void*> lbvhAllocs;
+    DevPool lbvhTrees;                  // the device-built mesh trees in force (set_mesh_bvh: one generation)
 
     int width = 0, height = 0;
+    // The accumulator every kernel and entry point reads: a VIEW.  It is accumOwn's buffer (tinsel_hip_init; look-ahead moves buffers between
+    // accumOwn, specFree and the shots), the caller's (tinsel_hip_init_external: accumOwn empty, nothing to free), or for one call the group's
+    // reduced frame (tinsel_hip_group_present).
     float4* accum = nullptr;
-    bool accumOwned = true;
+    DevBuf<float4> accumOwn;
 
     // sharded renders: accumulate tiles that have candidate paths of this shard (k_accumulate_tiled)
-    int* accTilesDev = nullptr;
+    DevBuf<int> accTilesDev;
     int accTilesCount = 0;
     int accTilesKey[6] = { 0, 0, 0, 0, 0, 0 };     // width, height, rank, world, shard tile, halo reach
 
     // display stage (tn_display.h): [0] filtered, [1] NLM means, [2] NLM output; sized width*height on first use
-    float4* display[3] = { nullptr, nullptr, nullptr };
-    size_t displayPixels = 0;
+    DevBuf<float4> display[3];
     const float4* presented = nullptr;
 
     // path batch buffers
     size_t batchSlots = 0;
     int batchNee = -1;
     int batchDepth = -1;
-    std::vector<void*> batchAllocs;
+    DevPool batchMem;
     PathState ps;
     QueueCtl ctl;
     int batchPipeline = -1;             // the pipeline the current batch buffers were allocated for
@@ -112,38 +114,53 @@ struct tinsel_hip
         uint32_t* walkList = nullptr;       // k_walk's / k_swalk's work list (k_seg_expand) and the prefix of the regions' front counts behind it
         uint32_t* segPrefix = nullptr;
         float4* walkRec = nullptr;          // k_walk's closest-hit records (tn_walk.h); batch-sized
-        // k_walk's stack entries beyond the LDS ones (tinsel_hip_tuning::walk_lds_stack): allocated by launch_walk on first use, freed with
-        // the renderer, not with the batch
-        uint32_t* walkOverflow = nullptr;
-        size_t walkOverflowCap = 0;
         uint32_t regions = 0, paths = 0;    // of the chunk last traced here: its regions and paths (tinsel_hip_queue_counts)
     } lane[2];
+    // k_walk's stack entries beyond the LDS ones (tinsel_hip_tuning::walk_lds_stack), by lane: grown by ensure_walk_overflow, freed with the
+    // renderer, not with the batch
+    DevBuf<uint32_t> walkOverflow[2];
     int lastLane = 0;                   // the lane of the chunk traced last
     int batchLanes = 1;                 // lanes allocated (1 or 2)
     size_t batchStateSlots = 0;         // path slots each lane holds (batchSlots: what ps.rad holds)
-    hipStream_t laneStream = nullptr;   // the second chunk's stream
-    hipEvent_t laneFork = nullptr, laneJoin = nullptr, accDone[2] = { nullptr, nullptr };
+    // the second chunk's stream and the events that order the two chunks: all of them or none (render_impl makes them in a local)
+    struct LaneSync
+    {
+        Stream stream;
+        Event fork, join, accDone;
+        int create() { return stream.create() || fork.create() || join.create() || accDone.create() ? -1 : 0; }
+    } laneSync;
     bool walkEnabled = true;                            // tinsel_hip_tuning::walk == 0: walk meshes inline in k_extend / k_shadow (A/B)
-    unsigned long long* walkProf = nullptr;             // developer-only (-DTN_WALK_PROF builds): section counters of k_walk
-    uint2* probeAlias = nullptr;                        // alias table of the probe (tinsel_hip_set_probe_sampling), built on first use
+    DevBuf<unsigned long long> walkProf;                // developer-only (-DTN_WALK_PROF builds): section counters of k_walk
+    DevBuf<uint2> probeAlias;                           // alias table of the probe (tinsel_hip_set_probe_sampling), built on first use
     int sharedMemLimit = 65536;
-    uint32_t* passSeedsDev = nullptr;   // the table: the seeds of passes [passSeedsBase, passSeedsBase + passSeedsCount)
-    size_t passSeedsCap = 0, passSeedsCount = 0;
+    DevBuf<uint32_t> passSeedsDev;      // the table: the seeds of passes [passSeedsBase, passSeedsBase + passSeedsCount)
+    size_t passSeedsCount = 0;
     uint32_t passSeedsBase = 0;
     const uint32_t* passSeeds = nullptr;    // the current call's first seed, inside the table
-    hipEvent_t passSeedsReady = nullptr;    // recorded behind the launch that wrote the table, on passSeedsStream
+    Event passSeedsReady;                   // recorded behind the launch that wrote the table, on passSeedsStream
     hipStream_t passSeedsStream = nullptr;
-    unsigned long long* statsDev = nullptr;
+    DevBuf<unsigned long long> statsDev;
     // ray queries (tinsel_hip_trace_rays / tinsel_hip_trace_camera): the host entries' chunk buffers, grown on demand, freed with the renderer
-    void* queryRaysDev = nullptr;
-    void* queryOutDev = nullptr;
-    size_t queryRaysCap = 0, queryOutCap = 0;   // bytes
+    DevBuf<unsigned char> queryRaysDev, queryOutDev;
     // k_query_refill's cursors: a ring of words, one per launch, and per word the event behind the launch that used it last (launch_query)
     static constexpr uint32_t kQueryCursors = 64;
-    uint32_t* queryCursorDev = nullptr;
-    hipEvent_t queryCursorDone[kQueryCursors] = {};
-    bool queryCursorUsed[kQueryCursors] = {};
-    uint32_t queryCursorNext = 0;
+    struct QueryCursors
+    {
+        DevBuf<uint32_t> words;
+        Event done[kQueryCursors];
+        bool used[kQueryCursors] = {};
+        uint32_t next = 0;
+        int create()
+        {
+            if (words.alloc(kQueryCursors))
+                return -1;
+            for (Event& e : done)
+                if (e.create())
+                    return -1;
+            return 0;
+        }
+    };
+    std::unique_ptr<QueryCursors> queryCursors;     // made whole by launch_query on first use
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)
@@ -164,17 +181,16 @@ struct tinsel_hip
     // call's running sum travels to the host
     int lookahead = 0;                  // 0 off, 1 on, 2 on + the caller's output array page-locked in place (TINSEL_LOOKAHEAD_PIN_OUTPUT)
     FrameParams lastFp;                 // of the most recent batch (its paths' radiance is still in ps.rad)
-    struct SpecShot { float4* buf; hipEvent_t ready; };
-    std::vector<float4*> specFree;      // accumulator-sized buffers not in use
+    struct SpecShot { DevBuf<float4> buf; Event ready; };
+    std::vector<DevBuf<float4>> specFree;      // accumulator-sized buffers not in use
     std::deque<SpecShot> specQueue;     // specQueue[j] = accum + the passes of the next j+1 calls, in flight or finished on workStream
     uint32_t specNextPass = 0;          // pass index the next speculated call starts at
     tinsel_camera specCamera;
     tinsel_options specOptions;
     int specPasses = 0;
     int lookaheadDepth = 0;             // calls per speculated batch; 0 = chosen from the batch capacity 
-    hipStream_t workStream = nullptr, copyStream = nullptr;
-    void* pinnedPtr = nullptr;          // caller's output buffer, page-locked in place (hipHostRegister) for the D2H DMA
-    size_t pinnedBytes = 0;
+    Stream workStream, copyStream;      // both or neither (lookahead_streams)
+    PinnedOutput pinned;                // the caller's output array, page-locked in place for the D2H DMA
 
     // process-per-GPU arm of the reduce (tinsel_hip_comm_*, tn_host_group.h): this rank's RCCL communicator
     void* comm = nullptr;               // ncclComm_t
@@ -182,6 +198,6 @@ struct tinsel_hip
 
     bool timing = false;
     std::vector<TimedSpan> spans;
-    std::vector<hipEvent_t> eventPool;
+    std::vector<Event> eventPool;       // timing events not in use: nothing is created or destroyed per launch once the pool is warm
     double gpuSeconds = 0.0;
 };
