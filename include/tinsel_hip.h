@@ -474,6 +474,11 @@ int tinsel_hip_nee_per_path(tinsel_hip* r);
 /* Primitives whose mesh BVH is walked by the dedicated k_walk kernel ahead of the scan kernels (large meshes in HBM,
  * split pipeline; tn_walk.h).  0: every mesh is walked inline, as IntersectRayMesh is called in the reference. */
 int tinsel_hip_walked_prims(tinsel_hip* r);
+/* Introspection: the Node64 records of each walked primitive's tree that k_walk's workgroups would stage into LDS under the tuning in
+ * force (the first records of its breadth-first top, tinsel_hip_mesh_tree's topCount at most): what is left of a workgroup's LDS beside
+ * the traversal stacks is handed out in primitive order, so a later primitive may get a part of its top, or none.
+ * out_counts[k]: the k-th walked primitive (primitive order).  Returns their number (<= 7), or -1 (capacity too small). */
+int tinsel_hip_walk_tops(tinsel_hip* r, int* out_counts, int capacity);
 /* Queue lengths of the LAST batch of the wavefront pipelines: out[b] = paths alive at the start of bounce b (entries of the
  * extension queue; bounce 0: the paths generated, tile padding of a shard included), out[max_bounces + b] = paths with
  * shadow rays at bounce b (split pipeline; 0 otherwise).  Synchronises.

@@ -117,6 +117,39 @@ def material(rng, name, emitter):
     return "\n".join(lines)
 
 
+def pose(rng, centre=None, spread=2.0, scale=(0.4, 1.8), moving=None):
+    """position / rotation / scale lines of a primitive.  The defaults are the fuzz corpus's own draws (the random stream of scene_text must not change:
+    the corpus file and the pinned seeds of tests/test_fuzz.py rest on it); tests/golden/make_mesh_scenes.py places its primitives with `centre`
+    (the position is drawn around it), `scale` (the range of the scale) and `moving` (None: drawn, a third move; True: the primitive moves AND turns
+    during the shutter; False: it stands still)"""
+    lines = []
+    p = rng.uniform(-spread, spread, 3)
+    if centre is not None:
+        p = p + np.asarray(centre, np.float64)
+    drawn = rng.random() < 0.33
+    if drawn if moving is None else moving:
+        lines.append("\tposition %s , %s" % (f3(p), f3(p + rng.uniform(-0.5, 0.5, 3))))
+    else:
+        lines.append("\tposition %s" % f3(p))
+    drawn = rng.random() < 0.6
+    if drawn if moving is None else True:
+        q = quat(rng)
+        drawn = rng.random() < 0.3
+        if moving:
+            e = q + 0.15*rng.normal(size=4)                 # (a turn of some ten degrees: a whole random turn would smear the mesh over the frame)
+            lines.append("\trotation %s , %s" % (f4(q), f4(e/np.linalg.norm(e))))
+        elif drawn and moving is None:
+            lines.append("\trotation %s , %s" % (f4(q), f4(quat(rng))))
+        else:
+            lines.append("\trotation %s" % f4(q))
+    s = float(rng.uniform(scale[0], scale[1]))
+    if rng.random() < 0.25 and moving is not False:
+        lines.append("\tscale %.6g , %.6g" % (s, s*float(rng.uniform(0.7, 1.4))))
+    elif rng.random() < 0.6 or moving is not None:
+        lines.append("\tscale %.6g" % s)
+    return lines
+
+
 def primitive(rng, kind, mat, light_samples):
     lines = ["primitive", "{", "\ttype %s" % ("mesh" if kind in ("quad", "tetra", "wedge") else kind)]
     if kind == "plane":
@@ -126,22 +159,7 @@ def primitive(rng, kind, mat, light_samples):
         n = n/np.linalg.norm(n)
         lines.append("\tplane %s %.6g" % (f3(n), float(rng.uniform(0.5, 3.0))))
     else:
-        p = rng.uniform(-2.0, 2.0, 3)
-        if rng.random() < 0.33:
-            lines.append("\tposition %s , %s" % (f3(p), f3(p + rng.uniform(-0.5, 0.5, 3))))
-        else:
-            lines.append("\tposition %s" % f3(p))
-        if rng.random() < 0.6:
-            q = quat(rng)
-            if rng.random() < 0.3:
-                lines.append("\trotation %s , %s" % (f4(q), f4(quat(rng))))
-            else:
-                lines.append("\trotation %s" % f4(q))
-        s = float(rng.uniform(0.4, 1.8))
-        if rng.random() < 0.25:
-            lines.append("\tscale %.6g , %.6g" % (s, s*float(rng.uniform(0.7, 1.4))))
-        elif rng.random() < 0.6:
-            lines.append("\tscale %.6g" % s)
+        lines += pose(rng)
         if kind == "sphere":
             lines.append("\tradius %.6g" % float(rng.uniform(0.2, 1.0)))
         else:

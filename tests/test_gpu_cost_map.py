@@ -11,12 +11,16 @@ import pytest
 from tinsel_amd import abi
 from tests import oracle_api as oa
 
-SCENES = ["cornell", "features", "many_spheres", "motionblur", "glass", "ajax_standin_96", "fuzz:03", "fuzz:11", "fuzz:24"]
+# (mesh:...: generated mesh-heavy scenes, tests/golden/make_mesh_scenes.py -- 12 meshes of 9 ... 5,000 triangles; 80 primitives, 3 of them meshes)
+SCENES = ["cornell", "features", "many_spheres", "motionblur", "glass", "ajax_standin_96", "fuzz:03", "fuzz:11", "fuzz:24", "mesh:twelve:1", "mesh:beyond_flat:1"]
 KEYS = ("rays", "internal_visits", "tri_tests", "prim_tests")
 THREADS = 16
 
 
 def _pack(name):
+    if name.startswith("mesh:"):
+        from tests.test_gpu_mesh_scenes import pack_bytes
+        return pack_bytes(name)
     if name.startswith("fuzz:"):
         return bytes(np.load(os.path.join(oa.GOLDEN, "fuzz.golden.npz"))["pack_" + name[5:]].tobytes())
     with open(os.path.join(oa.GOLDEN, name + ".pack"), "rb") as fh:

@@ -37,6 +37,9 @@ and `box`: the rays whose minimum the restriction to reached leaves changes at a
     fuzz:27          hit   4610  ties     0  dot   0  box   0     fuzz:28          hit  37554  ties     0  dot   0  box   0
     fuzz:29          hit  35925  ties     0  dot   0  box   0     fuzz:30          hit   4848  ties     0  dot   0  box   0
     fuzz:31          hit  48069  ties     0  dot   0  box   0
+and the generated mesh-heavy scenes (tests/golden/make_mesh_scenes.py, made by the reference's loader at test time):
+    mesh:seven:1        hit  35515  ties     0  dot   1  box   0     mesh:twelve:1       hit  36366  ties     0  dot   0  box   0
+    mesh:instances:1    hit  36273  ties     0  dot   0  box   0     mesh:beyond_flat:1  hit  69798  ties     0  dot   0  box   0
 """
 import ctypes as C
 import os
@@ -53,13 +56,19 @@ pytestmark = pytest.mark.gpu
 needs_ref = pytest.mark.skipif(not oa.have_ref(), reason="oracle/_ref not built")
 
 NAMED = ["cornell", "glass", "veach", "features", "motionblur", "many_spheres", "ajax_standin_96"]
-SCENES = NAMED + ["fuzz:%02d" % k for k in range(32)]
+# generated mesh-heavy scenes (tests/golden/make_mesh_scenes.py, made by the reference's loader at test time): 7 walked meshes, 12 meshes, 16 instances of 2
+# meshes with moving poses, 80 primitives beyond the flat scan
+MESH_SCENES = ["mesh:seven:1", "mesh:twelve:1", "mesh:instances:1", "mesh:beyond_flat:1"]
+SCENES = NAMED + ["fuzz:%02d" % k for k in range(32)] + MESH_SCENES
 N_RANDOM, N_AXIS, N_SURFACE = 65536, 4096, 4096
 FLT_MAX = np.float32(3.4028234663852886e38)
 CAP = 0.01
 
 
 def _pack(name):
+    if name.startswith("mesh:"):
+        from tests.test_gpu_mesh_scenes import pack_bytes
+        return pack_bytes(name)
     if name.startswith("fuzz:"):
         return bytes(np.load(os.path.join(oa.GOLDEN, "fuzz.golden.npz"))["pack_" + name[5:]].tobytes())
     with open(os.path.join(oa.GOLDEN, name + ".pack"), "rb") as fh:
@@ -447,7 +456,7 @@ def test_a_query_changes_nothing_else():
 # ---------------------------------------------------------------------------
 # 6: independence of configuration
 
-@pytest.mark.parametrize("name", ["cornell", "glass", "ajax_standin_96", "many_spheres"])
+@pytest.mark.parametrize("name", ["cornell", "glass", "ajax_standin_96", "many_spheres"] + MESH_SCENES)
 def test_same_bytes_under_every_configuration(name):
     import tinsel_amd
     scene, r = _renderer(name)

@@ -640,6 +640,20 @@ int tinsel_hip_mesh_tree(tinsel_hip* r, int primitive, void* out_nodes, int capa
 int tinsel_hip_walked_prims(tinsel_hip* r) { return (r && r->walkEnabled) ? r->walkPrims.count : 0; }
 int tinsel_hip_nee_per_path(tinsel_hip* r) { return r ? r->neePerPath : 0; }
 
+int tinsel_hip_walk_tops(tinsel_hip* r, int* out_counts, int capacity)
+{
+    if (!r || !out_counts || capacity < 0)
+        return fail("walk_tops: bad arguments");
+    const int n = r->walkEnabled ? r->walkPrims.count : 0;
+    if (capacity < n)
+        return fail("walk_tops: capacity is smaller than the number of walked primitives");
+    // (plan_walk reads the scene and the tuning in force: what the next render's k_walk launches stage)
+    const WalkPlan w = plan_walk(r);
+    for (int k = 0; k < n; ++k)
+        out_counts[k] = w.job.topCount[k];
+    return n;
+}
+
 int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces)
 {
     if (!r || !out || max_bounces < 1)
