@@ -214,6 +214,7 @@ typedef struct tinsel_hip_tuning {
     int32_t walk_leaf_min;      /* 0 default (8) | lanes waiting at a leaf that trigger k_walk's triangle phase */
     int32_t walk_grid_mult;     /* 0 default (1) | k_walk's grid in resident sets of workgroups: each workgroup a contiguous 1/grid of the work list */
     int32_t quads_in_scan;      /* -1 auto | 0: a quad (two-triangle mesh: a lamp) beside meshes walked by k_walk sends the scene to the general scan kernels (inline mesh walk compiled in) */
+    int32_t bounce_fit;         /* -1 auto | 0: k_bounce's general instance even where one compiled for the scene's feature set exists */
 } tinsel_hip_tuning;
 enum { TINSEL_ACCUMULATE_AUTO = 0, TINSEL_ACCUMULATE_TILED = 1, TINSEL_ACCUMULATE_WIDE = 2, TINSEL_ACCUMULATE_PIPED = 3 };
 
@@ -484,6 +485,15 @@ int tinsel_hip_walk_tops(tinsel_hip* r, int* out_counts, int capacity);
  * shadow rays at bounce b (split pipeline; 0 otherwise).  Synchronises.
  * Returns the number of bounces written (<= max_bounces), or -1. */
 int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces);
+/* The fused kernel's last launch: out[0] = the instance's kind (0 general, 1 general with detail counters, 2 closed static scene,
+ * 3 deferred mesh walks with pools / sharing / sorted queues), out[1] = the feature bits the
+ * scene and the plan asked for (TINSEL_BOUNCE_*).  Returns 0, or -1 when the renderer has not launched k_bounce yet. */
+int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2);
+/* The SCENE's share of those bits (media, probe, motion, mesh walk, sphere, transmission) from a scene description alone: no device, no
+ * renderer.  What a renderer created from `scene` with the default tuning reports until a primitive is moved or a mesh tree rebuilt. */
+unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene);
+enum { TINSEL_BOUNCE_MEDIA = 1, TINSEL_BOUNCE_PROBE = 2, TINSEL_BOUNCE_MOTION = 4, TINSEL_BOUNCE_MESH_WALK = 8, TINSEL_BOUNCE_SPHERE = 16,
+       TINSEL_BOUNCE_TRANSMISSION = 32, TINSEL_BOUNCE_POOLS = 64, TINSEL_BOUNCE_SHARE = 128, TINSEL_BOUNCE_SORT = 256, TINSEL_BOUNCE_ROULETTE = 512 };
 
 const char* tinsel_hip_last_error(void);
 
@@ -631,7 +641,7 @@ static_assert(sizeof(tinsel_filter) == 16, "Filter");
 static_assert(sizeof(tinsel_options) == 48, "Options");
 static_assert(offsetof(tinsel_options, max_depth) == 40, "Options.maxDepth");
 static_assert(sizeof(tinsel_pack_header) == 256, "pack header");
-static_assert(sizeof(tinsel_hip_tuning) == 120, "tuning");
+static_assert(sizeof(tinsel_hip_tuning) == 128, "tuning");
 static_assert(sizeof(tinsel_ray) == 32, "ray");
 static_assert(sizeof(tinsel_ray_hit) == 32, "ray hit");
 #endif

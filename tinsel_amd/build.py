@@ -119,6 +119,41 @@ def _parse_resources(text):
     return out
 
 
+def _code_bytes(device_obj):
+    """{kernel: bytes of machine code} of a device-only object (a gfx950 ELF64): the size of each kernel's function symbol, read from
+    the symbol table directly (no binutils needed)."""
+    import struct
+    with open(device_obj, "rb") as f:
+        b = f.read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    if b.startswith(magic):             # hipcc wraps the code object: [magic][count] then (offset, size, triple length, triple) per entry
+        count, = struct.unpack_from("<Q", b, len(magic))
+        pos = len(magic) + 8
+        for _ in range(count):
+            off, size, tlen = struct.unpack_from("<QQQ", b, pos)
+            triple = b[pos + 24:pos + 24 + tlen]
+            pos += 24 + tlen
+            if b"gfx950" in triple:
+                b = b[off:off + size]
+                break
+    if b[:6] != b"\x7fELF\x02\x01":
+        return {}
+    shoff, = struct.unpack_from("<Q", b, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", b, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + k*shentsize) for k in range(shnum)]
+    out = {}
+    for name, kind, flags, addr, off, size, link, info, align, entsize in sections:
+        if kind != 2:                   # SHT_SYMTAB
+            continue
+        stroff = sections[link][4]
+        for k in range(size//entsize):
+            st_name, st_info, st_other, st_shndx, st_value, st_size = struct.unpack_from("<IBBHQQ", b, off + k*entsize)
+            if (st_info & 15) == 2 and st_shndx != 0:       # STT_FUNC, defined
+                end = b.index(b"\0", stroff + st_name)
+                out[_kernel_name(b[stroff + st_name:end].decode())] = st_size
+    return out
+
+
 def _link(obj_dir, out, verbose=True):
     link = [hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out, os.path.join(obj_dir, "tinsel_hip.o"), os.path.join(obj_dir, "tinsel_fast.o")]
     if verbose:
@@ -154,6 +189,9 @@ def build_verified(verbose=True):
         _compile(tmp, (), verbose)
         res_err = res_proc.communicate()[1]
         resources = _parse_resources(res_err) if res_proc.returncode == 0 else {}
+        for name, size in (_code_bytes(os.path.join(tmp, "resources_only.o")) if resources else {}).items():
+            if name in resources:
+                resources[name]["code_bytes"] = size
         fresh = {n: _sha(os.path.join(tmp, n)) for n in names}
         have = {n: (_sha(os.path.join(OBJ_DIR, n)) if os.path.exists(os.path.join(OBJ_DIR, n)) else None) for n in names}
         same = all(fresh[n] == have[n] for n in names) and os.path.exists(OUT) and \

@@ -95,9 +95,27 @@ TN_D void pool_load(const uint32_t* pool, uint32_t e, PathRegs& p, uint32_t& slo
 // and the offsetof() of the late reads below cannot drift from what the launch lays out (the struct used to mirror a parameter
 // list by hand).
 struct BounceKernargs { DevScene scIn; SplitState ss; QueueCtl q; int bounceBegin, bounceEnd, stackEntries; CameraParams cam; FrameParams fp; const uint32_t* passSeeds; };
-template <bool COUNT, bool LDS, bool DEFER>
+
+// k_bounce's instances by KIND.  0: the general kernel, every BounceFeature (tn_scene.h) tested at run time; 1: the same with the detail
+// counters.  2 and up: FIT instances, compiled for the feature set below -- a test of a feature outside the set is decided at compile time,
+// so its code and the scalars it keeps live through the round loop are not in the instance.  The host launches a FIT instance only for a
+// scene and a plan whose features lie inside its set (plan_batch, tn_host_batch.h); everything else runs the general kernel.  Which sets:
+// what the fused scenes of BASELINE.md ask for -- the closed static box (cornell) and the open scene with deferred mesh walks, pools,
+// sharing and sorted queues (veach).  (A third one, the closed box with shared regions for small batches of cornell, did not clearly beat
+// the general kernel at 256^2 and is not compiled: profiles/r09_bounce_fit_icache.md.)
+enum BounceKind : int { kBounceGeneral = 0, kBounceCount = 1, kBounceFitClosed = 2, kBounceFitDeferred = 3 };
+constexpr uint32_t bounce_kind_features(int kind)
+{
+    return kind == kBounceFitClosed ? (uint32_t)kFeatSphere :
+           kind == kBounceFitDeferred ? (uint32_t)(kFeatSphere | kFeatPools | kFeatShare | kFeatSort) : (uint32_t)kFeatAll;
+}
+
+template <int KIND, bool LDS, bool DEFER>
 __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs ka)
 {
+    constexpr bool COUNT = KIND == kBounceCount;
+    constexpr uint32_t FEAT = bounce_kind_features(KIND);
+    typedef SceneT<LDS, false, DEFER ? 1 : 0, false, FEAT> SC;
     const DevScene& scIn = ka.scIn;
     const SplitState& ss = ka.ss;
     const QueueCtl& q = ka.q;
@@ -109,11 +127,22 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
     LdsStack<kBlock> st = { s_stack + threadIdx.x };
 
     // LDS: [stackEntries][kBlock] stack words, kScanWords, (fp.repack) the waves' shading pools, the staged arena
-    const bool repack = fp.repack != 0;
+    const bool repack = (FEAT & kFeatPools) && fp.repack != 0;
+    const bool shareRegions = (FEAT & kFeatShare) && fp.share != 0;
     const uint32_t wave = wave_in_block();
     uint32_t* const pool = s_stack + stackEntries*kBlock + kScanWords + wave*kPoolWordsPerWave;
-    SceneT<LDS, false, DEFER ? 1 : 0> sc;
+    SC sc;
     stage_scene_lds(sc, scIn, s_stack + stackEntries*kBlock + kScanWords + (repack ? kPoolWords : 0));
+    // (a FIT instance: what its scenes do not have, as constants)
+    if constexpr (!(FEAT & kFeatMedia)) sc.hasMedia = 0;
+    if constexpr (!(FEAT & kFeatProbe)) sc.probe.valid = 0;
+    if constexpr (!(FEAT & kFeatSort)) sc.sortQueues = 0;
+    if constexpr (KIND >= kBounceFitClosed) sc.flatScan = 1;        // (the host plans a FIT instance for flat-scan scenes only)
+    auto mat_at = [&](int prim) {
+        Mat m = load_mat(sc.mats, prim);
+        if constexpr (!(FEAT & kFeatTransmission)) m.transmission = 0.0f;       // (the value every material of its scenes holds)
+        return m;
+    };
     // the path state's pointers (ten of them and the radiance array: 22 SGPRs that a round needs for a dozen instructions at its start
     // and its end) from the kernel-argument segment where they are used: `ssIn(buf)` what load_state reads of buffer `buf`, `ssOut(buf)`
     // what store_state writes, `radOutNow()` the radiance array of finished paths
@@ -139,7 +168,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
         asm volatile("" : "+s"(sp));
         DevScene s;
         s.probe.data = sp->probe.data; s.probe.pdfX = sp->probe.pdfX; s.probe.cdfX = sp->probe.cdfX; s.probe.pdfY = sp->probe.pdfY; s.probe.cdfY = sp->probe.cdfY;
-        s.probe.width = sp->probe.width; s.probe.height = sp->probe.height; s.probe.valid = sp->probe.valid; s.probe.alias = sp->probe.alias;
+        s.probe.width = sp->probe.width; s.probe.height = sp->probe.height; s.probe.valid = (FEAT & kFeatProbe) ? sp->probe.valid : 0; s.probe.alias = sp->probe.alias;
         for (int c = 0; c < 3; ++c)
         {
             s.horizon[c] = sp->horizon[c];
@@ -170,7 +199,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
         {
             // this workgroup's stores of the previous bounce (path state, region counts) before this bounce's loads
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (fp.share)
+            if (shareRegions)
                 __syncthreads();        // its waves read each other's regions (`share` below); wave-uniform for the whole grid
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
@@ -179,7 +208,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
         // stream, dealt to its waves round by round.  A workgroup holds its LDS and its wave slots until its last wave ends;
         // where a round is long (veach: 4 shadow traces, features: 9) its waves drift apart unless they share (veach 1409 ->
         // 1457 Msamples/s, features 685 -> 712); where rounds are short the dealing costs more than it gives (env_loft, gloss -2 %)
-        const bool share = !FIRST && fp.share != 0;
+        const bool share = !FIRST && shareRegions;
         uint32_t gF[kRegionsPerBlock], gStart[kRegionsPerBlock];
         if (FIRST)
         {
@@ -267,7 +296,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
             if (have)
             {
                 TN_TICK(0)
-                prim = trace<SceneT<LDS, false, DEFER ? 1 : 0>, LdsStack<kBlock>, COUNT>(sc, st, p.o, p.d, p.time, t, n3, ctr);
+                prim = trace<SC, LdsStack<kBlock>, COUNT>(sc, st, p.o, p.d, p.time, t, n3, ctr);
                 rays++;
                 TN_TICK(1)
                 if (prim < 0)
@@ -309,7 +338,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
             {
                 {
                     const V3 n = n3;
-                    const Mat mat = load_mat(sc.mats, prim);
+                    const Mat mat = mat_at(prim);
                     HitCtx h;
                     on_hit_begin(p, mat, t, n, bounce, h, prim);
 
@@ -332,17 +361,17 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                             TN_TICK(2)
                             float ts;
                             V3 nn;
-                            const int hp = trace<SceneT<LDS, false, DEFER ? 1 : 0>, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, ctr);
+                            const int hp = trace<SC, LdsStack<kBlock>, COUNT>(sc, st, g.o, g.wi, p.time, ts, nn, ctr);
                             TN_TICK(3)
                             rays++;
                             shadowRays++;
                             // the BSDF terms only for the samples that arrive; the 28-register material record is re-read here
                             // instead of living across the shadow trace
                             if (light < 0)
-                                return (hp < 0) ? nee_contrib_probe(load_mat(sc.mats, prim), h, g.wi, skyColor, skyPdf) : V3(0.0f);
+                                return (hp < 0) ? nee_contrib_probe(mat_at(prim), h, g.wi, skyColor, skyPdf) : V3(0.0f);
                             if (!nee_light_reached(g, hp, ts))
                                 return V3(0.0f);
-                            return nee_contrib_light(sc, load_mat(sc.mats, prim), h, g.wi, g.nl, light, hp, ts);
+                            return nee_contrib_light(sc, mat_at(prim), h, g.wi, g.nl, light, hp, ts);
                         });
                         p.rad = p.rad + thrAtNee*sum;
                     }
@@ -352,9 +381,9 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     if (bounce + 1 < fp.maxDepth)
                     {
                         // the material is read again rather than kept in 28 registers across the shadow traces
-                        const Mat matAgain = load_mat(sc.mats, prim);
+                        const Mat matAgain = mat_at(prim);
                         alive = (bsdf_step(p, matAgain, h) == kContinue);
-                        if (alive && fp.rrStart > 0 && bounce + 1 >= fp.rrStart)
+                        if ((FEAT & kFeatRoulette) && alive && fp.rrStart > 0 && bounce + 1 >= fp.rrStart)
                             alive = roulette_survives(p);
                     }
                 }

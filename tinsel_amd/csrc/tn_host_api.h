@@ -654,6 +654,42 @@ int tinsel_hip_walk_tops(tinsel_hip* r, int* out_counts, int capacity)
     return n;
 }
 
+unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene)
+{
+    if (!scene || !scene->primitives)
+        return 0u;
+    uint32_t f = scene->probe_valid ? kFeatProbe : 0u;
+    for (int i = 0; i < scene->num_primitives; ++i)
+    {
+        const tinsel_primitive& p = scene->primitives[i];
+        const tinsel_material& m = p.material;
+        f |= (m.absorption.x != 0.0f || m.absorption.y != 0.0f || m.absorption.z != 0.0f) ? kFeatMedia : 0u;
+        f |= m.transmission != 0.0f ? kFeatTransmission : 0u;
+        f |= memcmp(&p.start_transform, &p.end_transform, sizeof(tinsel_transform)) != 0 ? kFeatMotion : 0u;
+        f |= p.type == TINSEL_GEOM_SPHERE ? kFeatSphere : 0u;
+        if (p.type == TINSEL_GEOM_MESH)
+        {
+            // one internal node over two leaves (a quad) is tested without the stack walk (DevMesh::twoLeaves, ray_mesh_two_leaves)
+            const tinsel_bvh_node* n = p.geo.mesh.nodes;
+            const bool twoLeaves = n && p.geo.mesh.num_nodes == 3 && !ref_is_leaf(n[0]) && n[0].left_index < 3u && ref_right(n[0]) < 3u &&
+                                   ref_is_leaf(n[n[0].left_index]) && ref_is_leaf(n[ref_right(n[0])]);
+            f |= twoLeaves ? 0u : kFeatMeshWalk;
+        }
+    }
+    return f;
+}
+
+int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2)
+{
+    if (!r || !out2)
+        return fail("bounce_plan: bad arguments");
+    if (r->lastBounceKind < 0)
+        return fail("bounce_plan: the fused kernel has not run yet");
+    out2[0] = (uint32_t)r->lastBounceKind;
+    out2[1] = r->lastBounceFeatures;
+    return 0;
+}
+
 int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces)
 {
     if (!r || !out || max_bounces < 1)

@@ -435,6 +435,39 @@ bool plan_bounce(const tinsel_hip* r, int* resident)
     return pools;
 }
 
+// What the scene as it is now and a render's plan ask of the fused kernel (BounceFeature, tn_scene.h), but for kFeatShare, which the cut of
+// each batch decides (trace_fused).  Derived for every render call, from what the host holds of the scene in force: a moved primitive, a
+// rebuilt mesh tree, another tuning or roulette setting cannot leave a stale set behind.
+uint32_t bounce_features(const tinsel_hip* r, bool pools)
+{
+    uint32_t f = 0;
+    f |= r->scene.hasMedia ? kFeatMedia : 0u;
+    f |= r->scene.probe.valid ? kFeatProbe : 0u;
+    f |= r->anyTransmission ? kFeatTransmission : 0u;
+    f |= r->scene.sortQueues ? kFeatSort : 0u;
+    f |= pools ? kFeatPools : 0u;
+    f |= r->rrStart > 0 ? kFeatRoulette : 0u;
+    for (size_t i = 0; i < r->primsHost.size(); ++i)
+    {
+        const Prim64& p = r->primsHost[i];
+        f |= (p.flags & kPrimMoving) ? kFeatMotion : 0u;
+        f |= p.type == (uint32_t)kPrimSphere ? kFeatSphere : 0u;
+        const int m = i < r->primMesh.size() ? r->primMesh[i] : -1;
+        if (p.type == (uint32_t)kPrimMesh && !(p.flags & kPrimQuadArena) && !(m >= 0 && r->meshesNow[(size_t)m].twoLeaves))
+            f |= kFeatMeshWalk;
+    }
+    return f;
+}
+
+// the FIT instance of k_bounce (tn_launch.h) for a scene whose features are `need`, PK_NONE where none is compiled for them
+int fit_bounce(uint32_t need, bool deferMeshes)
+{
+    auto within = [&](int kind) { return (need & ~bounce_kind_features(kind)) == 0u; };
+    if (deferMeshes)
+        return within(kBounceFitDeferred) ? PK_BOUNCE_FIT_DEFERRED : PK_NONE;
+    return within(kBounceFitClosed) ? PK_BOUNCE_FIT_CLOSED : PK_NONE;
+}
+
 // k_walk's launches of a render call (plan_walk): instance, workgroup, workgroups per CU, dynamic LDS, the job's fixed part
 struct WalkPlan
 {
@@ -554,6 +587,10 @@ struct BatchPlan
     RegionSpec regions;                 // how a batch is cut (render_batch bounds it by the lane's arrays)
     // the instance of each launch (tn_launch.h; PK_NONE: not launched -- k_lights where k_extend draws the light samples)
     int generate = PK_GENERATE, extend = PK_NONE, shadow = PK_NONE, lights = PK_NONE, shade = PK_NONE, step = PK_NONE, bounce = PK_NONE, mega = PK_NONE;
+    // fused: the features asked of k_bounce (bounce_features), and its instance for a batch whose cut shares a workgroup's regions
+    // (FrameParams::share, the one feature a batch's length decides: trace_fused takes `bounce` or `bounceShared`, nothing else)
+    uint32_t bounceFeatures = 0;
+    int bounceShared = PK_NONE;
     WalkPlan walkPlan;                  // where `walk`
     SwalkPlan swalkPlan;                // where `sceneWalk`
 };
@@ -657,6 +694,19 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     p.shade = sorted ? (mixedShade ? PK_SHADE_SORTED_MIXED : lds ? PK_SHADE_SORTED_LDS : PK_SHADE_SORTED) : (mixedShade ? PK_SHADE_MIXED : lds ? PK_SHADE_LDS : PK_SHADE);
     // (the detail-counting variants walk the scene BVH: nothing to defer)
     p.bounce = count ? (lds ? PK_BOUNCE_COUNT_LDS : PK_BOUNCE_COUNT) : r->scene.deferMeshes ? (lds ? PK_BOUNCE_LDS_DEFER : PK_BOUNCE_DEFER) : lds ? PK_BOUNCE_LDS : PK_BOUNCE;
+    p.bounceShared = p.bounce;
+    if (fused)
+    {
+        // a FIT instance where one is compiled for what the scene and the plan ask for (the whole scene in LDS, the flat scan, no detail
+        // counters: what every fused BASELINE scene is); tinsel_hip_tuning::bounce_fit = 0: the general kernel (parity tests, A/B)
+        p.bounceFeatures = bounce_features(r, p.pools);
+        if (lds && !count && r->scene.flatScan && r->tune.bounce_fit != 0)
+        {
+            const int alone = fit_bounce(p.bounceFeatures, r->scene.deferMeshes != 0), shared = fit_bounce(p.bounceFeatures | kFeatShare, r->scene.deferMeshes != 0);
+            p.bounce = alone != PK_NONE ? alone : p.bounce;
+            p.bounceShared = shared != PK_NONE ? shared : p.bounceShared;
+        }
+    }
     p.mega = count ? (lds ? PK_MEGA_COUNT_LDS : PK_MEGA_COUNT) : lds ? PK_MEGA_LDS : PK_MEGA;
     p.walkPlan = p.walk ? plan_walk(r) : WalkPlan();
     p.swalkPlan = p.sceneWalk ? plan_swalk(r) : SwalkPlan();
@@ -1060,7 +1110,11 @@ int trace_fused(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     a.bounce = 0;
     a.bounceEnd = a.fp.maxDepth;
     a.order = nullptr;
-    a.variant = p.bounce;
+    a.variant = a.fp.share ? p.bounceShared : p.bounce;
+    r->lastBounceKind = a.variant == PK_BOUNCE_FIT_CLOSED ? kBounceFitClosed :
+                        a.variant == PK_BOUNCE_FIT_DEFERRED ? kBounceFitDeferred :
+                        (a.variant == PK_BOUNCE_COUNT_LDS || a.variant == PK_BOUNCE_COUNT) ? kBounceCount : kBounceGeneral;
+    r->lastBounceFeatures = p.bounceFeatures | (a.fp.share ? kFeatShare : 0u);
     ScopedTimer t(r, KN_BOUNCE, st);
     return launch_path(r, a, st);
 }

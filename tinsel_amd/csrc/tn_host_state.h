@@ -17,7 +17,7 @@ inline tinsel_hip_tuning tuning_defaults()
     t.tail_divide = 4;
     t.accumulate = TINSEL_ACCUMULATE_AUTO;
     t.walk_block = 0;
-    t.walk_single = t.walk_lds_stack = t.quads_in_scan = -1;
+    t.walk_single = t.walk_lds_stack = t.quads_in_scan = t.bounce_fit = -1;
     t.walk_refill_min = t.walk_leaf_min = t.walk_grid_mult = 0;
     return t;
 }
@@ -72,6 +72,9 @@ struct tinsel_hip
     bool sceneEnclosed = false;         // two planes face each other: (practically) no ray leaves the scene (k_bounce's shading pools stay off)
     int bvhMode = TINSEL_BVH_REFERENCE;
     int rrStart = 0;                    // > 0: Russian roulette from this bounce on (opt-in)
+    bool anyTransmission = false;       // a material has a transmission lobe (materials never change after create)
+    int lastBounceKind = -1;            // k_bounce's last launch: its kind (tn_fused.h BounceKind) and the features asked of it (tinsel_hip_bounce_plan)
+    uint32_t lastBounceFeatures = 0;
     DevPool lbvhTrees;                  // the device-built mesh trees in force (set_mesh_bvh: one generation)
 
     int width = 0, height = 0;

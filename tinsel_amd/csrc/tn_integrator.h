@@ -134,7 +134,9 @@ struct NeeGeo
 template <class SC>
 TN_D void primitive_sample(const SC& sc, int index, float time, V3& pos, V3& normal, Rng& rng)
 {
-    const Prim64 p = load_prim(sc.prims, index);
+    Prim64 p = load_prim(sc.prims, index);
+    if constexpr (!(SC::kFeatures & kFeatMotion))
+        p.flags &= ~(uint32_t)kPrimMoving;
     const Xform x = prim_pose(sc, p, time);
 
     if (p.type == kPrimSphere)

@@ -391,7 +391,9 @@ TN_D bool prim_intersect(const SC& sc, int index, Stack& st, int sp, V3 o, V3 d,
                          V3 rcpWorld = V3(0.0f), bool haveRcpWorld = false, const Prim64* fetched = nullptr)
 {
     // (`fetched`: the flat scan's record, requested together with the leaf box)
-    const Prim64 p = fetched ? *fetched : UNIFORM ? load_prim_uniform(sc.kPrims, index) : load_prim(sc.prims, index);
+    Prim64 p = fetched ? *fetched : UNIFORM ? load_prim_uniform(sc.kPrims, index) : load_prim(sc.prims, index);
+    if constexpr (!(SC::kFeatures & kFeatMotion))
+        p.flags &= ~(uint32_t)kPrimMoving;      // (no primitive of the scene moves: the interpolated pose is not compiled in)
     if (COUNT) ctr.prims++;
 
     if (p.type == kPrimPlane)
@@ -455,8 +457,8 @@ TN_D bool prim_intersect(const SC& sc, int index, Stack& st, int sp, V3 o, V3 d,
         if (!ray_mesh_two_leaves<COUNT>(mesh_nodes(sc, m), mtris, m.root, lo, ld, lrcp, h, ctr))
             return false;
     }
-    else if (SC::kWalkedOnly)
-        return false;               // (the host runs these variants only where every other mesh is walked by k_walk)
+    else if (SC::kWalkedOnly || !(SC::kFeatures & kFeatMeshWalk))
+        return false;               // (the host runs these variants only where every other mesh is walked by k_walk / no mesh needs the walk)
     else if (!ray_mesh<Stack, COUNT, ANYHIT>(mesh_nodes(sc, m), mtris, m.root, st, sp, lo, ld, lrcp, h, ctr, tStop))
         return false;
     }

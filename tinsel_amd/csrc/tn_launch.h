@@ -16,7 +16,7 @@
 namespace tn {
 
 // Every path-kernel instance the host launches: id, workgroup, 1 where create raises its dynamic-LDS limit, arguments, instance (in code-object
-// order).  COUNT: detail counters; LDS: the whole scene in LDS; MIXED: the arena staged, meshes in HBM; W1 / W2: walked_only_level.
+// order).  COUNT: detail counters; FIT: k_bounce compiled for a fixed feature set (tn_fused.h); LDS: the whole scene in LDS; MIXED: the arena staged, meshes in HBM; W1 / W2: walked_only_level.
 #define TN_PATH_KERNELS(X)                                                                                          \
     X(PK_GENERATE,              kBlock, 0, GENERATE, k_generate)                                                    \
     X(PK_EXTEND_W2_MIXED,       kBlock, 0, EXTEND,   k_extend<false, true, 2, true>)                                \
@@ -51,12 +51,14 @@ namespace tn {
     X(PK_SHADE_MIXED,           kBlock, 0, SHADE,    k_shade<true, true>)                                           \
     X(PK_SHADE_LDS,             kBlock, 0, SHADE,    k_shade<true>)                                                 \
     X(PK_SHADE,                 kBlock, 0, SHADE,    k_shade<false>)                                                \
-    X(PK_BOUNCE_COUNT_LDS,      kBlock, 1, BOUNCE,   k_bounce<true, true, false>)                                   \
-    X(PK_BOUNCE_COUNT,          kBlock, 1, BOUNCE,   k_bounce<true, false, false>)                                  \
-    X(PK_BOUNCE_LDS_DEFER,      kBlock, 1, BOUNCE,   k_bounce<false, true, true>)                                   \
-    X(PK_BOUNCE_DEFER,          kBlock, 1, BOUNCE,   k_bounce<false, false, true>)                                  \
-    X(PK_BOUNCE_LDS,            kBlock, 1, BOUNCE,   k_bounce<false, true, false>)                                  \
-    X(PK_BOUNCE,                kBlock, 1, BOUNCE,   k_bounce<false, false, false>)                                 \
+    X(PK_BOUNCE_COUNT_LDS,      kBlock, 1, BOUNCE,   k_bounce<kBounceCount, true, false>)                           \
+    X(PK_BOUNCE_COUNT,          kBlock, 1, BOUNCE,   k_bounce<kBounceCount, false, false>)                          \
+    X(PK_BOUNCE_LDS_DEFER,      kBlock, 1, BOUNCE,   k_bounce<kBounceGeneral, true, true>)                          \
+    X(PK_BOUNCE_DEFER,          kBlock, 1, BOUNCE,   k_bounce<kBounceGeneral, false, true>)                         \
+    X(PK_BOUNCE_LDS,            kBlock, 1, BOUNCE,   k_bounce<kBounceGeneral, true, false>)                         \
+    X(PK_BOUNCE,                kBlock, 1, BOUNCE,   k_bounce<kBounceGeneral, false, false>)                        \
+    X(PK_BOUNCE_FIT_CLOSED,     kBlock, 1, BOUNCE,   k_bounce<kBounceFitClosed, true, false>)                       \
+    X(PK_BOUNCE_FIT_DEFERRED,   kBlock, 1, BOUNCE,   k_bounce<kBounceFitDeferred, true, true>)                      \
     X(PK_STEP_W2_MIXED,         kBlock, 0, STEP,     k_step<true, 2, true>)                                         \
     X(PK_STEP_W1_MIXED,         kBlock, 0, STEP,     k_step<true, 1, true>)                                         \
     X(PK_STEP_W1,               kBlock, 0, STEP,     k_step<false, 1, false>)                                       \

@@ -209,12 +209,33 @@ struct DevScene
 typedef float ConstF4V __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) ConstF4V* ConstF4;
 
+// What a scene and a render's plan may ask of the fused kernel (k_bounce, tn_fused.h).  The host derives the set once per render call
+// (bounce_features, tn_host_batch.h: the scene's bits from its primitives, meshes and materials, the plan's from plan_batch); a FIT instance
+// of k_bounce is compiled for a fixed set and carries neither the code nor the scalars of a feature outside it.  The general instances are
+// compiled for all of them and test each one at run time.
+enum BounceFeature : uint32_t
+{
+    kFeatMedia = 1u,            // a material absorbs (DevScene::hasMedia)
+    kFeatProbe = 2u,            // a light probe is sampled (DevProbe::valid)
+    kFeatMotion = 4u,           // a primitive's pose is interpolated per ray (kPrimMoving)
+    kFeatMeshWalk = 8u,         // a mesh needs the stack walk ray_mesh: neither a quad in the arena nor two leaves
+    kFeatSphere = 16u,          // a sphere primitive (reported; every compiled set has it, so no kernel code depends on it)
+    kFeatTransmission = 32u,    // a material with a transmission lobe
+    kFeatPools = 64u,           // the waves' shading pools (FrameParams::repack)
+    kFeatShare = 128u,          // a workgroup's regions dealt to its waves as one stream (FrameParams::share)
+    kFeatSort = 256u,           // the next bounce's queue sorted (DevScene::sortQueues)
+    kFeatRoulette = 512u,       // Russian roulette (FrameParams::rrStart)
+    kFeatAll = 1023u
+};
+
 // MIXED (with LDS): the arena is staged whole and every scene record resolves to LDS at compile time, but some meshes live in
 // HBM -- the split pipeline's scenes (glass, the 524k-triangle config).  Only the mesh accessors below then choose per mesh;
 // without it those kernels reach everything through generic pointers (flat loads, which wait on both memory counters).
-template <bool LDS, int WALKED_ONLY = 0, int DEFER = 2, bool MIXED = false>
+// FEATURES: the BounceFeature set the kernel is compiled for (the scene's bits: what the intersection and sampling code may meet).
+template <bool LDS, int WALKED_ONLY = 0, int DEFER = 2, bool MIXED = false, uint32_t FEATURES = kFeatAll>
 struct SceneT : DevScene
 {
+    static constexpr uint32_t kFeatures = FEATURES;
     static constexpr bool kLds = LDS;
     static constexpr bool kMixed = MIXED;
     static constexpr bool kWalkedOnly = WALKED_ONLY != 0;

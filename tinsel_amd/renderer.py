@@ -112,6 +112,10 @@ def load_library():
     L.tinsel_hip_walked_prims.argtypes = [vp]
     if hasattr(L, "tinsel_hip_walk_tops"):             # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_walk_tops.argtypes = [vp, C.POINTER(C.c_int), ci]
+    if hasattr(L, "tinsel_hip_bounce_plan"):          # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_bounce_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.tinsel_hip_scene_features.restype = C.c_uint
+        L.tinsel_hip_scene_features.argtypes = [C.POINTER(abi.SceneDesc)]
     if hasattr(L, "tinsel_hip_queue_counts"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_queue_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.tinsel_hip_set_lookahead.argtypes = [vp, ci]
@@ -146,7 +150,7 @@ def load_library():
 
 
 EXPORTED_SYMBOLS = [
-    "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
+    "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
     "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_render_cost", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
@@ -194,6 +198,10 @@ class Scene:
     @property
     def num_primitives(self):
         return self.desc.num_primitives
+
+    def bounce_features(self):
+        """tinsel_hip_scene_features: the abi.BOUNCE_* bits this scene asks of the fused kernel (no device needed)"""
+        return int(load_library().tinsel_hip_scene_features(C.byref(self.desc)))
 
 
 def _bytes_at(ptr, n):
@@ -616,6 +624,13 @@ class HipRenderer:
         n = self._L.tinsel_hip_queue_counts(self._h, out, max_bounces)
         _check(min(n, 0), "tinsel_hip_queue_counts")
         return list(out[:n]), list(out[max_bounces:max_bounces + n])
+
+    def bounce_plan(self):
+        """(kind, features) of the fused kernel's last launch: abi.BOUNCE_GENERAL / _FIT_CLOSED / ..., and the abi.BOUNCE_* feature bits
+        the scene and the plan asked for."""
+        out = (C.c_uint32*2)()
+        _check(self._L.tinsel_hip_bounce_plan(self._h, out), "tinsel_hip_bounce_plan")
+        return int(out[0]), int(out[1])
 
     def close(self):
         if self._h:
