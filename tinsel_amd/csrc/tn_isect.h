@@ -357,10 +357,10 @@ TN_D void pose_inv_ray(const Prim64& p, const Xform& x, V3 o, V3 d, V3& lo, V3& 
     lrcp = rcp3_cr(ld);
 }
 
-TN_D Prim64 load_prim(const Prim64* prims, int idx)
+// a primitive's 64-B record from the four 16-B vectors it was loaded as (float4 or ConstF4V)
+template <class F4>
+TN_D Prim64 unpack_prim(const F4& a, const F4& b, const F4& c, const F4& d)
 {
-    const float4* pp = reinterpret_cast<const float4*>(prims + idx);
-    float4 a = pp[0], b = pp[1], c = pp[2], d = pp[3];
     Prim64 p;
     p.px = a.x; p.py = a.y; p.pz = a.z; p.s = a.w;
     p.rx = b.x; p.ry = b.y; p.rz = b.z; p.rw = b.w;
@@ -370,18 +370,19 @@ TN_D Prim64 load_prim(const Prim64* prims, int idx)
     return p;
 }
 
+TN_D Prim64 load_prim(const Prim64* prims, int idx)
+{
+    const float4* pp = reinterpret_cast<const float4*>(prims + idx);
+    float4 a = pp[0], b = pp[1], c = pp[2], d = pp[3];
+    return unpack_prim(a, b, c, d);
+}
+
 // the same record through the constant-address-space pointer, at a wave-uniform index (scalar loads)
 TN_D Prim64 load_prim_uniform(ConstF4 prims, int idx)
 {
     ConstF4 pp = prims + (size_t)idx*4;
     const ConstF4V a = pp[0], b = pp[1], c = pp[2], d = pp[3];
-    Prim64 p;
-    p.px = a.x; p.py = a.y; p.pz = a.z; p.s = a.w;
-    p.rx = b.x; p.ry = b.y; p.rz = b.z; p.rw = b.w;
-    p.g0 = c.x; p.g1 = c.y; p.g2 = c.z; p.g3 = c.w;
-    p.type = __float_as_uint(d.x); p.flags = __float_as_uint(d.y);
-    p.mesh = __float_as_uint(d.z); p.moving = __float_as_uint(d.w);
-    return p;
+    return unpack_prim(a, b, c, d);
 }
 
 // PrimitiveIntersect (intersection.h:951-1020)
@@ -583,12 +584,7 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
         ConstF4V b0 = sc.kBoxes[i*2], b1 = sc.kBoxes[i*2 + 1];
         ConstF4V ra = sc.kPrims[i*4], rb = sc.kPrims[i*4 + 1], rc = sc.kPrims[i*4 + 2], rd = sc.kPrims[i*4 + 3];
         asm volatile("" : "+s"(b0), "+s"(b1), "+s"(ra), "+s"(rb), "+s"(rc), "+s"(rd));        // (all six in flight before the first is used)
-        Prim64 rec;
-        rec.px = ra.x; rec.py = ra.y; rec.pz = ra.z; rec.s = ra.w;
-        rec.rx = rb.x; rec.ry = rb.y; rec.rz = rb.z; rec.rw = rb.w;
-        rec.g0 = rc.x; rec.g1 = rc.y; rec.g2 = rc.z; rec.g3 = rc.w;
-        rec.type = __float_as_uint(rd.x); rec.flags = __float_as_uint(rd.y);
-        rec.mesh = __float_as_uint(rd.z); rec.moving = __float_as_uint(rd.w);
+        Prim64 rec = unpack_prim(ra, rb, rc, rd);
         if (__float_as_uint(b1.z) == 0u)
         {
             float tb;

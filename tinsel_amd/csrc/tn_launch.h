@@ -71,9 +71,9 @@ namespace tn {
     X(PK_SWALK_EXTEND_LDS,      1024,   1, SWALK,    k_swalk<false, 1024, 1>)                                       \
     X(PK_SWALK_EXTEND_MIXED,    1024,   1, SWALK,    k_swalk<false, 1024, 2>)                                       \
     X(PK_SWALK_EXTEND,          kBlock, 1, SWALK,    k_swalk<false, 256, 0>)                                        \
-    X(PK_WALK_SINGLE_1024X2,    1024,   1, WALK,     k_walk<1024, 8, kWalkSingle>)                                  \
-    X(PK_WALK_SINGLE_1024,      1024,   1, WALK,     k_walk<1024, 4, kWalkSingle>)                                  \
-    X(PK_WALK_SINGLE_256,       256,    1, WALK,     k_walk<256, 5, kWalkSingle>)                                   \
+    X(PK_WALK_SINGLE_1024X2,    1024,   1, WALK,     k_walk<1024, 8>)                                               \
+    X(PK_WALK_SINGLE_1024,      1024,   1, WALK,     k_walk<1024, 4>)                                               \
+    X(PK_WALK_SINGLE_256,       256,    1, WALK,     k_walk<256, 5>)                                                \
     X(PK_WALK_RAYS_1024X2,      1024,   1, WALK,     k_walk_rays<1024, 8>)                                          \
     X(PK_WALK_RAYS_1024,        1024,   1, WALK,     k_walk_rays<1024, 4>)                                          \
     X(PK_WALK_RAYS_256,         256,    1, WALK,     k_walk_rays<256, 5>)                                           \

@@ -105,9 +105,8 @@ TN_D Node64 load_node_from(Ptr nodes, uint32_t idx)
     return n;
 }
 
-// Walk mode (template parameter MODE of k_walk; launch_walk picks it):
-//   kWalkSingle  ONE walked primitive (the host knows): tree, triangles and the staged top are the same for every lane -- kernel-argument
-//                scalars instead of five per-lane registers.
+// ONE walked primitive (k_walk; the host knows): tree, triangles and the staged top are the same for every lane -- kernel-argument scalars
+// instead of five per-lane registers.  Several: k_walk_rays, below.
 // (Round 4's kWalkPairs -- a node over two one-triangle leaves fetched as ONE 128-B record in the triangle phase -- was built in three
 // versions, bit-identical, and never paid: 10.8-10.9 ms without, 10.96-11.02 with on the 524k-triangle config, glass 6.5 -> 8.8 ms;
 // profiles/r04_a..c_ab_walk_pairs*.md have the numbers, `git log -- tinsel_amd/csrc/tn_walk.h` the code.)
@@ -116,7 +115,6 @@ TN_D Node64 load_node_from(Ptr nodes, uint32_t idx)
 // refill and its record, not its node fetches -- and TWO tree levels per 128-B record (a node's child boxes followed by those of its larger
 // internal child: a third fewer visits, each of twice the bytes: 14.0 ms against 10.7 on the 524k-triangle config -- the walk is bound by the
 // BYTES it pulls through a CU's L1, in 64-B sectors, not by lines or round trips).  profiles/r05_b_ab_glass_lds_mesh.md, r05_c_ab_walk_fat.md.)
-constexpr int kWalkSingle = 2;
 
 // The closest hit's normal for its record: n*sign with n = Cross(b - a, c - a) as IntersectRayTriTwoSided forms it (intersection.h:122-124),
 // computed again from the triangle where the record is written -- the lane's next refill, whose chain of dependent loads hides the
@@ -135,11 +133,9 @@ TN_D V3 hit_normal(GlobalF4 tris, int tri, float sign)
 constexpr int kWalkCtlWords = 16;
 constexpr int kWalkLaneRows = 2;
 
-template <int BLOCK, int WAVES, int MODE = 0>
+template <int BLOCK, int WAVES>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
 {
-    constexpr bool SINGLE = (MODE & kWalkSingle) != 0;
-    static_assert(SINGLE, "k_walk is instantiated for ONE walked primitive only: several go through k_walk_rays (below)");
     constexpr uint32_t kAtLeaf = kLeafBit;      // refs that wait for the triangle phase
     extern __shared__ __attribute__((aligned(16))) uint32_t s_walk[];
     uint32_t* const stack = s_walk + threadIdx.x;               // this lane's column: entry i at stack[i*BLOCK]
@@ -199,8 +195,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
     // ONE walked primitive (the common case): its record, leaf box and mesh table entry are wave-uniform -- read once, not
     // behind every refill's ray fetch (the refill is a chain of dependent loads: queue -> slot -> ray -> [box, primitive,
     // mesh]; the last three were a third of it)
-    const bool single = SINGLE || job.numPrims == 1;
-    Prim64 prim0 = load_prim(sc.prims, job.prim[0]);
+    const Prim64 prim0 = load_prim(sc.prims, job.prim[0]);
     float4 box0a, box0b;
     {
         const float4* bp = reinterpret_cast<const float4*>(sc.primBoxes + job.prim[0]);
@@ -222,9 +217,6 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
     float hv = 0.0f, hw = 0.0f;         // (u = 1 - v - w is recomputed where the record is written: IntersectRayTriTwoSided's own expression)
     int htri = -1;
     float hsign = 0.0f;                 // the hit's `sign` (IntersectRayTriTwoSided's d): its normal n*sign is formed where the record is written
-    GlobalF4 mnodes = nullptr;
-    GlobalF4 mtris = nullptr;
-    uint32_t topBase = 0, topN = 0;     // this lane's tree: refs < topN are staged at s_top[(topBase + ref)*4 ..]
     bool finiteAll = true;              // wave-uniform: every active lane's 1/d is finite
     bool exhausted = bbeg >= end;       // wave-uniform: the workgroup's range has been handed out
     TN_WP_DECL
@@ -258,7 +250,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
                     out[0] = make_float4(closestT, 1.0f - hv - hw, hv, hw);
                     if (closestT < kFltMax)
                     {
-                        const V3 hn = hit_normal(SINGLE ? mesh0tris : mtris, htri, hsign);
+                        const V3 hn = hit_normal(mesh0tris, htri, hsign);
                         out[1] = make_float4(hn.x, hn.y, hn.z, __int_as_float(htri));
                     }
                     *s_item = kNoItem;
@@ -270,7 +262,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
                     uint32_t qi = __umulhi(my, perM), rem = my - qi*per;
                     if (rem >= per) { ++qi; rem -= per; }
                     uint32_t k = __umulhi(rem, KbM), kb = rem - k*Kb;
-                    if (kb >= Kb) { ++k; kb -= Kb; }
+                    if (kb >= Kb) { ++k; kb -= Kb; }            // (Kb is 1 here, so k == rem and kb == 0: the division is still to be measured away)
                     const uint32_t slot = job.queue[qi];
                     const uint32_t recAt = slot*per + rem;      // records are indexed by position, like everything the scan kernels read
 
@@ -293,30 +285,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
                     const V3 wo(ro.x, ro.y, ro.z), wd(rd.x, rd.y, rd.z);
                     const bool noRay = job.mixed == 1 && rd.x == 0.0f && rd.y == 0.0f && rd.z == 0.0f;      // (a path without an extension ray)
 
-                    int index = job.prim[0];
-                    uint32_t tb = 0, tn = (uint32_t)job.topCount[0], run = (uint32_t)job.topCount[0];
-                    if (!SINGLE)
-                    {
-#pragma unroll
-                        for (int q = 1; q < kWalkMaxPrims; ++q)
-                        {
-                            if ((uint32_t)q == kb)
-                            {
-                                index = job.prim[q];
-                                tb = run;
-                                tn = (uint32_t)job.topCount[q];
-                            }
-                            run += (uint32_t)job.topCount[q];
-                        }
-                    }
-
                     // the leaf-box test of the scan (trace_flat / the scene BVH walk): same function, same operands
-                    float4 b0 = box0a, b1 = box0b;
-                    if (!single)
-                    {
-                        const float4* bp = reinterpret_cast<const float4*>(sc.primBoxes + index);
-                        b0 = bp[0]; b1 = bp[1];
-                    }
+                    const float4 b0 = box0a, b1 = box0b;
                     const V3 wrcp = rcp3_cr(wd);
                     float tbox;
                     bool enters = true;         // rays the scan does not box-test (ray_sane) are walked unconditionally
@@ -333,31 +303,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
                     else
                     {
                         // PrimitiveIntersect's mesh branch up to IntersectRayMesh (intersection.h:977-990)
-                        Prim64 p = prim0;
-                        if (!single)
-                            p = load_prim(sc.prims, index);
-                        const Xform x = prim_pose(sc, p, time);
-                        pose_inv_ray(p, x, wo, wd, o, d, rcp, wrcp, true);
-                        if (SINGLE)
-                            ref = mesh0root;
-                        else if (single)
-                        {
-                            mnodes = mesh0nodes;
-                            mtris = mesh0tris;
-                            ref = mesh0root;
-                        }
-                        else
-                        {
-                            const DevMesh* m = sc.meshes + p.mesh;
-                            mnodes = as_global(m->nodes);
-                            mtris = as_global(m->tris);
-                            ref = m->root;
-                        }
-                        if (!SINGLE)
-                        {
-                            topBase = tb;
-                            topN = tn;
-                        }
+                        const Xform x = prim_pose(sc, prim0, time);
+                        pose_inv_ray(prim0, x, wo, wd, o, d, rcp, wrcp, true);
+                        ref = mesh0root;
                         sp = 0;
                         closestT = kFltMax;
                         htri = -1;
@@ -380,7 +328,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
         bool pop = false;
 #ifdef TN_WALK_PROF
         { const unsigned long long nm = __ballot(active && !(ref & kAtLeaf)); if (nm) { TN_WP_COUNT(7, 1) TN_WP_COUNT(9, __popcll(nm)) }
-          TN_WP_COUNT(14, __popcll(__ballot(active && !(ref & kAtLeaf) && ref < (SINGLE ? top0N : topN)))) }
+          TN_WP_COUNT(14, __popcll(__ballot(active && !(ref & kAtLeaf) && ref < top0N))) }
         TN_WP_TICK(4)
 #endif
 
@@ -388,10 +336,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
         if (active && !(ref & kAtLeaf))
         {
             Node64 nd;
-            if (ref < (SINGLE ? top0N : topN))
-                nd = load_node_from((const WalkF4*)s_top, SINGLE ? ref : topBase + ref);    // 4 x ds_read_b128
+            if (ref < top0N)
+                nd = load_node_from((const WalkF4*)s_top, ref);         // 4 x ds_read_b128
             else
-                nd = load_node_from(SINGLE ? mesh0nodes : mnodes, ref);                     // 4 x global_load_dwordx4
+                nd = load_node_from(mesh0nodes, ref);                   // 4 x global_load_dwordx4
             float tL, tR;
             bool hL, hR;
             if (finiteAll)
@@ -441,7 +389,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
             {
                 // ONE round trip per phase: every lane requests its leaf's Tri48 before anybody waits
                 const uint32_t idx = ref & ~kLeafBit;
-                GlobalF4 tp = (SINGLE ? mesh0tris : mtris) + (size_t)idx*3;
+                GlobalF4 tp = mesh0tris + (size_t)idx*3;
                 const WalkF4 q3 = tp[0], q4 = tp[1], q5 = tp[2];
                 bool any = false;
                 {
@@ -487,7 +435,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
         out[0] = make_float4(closestT, 1.0f - hv - hw, hv, hw);
         if (closestT < kFltMax)
         {
-            const V3 hn = hit_normal(SINGLE ? mesh0tris : mtris, htri, hsign);
+            const V3 hn = hit_normal(mesh0tris, htri, hsign);
             out[1] = make_float4(hn.x, hn.y, hn.z, __int_as_float(htri));
         }
     }
@@ -498,8 +446,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_walk(DevScene sc, WalkJob job)
 // ---------------------------------------------------------------------------
 // k_walk_rays: SEVERAL walked primitives.  The same walk; a work item is a RAY (slot, k): the lane that takes it tests all walked primitives'
 // leaf boxes once -- the records are wave-uniform -- and walks the ones the ray enters one after the other (`pend`: a bit per primitive still
-// to visit; the ray itself parked in an LDS row as position | k << 27).  Until round 5 an item was a (ray, primitive) pair through k_walk's
-// MODE 0: glass fetched every ray twice, the reference's table.tin -- seven walked meshes -- seven times, to find most of the boxes missed
+// to visit; the ray itself parked in an LDS row as position | k << 27).  Until round 5 an item was a (ray, primitive) pair through a mode
+// of k_walk: glass fetched every ray twice, the reference's table.tin -- seven walked meshes -- seven times, to find most of the boxes missed
 // (table.tin 690 -> 896 Msamples/s, transmission.tin 654 -> 815, glass k_walk 6.67 -> 5.91 ms: profiles/r05_e_ab_walk_by_ray.md).  A kernel of
 // its own, not a mode of k_walk: written as one template, the one-primitive kernel of the 524k-triangle config came out 4-8 % slower with an
 // identical node phase (profiles/r05_g_ab_walk_single_refill.md) -- its source is left exactly as rounds 3-4 tuned it.
