@@ -441,6 +441,34 @@ int tinsel_hip_trace_rays_device(tinsel_hip* r, int mode, long long n, const tin
  * TINSEL_MODE_NORMALS), generated on the device; out_host[j*width + i] */
 int tinsel_hip_trace_camera(tinsel_hip* r, const tinsel_camera* camera, int width, int height, float time, tinsel_ray_hit* out_host);
 
+/* Radiance queries on the resident scene: the reference's PathTrace(scene, origin, dir, time, maxDepth, rand) (render.cpp:230-388) for
+ * paths the caller starts -- light-map and probe baking, radiance caches, re-tracing one pixel's samples, reference radiance for rays in
+ * a device tensor.  One record starts one path: the ray (`direction` is used as given; PathTrace expects unit length), the shutter time
+ * that poses moving primitives, and rng1 / rng2, the two words of the reference's Random at the moment PathTrace is entered -- for
+ * Random(seed): rng1 = 315645664 + seed, rng2 = rng1 ^ 0x13ab45fe.  Reserved words are ignored.  A caller who wants many samples of one
+ * ray repeats it with different generator words.
+ * out[4*k .. 4*k + 2] is the value PathTrace returns for record k, bit for bit under TINSEL_ARITH_EXACT: unclamped and unfiltered (clamp
+ * and the reconstruction filter belong to AddSample, which a query does not run); out[4*k + 3] is reserved.
+ * A query uses the scene in force (rebuild_scene, refit_mesh, set_mesh_bvh) and the renderer's roulette, probe-sampling and arithmetic
+ * settings; it ignores the shard, needs no tinsel_hip_init, and leaves the accumulator, the pass index, the pass seeds, the tuning and
+ * look-ahead as they were.  Its rays and samples ARE counted in tinsel_hip_stats: a query is path tracing.  It runs the paired
+ * pipeline where a render would and the split pipeline otherwise (also under TINSEL_PIPELINE_MEGAKERNEL and on scenes a render takes
+ * through the fused kernel), behind kernel "k_generate_rays" in tinsel_hip_kernel_times (with kernel timing on, a query starts a new
+ * record like a render call does).  More paths than tinsel_hip_set_batch_paths allows run as several batches, one after the other;
+ * the result does not depend on the cut.  Bad arguments -- a null renderer, n < 0 or n >= 2^31, max_depth < 1, a null array with n > 0,
+ * a moved primitive without tinsel_hip_rebuild_scene -- return -1 and launch nothing; n == 0 returns 0.
+ * Memory: the paths are traced in the renderer's path buffers, the state of min(n, batch_paths) paths (a render that runs another
+ * pipeline allocates its own again); the host entry adds staging buffers kept until tinsel_hip_destroy, shared with
+ * tinsel_hip_trace_rays: at most 64 MB (2^20 paths per chunk: 48 MB of records, 16 MB of results), whatever n is. */
+typedef struct tinsel_path_start { float ox, oy, oz, time;  float dx, dy, dz, reserved0;  uint32_t rng1, rng2, reserved1, reserved2; } tinsel_path_start;
+
+/* host arrays (staged through device buffers the renderer keeps, in chunks); returns when `out_rgbx_host` is written */
+int tinsel_hip_trace_radiance(tinsel_hip* r, long long n, const tinsel_path_start* starts_host, int max_depth, float* out_rgbx_host);
+/* device arrays, 16-byte aligned, not overlapping; enqueued on `stream` (NULL: the default stream) and not waited for.  The path buffers
+ * are the renderer's: `stream` first waits, on the device, for what the renderer has in flight -- look-ahead chunks included, none is
+ * discarded -- and the renderer's next use of the buffers, on whatever stream, waits for the query. */
+int tinsel_hip_trace_radiance_device(tinsel_hip* r, long long n, const tinsel_path_start* starts_dev, int max_depth, float* out_rgbx_dev, void* stream);
+
 /* Allocates the per-batch path buffers a later render of `passes` passes at `max_depth` will need, so that the first
  * such call does not pay for hipMalloc (tinsel_hip_render* allocate on demand otherwise). */
 int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth);
@@ -644,6 +672,7 @@ static_assert(sizeof(tinsel_pack_header) == 256, "pack header");
 static_assert(sizeof(tinsel_hip_tuning) == 128, "tuning");
 static_assert(sizeof(tinsel_ray) == 32, "ray");
 static_assert(sizeof(tinsel_ray_hit) == 32, "ray hit");
+static_assert(sizeof(tinsel_path_start) == 48, "path start");
 #endif
 
 #endif /* TINSEL_HIP_H */

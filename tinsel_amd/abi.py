@@ -140,6 +140,19 @@ RAY_HIT_DTYPE = [("t", "<f4"), ("primitive", "<i4"), ("nx", "<f4"), ("ny", "<f4"
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 
 
+class PathStart(C.Structure):
+    """tinsel_path_start: the ray a path starts with (direction used as given; PathTrace expects unit length), its shutter time, and the
+    two words of the reference's Random when PathTrace is entered (tinsel_amd.rng_state); reserved words are ignored"""
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("time", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("reserved0", C.c_float),
+                ("rng1", C.c_uint32), ("rng2", C.c_uint32), ("reserved1", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+# an (n, 12) array of 32-bit words viewed as PATH_START_DTYPE is a tinsel_path_start[n]
+PATH_START_DTYPE = [("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("time", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("reserved0", "<f4"),
+                    ("rng1", "<u4"), ("rng2", "<u4"), ("reserved1", "<u4"), ("reserved2", "<u4")]
+
+
 class KernelTimeV1(C.Structure):
     """tinsel_kernel_time as libraries built before round 4 wrote it (no busy_ms): renderer.HipRenderer.kernel_times"""
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_float)]

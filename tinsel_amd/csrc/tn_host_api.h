@@ -152,6 +152,47 @@ int tinsel_hip_trace_camera(tinsel_hip* r, const tinsel_camera* camera, int widt
     return 0;
 }
 
+// Radiance queries (tn_radiance.h, tn_host_radiance.h): the integrator on paths the caller starts.  The accumulator, the pass index, the pass
+// seeds and the tuning are not touched, look-ahead work in flight is waited for on the device and kept; rays and samples are counted.
+int tinsel_hip_trace_radiance_device(tinsel_hip* r, long long n, const tinsel_path_start* starts_dev, int max_depth, float* out_rgbx_dev, void* stream)
+{
+    if (radiance_args(r, n, starts_dev, out_rgbx_dev, max_depth, "trace_radiance_device"))
+        return -1;
+    const uintptr_t a = (uintptr_t)starts_dev, b = (uintptr_t)out_rgbx_dev;
+    const uintptr_t aBytes = (uintptr_t)n*sizeof(tinsel_path_start), bBytes = (uintptr_t)n*sizeof(float4);
+    if ((a & 15u) || (b & 15u))
+        return fail("trace_radiance_device: the arrays must be 16-byte aligned");
+    if (a < b + bBytes && b < a + aBytes)
+        return fail("trace_radiance_device: the arrays overlap");
+    if (query_ready(r, "trace_radiance_device"))
+        return -1;
+    if (n == 0)
+        return 0;
+    return trace_radiance(r, (size_t)n, starts_dev, (float4*)out_rgbx_dev, max_depth, (hipStream_t)stream);
+}
+
+int tinsel_hip_trace_radiance(tinsel_hip* r, long long n, const tinsel_path_start* starts_host, int max_depth, float* out_rgbx_host)
+{
+    if (radiance_args(r, n, starts_host, out_rgbx_host, max_depth, "trace_radiance") || query_ready(r, "trace_radiance"))
+        return -1;
+    const size_t chunk = std::min<size_t>((size_t)n, kRadianceChunk);
+    if (chunk == 0)
+        return 0;
+    if (query_buffer(r->queryRaysDev, chunk*sizeof(tinsel_path_start)) || query_buffer(r->queryOutDev, chunk*sizeof(float4)))
+        return -1;
+    unsigned char* const startsDev = r->queryRaysDev.get();
+    float4* const outDev = (float4*)r->queryOutDev.get();
+    for (size_t done = 0; done < (size_t)n; done += chunk)
+    {
+        const size_t m = std::min(chunk, (size_t)n - done);
+        HIP_TRY(hipMemcpy(startsDev, starts_host + done, m*sizeof(tinsel_path_start), hipMemcpyHostToDevice));
+        if (trace_radiance(r, m, startsDev, outDev, max_depth, nullptr))
+            return -1;
+        HIP_TRY(hipMemcpy(out_rgbx_host + done*4, outDev, m*sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -15,6 +15,7 @@ void free_batch(tinsel_hip* r)
     r->batchLanes = 1;
     r->batchNee = -1;
     r->batchDepth = -1;
+    r->lastBatchSlots = 0;          // (tinsel_hip_read_batch_radiance: the batch's radiance went with the buffers)
 }
 
 // blocks per CU of the streaming kernels' fixed grid.  Swept 4..256 on every config: 32 is best everywhere (finer static
@@ -595,11 +596,12 @@ struct BatchPlan
     SwalkPlan swalkPlan;                // where `sceneWalk`
 };
 
-// perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve)
-BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap)
+// perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve);
+// pipeline: the caller's choice in the place of resolve_pipeline's (a radiance query's, tn_host_radiance.h)
+BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int pipeline = -1)
 {
     BatchPlan p;
-    p.pipeline = resolve_pipeline(r);
+    p.pipeline = pipeline >= 0 ? pipeline : resolve_pipeline(r);
     const bool fused = p.pipeline == TINSEL_PIPELINE_WAVEFRONT, split = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT,
                paired = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED;
 
@@ -781,6 +783,9 @@ int ensure_batch(tinsel_hip* r, const BatchPlan& p, int maxDepth)
     if (r->batchSlots >= p.slots && r->batchStateSlots >= p.stateSlots && r->batchLanes >= p.lanes && r->batchNee == K && r->batchDepth >= maxDepth &&
         r->batchPipeline == p.pipeline && (lane.walkRec != nullptr) == p.walkRecords && (lane.walkList != nullptr) == p.workList)
         return 0;
+    // (a radiance query's device entry, or look-ahead, may have left launches over the old buffers in flight on another stream)
+    if (r->batchPipeline >= 0)
+        HIP_TRY(hipDeviceSynchronize());
     free_batch(r);
 
     // the radiance of finished paths by slot is what every pipeline hands to the accumulate kernels
@@ -1071,7 +1076,8 @@ int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L
         *grid = std::max(1, std::min(*grid, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
     if (cut_batch(p, L, a, slots, grid))
         return -1;
-    ScopedTimer t(r, KN_GENERATE, st);
+    // (the plan says which paths: the camera's, or a radiance query's -- k_generate_rays reads a.radiance and no camera)
+    ScopedTimer t(r, p.generate == PK_GENERATE_RAYS ? KN_GENERATE_RAYS : KN_GENERATE, st);
     a.grid = *grid;
     a.variant = p.generate;
     a.ldsBytes = 0;
@@ -1270,13 +1276,14 @@ size_t batch_frame(const tinsel_hip* r, FrameParams& fp)
     return slots;
 }
 
-// One batch -- or one overlapped chunk -- of passes fp.passBase .. + fp.numPasses, traced in lane L; the paths' radiance goes to rad[0, slots)
-int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams& cam, FrameParams fp, float4* rad,
-                 bool accumulate = true)
+// The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
+// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance query, tn_host_radiance.h -- the split or the paired pipeline
+// behind k_generate_rays, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
+int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
+                size_t slots, const RadianceJob* starts = nullptr)
 {
-    const size_t slots = batch_frame(r, fp);
-    if (!slots)
-        return fail("render: batch too large");
+    if (starts && (p.generate != PK_GENERATE_RAYS || (p.pipeline != TINSEL_PIPELINE_WAVEFRONT_SPLIT && p.pipeline != TINSEL_PIPELINE_WAVEFRONT_PAIRED)))
+        return fail("trace_batch: caller-started paths run the split or the paired pipeline");
     r->lastPipeline = p.pipeline;
 
     // what every launch of the batch shares
@@ -1285,7 +1292,10 @@ int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
     a.scene = r->scene;
     a.ps.rad = rad;
     a.ctl = r->ctl;
-    a.cam = cam;
+    if (cam)
+        a.cam = *cam;
+    if (starts)
+        a.radiance = *starts;
     a.fp = fp;
     a.passSeeds = r->passSeeds;
     a.walkRec = p.walk ? L.walkRec : nullptr;
@@ -1310,11 +1320,43 @@ int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hi
         if (rc)
             return -1;
     }
-
     r->lastFp = fp;
+    return 0;
+}
+
+// One batch -- or one overlapped chunk -- of passes fp.passBase .. + fp.numPasses, traced in lane L; the paths' radiance goes to rad[0, slots)
+int render_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams& cam, FrameParams fp, float4* rad,
+                 bool accumulate = true)
+{
+    const size_t slots = batch_frame(r, fp);
+    if (!slots)
+        return fail("render: batch too large");
+    if (trace_batch(r, p, L, st, &cam, fp, rad, slots))
+        return -1;
     if (!accumulate)
         return 0;
     return launch_accumulate(r, st, fp, rad, r->accum);
+}
+
+// The path buffers (ensure_batch) have one user at a time.  Renders order themselves by their stream, and what look-ahead leaves in flight is
+// waited for by whoever comes next (lookahead_cancel) -- but the device entry of a radiance query neither waits nor cancels, on a stream of the
+// caller's.  So whoever leaves the buffers on a stream the next user cannot know records the fence behind its last launch, and every user
+// makes its stream wait for a fence recorded elsewhere before its first.
+int batch_fence_wait(tinsel_hip* r, hipStream_t st)
+{
+    if (r->batchFencePending && r->batchFenceStream != st)
+        HIP_TRY(hipStreamWaitEvent(st, r->batchFence, 0));
+    return 0;
+}
+
+int batch_fence_signal(tinsel_hip* r, hipStream_t st)
+{
+    if (r->batchFence.create())
+        return -1;
+    HIP_TRY(hipEventRecord(r->batchFence, st));
+    r->batchFenceStream = st;
+    r->batchFencePending = true;
+    return 0;
 }
 
 // return finished timing events to the pool (a render call's kernel times cover that call alone)
@@ -1425,7 +1467,7 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
         perBatch = passes;
 
     const BatchPlan plan = plan_batch(r, perPass, perBatch, !traceOnly);
-    if (ensure_batch(r, plan, fp.maxDepth))
+    if (ensure_batch(r, plan, fp.maxDepth) || batch_fence_wait(r, st))
         return -1;
 
     if (traceOnly && perBatch < passes)
@@ -1489,6 +1531,9 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
         r->lastFp.accEnd = n;
     }
     r->passIndex += (uint32_t)passes;
+    // (the default stream and the look-ahead's are the renderer's own: a query asks those itself, tn_host_radiance.h)
+    if (st && st != (hipStream_t)r->workStream && batch_fence_signal(r, st))
+        return -1;
     return 0;
 }
 

@@ -164,6 +164,12 @@ struct tinsel_hip
         }
     };
     std::unique_ptr<QueryCursors> queryCursors;     // made whole by launch_query on first use
+    // radiance queries (tinsel_hip_trace_radiance*, tn_host_radiance.h) trace in the path buffers: the event behind their last user on a
+    // stream the next user cannot know (batch_fence_signal / batch_fence_wait, tn_host_batch.h), and the events a query records on the
+    // renderer's own streams -- [0] the default one, [1] the look-ahead's -- to wait for what they hold
+    Event batchFence, queryFork[2];
+    hipStream_t batchFenceStream = nullptr;
+    bool batchFencePending = false;
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)

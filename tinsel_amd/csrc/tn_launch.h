@@ -86,7 +86,8 @@ namespace tn {
     X(PK_QUERYR_CLOSEST_LDS,    kBlock, 0, QUERY,    k_query_refill<kQueryClosest, true>)                           \
     X(PK_QUERYR_CLOSEST,        kBlock, 0, QUERY,    k_query_refill<kQueryClosest, false>)                          \
     X(PK_QUERYR_OCCLUDED_LDS,   kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, true>)                          \
-    X(PK_QUERYR_OCCLUDED,       kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, false>)
+    X(PK_QUERYR_OCCLUDED,       kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, false>)                         \
+    X(PK_GENERATE_RAYS,         kBlock, 0, GENERATE_RAYS, k_generate_rays)
 
 enum PathKernel : int
 {
@@ -119,6 +120,7 @@ struct LaunchArgs
     uint32_t ldsBytes;              // dynamic LDS of the launch
     uint32_t* cost;                 // k_cost: the cost map's four planes
     QueryJob query;                 // k_query
+    RadianceJob radiance;           // k_generate_rays
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -133,6 +135,7 @@ struct LaunchArgs
 #define TN_ARGS_SWALK    a.scene, a.ss, a.ctl, a.bounce, a.swalk
 #define TN_ARGS_WALK     a.scene, a.walk
 #define TN_ARGS_QUERY    a.scene, a.query, a.cam, a.stackEntries
+#define TN_ARGS_GENERATE_RAYS a.ss, a.ctl, a.radiance, a.scene.primBoxes, a.bins
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

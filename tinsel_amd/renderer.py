@@ -90,6 +90,9 @@ def load_library():
     L.tinsel_hip_trace_rays.argtypes = [vp, ci, C.c_longlong, vp, vp]
     L.tinsel_hip_trace_rays_device.argtypes = [vp, ci, C.c_longlong, vp, vp, vp]
     L.tinsel_hip_trace_camera.argtypes = [vp, C.POINTER(abi.Camera), ci, ci, cf, vp]
+    if hasattr(L, "tinsel_hip_trace_radiance"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_trace_radiance.argtypes = [vp, C.c_longlong, vp, ci, vp]
+        L.tinsel_hip_trace_radiance_device.argtypes = [vp, C.c_longlong, vp, ci, vp, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -165,7 +168,21 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_tuning_init", "tinsel_hip_create_tuned", "tinsel_hip_set_tuning", "tinsel_hip_get_tuning", "tinsel_hip_group_create_tuned",
     "tinsel_hip_comm_unique_id", "tinsel_hip_comm_init", "tinsel_hip_comm_size", "tinsel_hip_comm_reduce_accum",
     "tinsel_hip_trace_rays", "tinsel_hip_trace_rays_device", "tinsel_hip_trace_camera",
+    "tinsel_hip_trace_radiance", "tinsel_hip_trace_radiance_device",
 ]
+
+
+def rng_state(seed, skip=0):
+    """The two words (rng1, rng2 of abi.PathStart) of the reference's Random(seed) after `skip` calls of Rand(): what a radiance query's
+    record carries for a path whose generator has made `skip` draws before PathTrace is entered (a camera path: 3 -- x, y, t).
+    Vectorised over numpy uint32 (any integer is taken modulo 2^32); returns two uint32 arrays of seed's shape."""
+    shape = np.shape(seed)
+    s1 = np.asarray(seed).astype(np.uint32).reshape(-1) + np.uint32(315645664)
+    s2 = s1 ^ np.uint32(0x13AB45FE)
+    for _ in range(int(skip)):
+        s1 = (s2 ^ ((s1 << np.uint32(5)) | (s1 >> np.uint32(27)))) ^ (s1*s2)
+        s2 = s1 ^ ((s2 << np.uint32(12)) | (s2 >> np.uint32(20)))
+    return s1.reshape(shape), s2.reshape(shape)
 
 
 def _check(rc, what):
@@ -510,6 +527,41 @@ class HipRenderer:
         # (an empty array's data pointer may be null: hand the library addresses it can check)
         keep_r, keep_o = (rays, out) if n else (np.zeros((1, 8), np.float32), np.zeros(1, out.dtype))
         _check(self._L.tinsel_hip_trace_rays(self._h, m, n, keep_r.ctypes.data_as(C.c_void_p), keep_o.ctypes.data_as(C.c_void_p)), "tinsel_hip_trace_rays")
+        return out
+
+    def radiance(self, starts, max_depth):
+        """Radiance queries on the resident scene (tinsel_hip_trace_radiance*): the reference's PathTrace for paths the caller starts,
+        one per record of `starts` -- a numpy array of abi.PATH_START_DTYPE, or an (n, 12) array of 32-bit words holding the same
+        48-byte records (origin xyz, time, direction xyz -- unit length, used as given --, a reserved word, rng1, rng2 from rng_state,
+        two reserved words): the host entry, returns float32 (n, 4) = radiance rgb + a reserved word, unclamped and unfiltered.  A
+        contiguous (n, 12) float32 / int32 torch tensor on this renderer's device goes to the device entry on torch's current stream,
+        not waited for, and a float32 (n, 4) tensor comes back.  Uses the scene in force and the roulette, probe-sampling and arithmetic
+        settings; leaves the accumulator, pass index and tuning as they were; its rays and samples are counted in stats(); needs no init()."""
+        max_depth = int(max_depth)
+        if not isinstance(starts, np.ndarray) and hasattr(starts, "data_ptr"):
+            import torch
+            if starts.dtype not in (torch.float32, torch.int32) or starts.dim() != 2 or starts.shape[1] != 12 or not starts.is_contiguous() or not starts.is_cuda:
+                raise ValueError("radiance: a contiguous (n, 12) float32 or int32 tensor on the GPU is expected")
+            if starts.device.index != self.device:
+                raise ValueError("radiance: the tensor is on %s, the renderer on device %d" % (starts.device, self.device))
+            n = int(starts.shape[0])
+            out = torch.empty((n, 4), dtype=torch.float32, device=starts.device)
+            if n:
+                stream = torch.cuda.current_stream(starts.device).cuda_stream
+                _check(self._L.tinsel_hip_trace_radiance_device(self._h, n, starts.data_ptr(), max_depth, out.data_ptr(), stream), "tinsel_hip_trace_radiance_device")
+            return out
+        starts = np.asarray(starts)
+        if starts.dtype == np.dtype(abi.PATH_START_DTYPE) and starts.ndim == 1:
+            words = np.ascontiguousarray(starts)
+        elif starts.dtype.itemsize == 4 and starts.dtype.kind in "fiu" and starts.ndim == 2 and starts.shape[1] == 12:
+            words = np.ascontiguousarray(starts)
+        else:
+            raise ValueError("radiance: an array of abi.PATH_START_DTYPE or an (n, 12) array of 32-bit words is expected")
+        n = words.shape[0]
+        out = np.zeros((n, 4), np.float32)
+        # (an empty array's data pointer may be null: hand the library addresses it can check)
+        keep_s, keep_o = (words, out) if n else (np.zeros((1, 12), np.float32), np.zeros((1, 4), np.float32))
+        _check(self._L.tinsel_hip_trace_radiance(self._h, n, keep_s.ctypes.data_as(C.c_void_p), max_depth, keep_o.ctypes.data_as(C.c_void_p)), "tinsel_hip_trace_radiance")
         return out
 
     def trace_camera(self, camera, width, height, time=1.0):
