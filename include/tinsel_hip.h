@@ -469,6 +469,49 @@ int tinsel_hip_trace_radiance(tinsel_hip* r, long long n, const tinsel_path_star
  * discarded -- and the renderer's next use of the buffers, on whatever stream, waits for the query. */
 int tinsel_hip_trace_radiance_device(tinsel_hip* r, long long n, const tinsel_path_start* starts_dev, int max_depth, float* out_rgbx_dev, void* stream);
 
+/* Gather queries on the resident scene: `samples` paths from each of n surface points, drawn and reduced on the device -- one mean
+ * radiance per point for light-map baking, probe baking and radiance caches, where n*samples tinsel_path_start records in and as many
+ * results out would be the whole cost.  A point is a position (the origin as given: the caller applies its own offset off the surface),
+ * the shutter time, a normal (used as given: the caller supplies unit length) and a seed.
+ * Sample s of point k (0 <= s < samples): the generator is the reference's Random(seed_k + s), the sum wrapping in 32 bits;
+ * u1 = Randf(), then u2 = Randf().  TINSEL_GATHER_COSINE: BasisFromVector(n, &u, &v), d = CosineSampleHemisphere(u1, u2), direction
+ * u*d.x + v*d.y + n*d.z -- the basis as render.cpp:328 builds it, the sum in the operand order of disney.h:256-258
+ * (`U*d.x + V*d.y + N*d.z`, added left to right).  TINSEL_GATHER_SPHERE: direction UniformSampleSphere(u1, u2), the normal ignored.
+ * PathTrace (render.cpp:230-388) is entered with that ray, the point's time and the generator as it stands after the two draws:
+ * rng1 / rng2 of tinsel_path_start for Random(seed_k + s) advanced twice.  Callers who want independent streams space their seeds by
+ * at least `samples`.
+ * out[4*k .. 4*k + 2] is the sum over s = 0 .. samples - 1, in ascending s, in fp32, without contraction, of what PathTrace returns for
+ * sample s, divided by (float)samples with an IEEE divide (TINSEL_ARITH_EXACT); out[4*k + 3] is reserved and written as 0.  Unclamped and
+ * unfiltered, as for radiance queries.  COSINE: mean * pi is the irradiance, mean * albedo a Lambertian surface's exitant radiance;
+ * SPHERE: the mean incident radiance (a light probe).
+ * starts_out, when not NULL, receives the generated tinsel_path_start of path (k, s) at index k*samples + s, reserved words 0, whatever
+ * order the device traced them in: tinsel_hip_trace_radiance on it gives the summands (re-tracing a firefly).
+ * Everything else is as for radiance queries: the scene in force and the renderer's roulette, probe-sampling and arithmetic settings;
+ * the shard ignored, no tinsel_hip_init needed; accumulator, pass index, pass seeds, tuning and look-ahead untouched; rays and samples
+ * counted in tinsel_hip_stats; the paired pipeline where a render would run it and the split pipeline otherwise, behind kernel
+ * "k_generate_gather" and in front of "k_gather_reduce" in tinsel_hip_kernel_times.  A batch holds whole points only,
+ * floor(batch_paths / samples) of them (one at least); batches run one after the other and the result does not depend on the cut.
+ * Bad arguments -- a null renderer, a mode out of range, n < 0 or n >= 2^31, samples outside [1, 65536], max_depth < 1, a null points or
+ * out array with n > 0, a moved primitive without tinsel_hip_rebuild_scene -- return -1 and launch nothing; n == 0 returns 0.  The
+ * arguments and the scene are judged before n is looked at: n == 0 with a mode out of range, or with a moved primitive, returns -1.
+ * Memory: the path buffers of a batch as for radiance queries, plus 16 bytes per path of the batch kept until tinsel_hip_destroy (the
+ * paths' radiance, which the reduction reads).  The host entry stages through the buffers of tinsel_hip_trace_rays /
+ * tinsel_hip_trace_radiance, at most 64 MB whatever n and samples are: 2^20 points per chunk (32 MB of points, 16 MB of means); with
+ * starts_out a chunk is min(2^20, floor(64 MB / (48 + 48*samples))) points, so that points, means and one chunk's records (in a third
+ * buffer of the renderer's) stay below the same ceiling. */
+typedef struct tinsel_gather_point { float px, py, pz, time;  float nx, ny, nz;  uint32_t seed; } tinsel_gather_point;
+
+#define TINSEL_GATHER_COSINE 0   /* cosine-weighted hemisphere about the normal: mean * pi = irradiance, mean * albedo = Lambertian exitant radiance */
+#define TINSEL_GATHER_SPHERE 1   /* uniform sphere, normal ignored: mean incident radiance (a light probe) */
+
+/* host arrays (staged in chunks); returns when `out_rgbx_host` (and `starts_out_host`) is written */
+int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
+                               float* out_rgbx_host, tinsel_path_start* starts_out_host /* may be NULL */);
+/* device arrays, 16-byte aligned, not overlapping; enqueued on `stream` (NULL: the default stream) and not waited for, ordered against the
+ * renderer's own work as tinsel_hip_trace_radiance_device is */
+int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
+                                      float* out_rgbx_dev, tinsel_path_start* starts_out_dev /* may be NULL */, void* stream);
+
 /* Allocates the per-batch path buffers a later render of `passes` passes at `max_depth` will need, so that the first
  * such call does not pay for hipMalloc (tinsel_hip_render* allocate on demand otherwise). */
 int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth);
@@ -673,6 +716,7 @@ static_assert(sizeof(tinsel_hip_tuning) == 128, "tuning");
 static_assert(sizeof(tinsel_ray) == 32, "ray");
 static_assert(sizeof(tinsel_ray_hit) == 32, "ray hit");
 static_assert(sizeof(tinsel_path_start) == 48, "path start");
+static_assert(sizeof(tinsel_gather_point) == 32, "gather point");
 #endif
 
 #endif /* TINSEL_HIP_H */

@@ -1,0 +1,306 @@
+"""Gather queries (tinsel_hip_gather_radiance / _device; kernels k_generate_gather, k_gather_reduce): many paths per surface point, drawn
+and reduced on the device.
+
+The points are the first-hit points of a pack's own camera at 16 x 12 (HipRenderer.first_hit_points: misses dropped, moved off the surface
+along the turned normal by the reference's ray epsilon), max_depth is 4.  What a gather returns is held to what the library already
+answers for the SAME paths one by one: gather(..., return_starts=True) gives the generated tinsel_path_start records, radiance() of those
+records (held to the reference bit for bit by test_gpu_radiance_query.py) gives the summands, and a float32 sum sequential in s
+(np.add.accumulate) divided by float32(S) must be the gather's mean, bit for bit.  The records themselves are held to the stated formulas:
+generator words exactly, origin and time exactly, directions to 5e-6 of a float64 evaluation (about a dozen float32 roundings of
+quantities no larger than 2 pi: 12 * 2 pi * 2^-24 = 4.5e-6; a wrong axis, sign or hemisphere is off by 1e-2 or more)."""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import tinsel_amd
+from tinsel_amd import abi
+from tests import oracle_api as oa
+from tests.test_gpu_ray_query import _cam_opt, _renderer
+
+pytestmark = pytest.mark.gpu
+
+W, H, DEPTH = 16, 12, 4
+SAMPLES = (1, 5, 67)
+MODES = ("cosine", "sphere")
+DIR_TOL = 5e-6
+
+
+@functools.lru_cache(maxsize=None)
+def _surface(name):
+    """(positions [n, 3], normals [n, 3]) of the pack's first-hit points: computed once, shared, left unchanged"""
+    scene, r = _renderer(name)
+    try:
+        cam, _ = _cam_opt(scene)
+        points, _, primitive, normal = r.first_hit_points(cam, W, H)
+    finally:
+        r.close()
+    hit = primitive >= 0
+    pos, nrm = np.ascontiguousarray(points[hit]), np.ascontiguousarray(normal[hit])
+    assert len(pos) > 64 and np.allclose(np.linalg.norm(nrm, axis=1), 1.0, atol=1e-5)
+    pos.setflags(write=False)
+    nrm.setflags(write=False)
+    return pos, nrm
+
+
+def _sequential_mean(rad, n, samples):
+    """sum over s in ascending s, in float32, of rad[k*samples + s], divided by float32(samples)"""
+    per = np.ascontiguousarray(rad[:, :3]).reshape(n, samples, 3)
+    total = np.add.accumulate(per, axis=1, dtype=np.float32)[:, -1, :]
+    assert total.dtype == np.float32
+    return total/np.float32(samples)
+
+
+def _hold_mean(r, pts, samples, mode, what):
+    n = len(pts)
+    mean, starts = r.gather(pts, samples, DEPTH, mode, return_starts=True)
+    assert mean.dtype == np.float32 and mean.shape == (n, 4) and starts.shape == (n*samples,)
+    rad = r.radiance(starts, DEPTH)
+    want = _sequential_mean(rad, n, samples)
+    assert np.isfinite(want).all() and want.any(), what
+    assert np.array_equal(mean[:, :3], want), "%s: %d of %d means differ from the sequential sum (largest difference %g)" % (
+        what, int((mean[:, :3] != want).any(axis=1).sum()), n, float(np.abs(mean[:, :3] - want).max()))
+    assert not mean[:, 3].any() and (mean[:, 3].view(np.uint32) == 0).all(), what
+    return mean, starts
+
+
+# ---------------------------------------------------------------------------
+# 1: the mean is the stated sum, bit for bit
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", ["cornell", "ajax_standin_96", "motionblur", "cornell_probe"])
+def test_the_mean_is_the_sequential_sum_of_the_paths_radiance(name, mode):
+    pos, nrm = _surface(name)
+    scene, r = _renderer(name)
+    try:
+        if name == "ajax_standin_96":
+            assert r.walked_prims > 0                   # (the paired pipeline: k_walk + k_step behind k_generate_gather)
+        cam, _ = _cam_opt(scene)
+        times = 1.0
+        if name == "motionblur":
+            assert cam.shutter_end > cam.shutter_start
+            times = np.linspace(cam.shutter_start, cam.shutter_end, len(pos)).astype(np.float32)
+            assert len(np.unique(times)) == len(pos)
+        for samples in SAMPLES:
+            pts = tinsel_amd.gather_points(pos, nrm, samples, time=times, base_seed=1000*samples)
+            _, starts = _hold_mean(r, pts, samples, mode, "%s %s S=%d" % (name, mode, samples))
+            assert np.array_equal(starts["time"].reshape(len(pos), samples), np.repeat(pts["time"][:, None], samples, axis=1))
+    finally:
+        r.close()
+
+
+# ---------------------------------------------------------------------------
+# 2: the starts are the stated ones
+
+def _expected_directions(normals, u1, u2, mode):
+    """float64 evaluation of the stated formulas on the float32 draws, with the float32 value of the 2 pi constant"""
+    two_pi = np.float64(np.float32(np.pi)*np.float32(2.0))
+    u1, u2, n = u1.astype(np.float64), u2.astype(np.float64), normals.astype(np.float64)
+    if mode == "sphere":                                        # UniformSampleSphere (maths.h:1278-1287)
+        z = 1.0 - 2.0*u1
+        rr = np.sqrt(np.maximum(0.0, 1.0 - z*z))
+        return np.stack([rr*np.cos(two_pi*u2), rr*np.sin(two_pi*u2), z], axis=-1)
+    # BasisFromVector (maths.h:1261-1275)
+    first = np.abs(n[..., 0]) > np.abs(n[..., 1])
+    with np.errstate(all="ignore"):
+        ia = 1.0/np.sqrt(n[..., 0]**2 + n[..., 2]**2)
+        ib = 1.0/np.sqrt(n[..., 1]**2 + n[..., 2]**2)
+        zero = np.zeros_like(ia)
+        u = np.where(first[..., None], np.stack([-n[..., 2]*ia, zero, n[..., 0]*ia], axis=-1), np.stack([zero, n[..., 2]*ib, -n[..., 1]*ib], axis=-1))
+    v = np.cross(n, u)
+    # CosineSampleHemisphere (maths.h:1304-1310, 1319-1325)
+    rr = np.sqrt(u1)
+    sx, sy = rr*np.cos(two_pi*u2), rr*np.sin(two_pi*u2)
+    z = np.sqrt(np.maximum(0.0, 1.0 - sx*sx - sy*sy))
+    return u*sx[..., None] + v*sy[..., None] + n*z[..., None]
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_the_starts_are_the_stated_ones(mode):
+    pos, nrm = _surface("cornell")
+    n, samples = len(pos), 5
+    seeds = (np.arange(n, dtype=np.uint64)*np.uint64(977) + np.uint64(31)).astype(np.uint32)
+    seeds[:3] = [2**32 - 1, 2**32 - 3, 0]                       # seed + s wraps in 32 bits
+    times = np.linspace(0.0, 1.0, n).astype(np.float32)
+    pts = tinsel_amd.gather_points(pos, nrm, samples, time=times, seeds=seeds)
+    scene, r = _renderer("cornell")
+    try:
+        _, starts = r.gather(pts, samples, DEPTH, mode, return_starts=True)
+    finally:
+        r.close()
+    starts = starts.reshape(n, samples)
+    path_seed = seeds[:, None] + np.arange(samples, dtype=np.uint32)[None, :]            # (uint32: wraps)
+    assert path_seed.dtype == np.uint32 and path_seed[0, 1] == 0
+    w1, w2 = tinsel_amd.rng_state(path_seed, 2)
+    assert np.array_equal(starts["rng1"], w1) and np.array_equal(starts["rng2"], w2)
+    for f, src in (("ox", "px"), ("oy", "py"), ("oz", "pz"), ("time", "time")):
+        assert np.array_equal(starts[f].view(np.uint32), np.repeat(pts[src][:, None], samples, axis=1).view(np.uint32)), f
+    for f in ("reserved0", "reserved1", "reserved2"):
+        assert not starts[f].view(np.uint32).any(), f
+    # Randf(): (float)Rand() * 2^-32, Rand() being the generator's new first word
+    u1 = tinsel_amd.rng_state(path_seed, 1)[0].astype(np.float32)*np.float32(2.0**-32)
+    u2 = w1.astype(np.float32)*np.float32(2.0**-32)
+    assert u1.dtype == np.float32 and u2.dtype == np.float32
+    normals = np.repeat(nrm[:, None, :], samples, axis=1)
+    want = _expected_directions(normals, u1, u2, mode)
+    got = np.stack([starts["dx"], starts["dy"], starts["dz"]], axis=-1).astype(np.float64)
+    err = np.abs(got - want)
+    print("%s: largest direction error %.3g (bound %.3g)" % (mode, err.max(), DIR_TOL))
+    assert err.max() <= DIR_TOL, (mode, float(err.max()))
+    if mode == "cosine":
+        assert ((got*normals).sum(axis=-1) >= -DIR_TOL).all()
+    else:
+        assert (got[..., 2] < -0.5).any() and (got[..., 2] > 0.5).any()      # the whole sphere, whatever the normal
+
+
+# ---------------------------------------------------------------------------
+# 3: the batch cut shows nowhere
+
+def test_the_batch_cut_shows_nowhere():
+    pos, nrm = _surface("cornell")
+    n, samples = 1500, 67
+    pick = np.arange(n) % len(pos)
+    pts = tinsel_amd.gather_points(pos[pick], nrm[pick], samples, base_seed=7)
+    assert len(np.unique(pts["seed"])) == n
+    scene, r = _renderer("cornell")
+    try:
+        r.enable_kernel_timing(True)
+        whole = r.gather(pts, samples, DEPTH)
+        assert r.kernel_times()["k_gather_reduce"][0] == 1
+        r.set_batch_paths(65536)
+        per_batch = 65536//samples
+        assert per_batch == 978 and per_batch < n and per_batch % 64 != 0
+        cut, starts = r.gather(pts, samples, DEPTH, return_starts=True)
+        times = r.kernel_times()
+        assert times["k_gather_reduce"][0] == 2 and times["k_generate_gather"][0] == 2, times
+        # one point a batch: batch_paths below the sample count
+        r.set_batch_paths(1024)
+        few = r.gather(pts[970:990], 1500, DEPTH, "sphere")
+        assert r.kernel_times()["k_gather_reduce"][0] == 20
+        r.set_batch_paths(64 << 20)
+        few_whole = r.gather(pts[970:990], 1500, DEPTH, "sphere")
+    finally:
+        r.close()
+    assert whole.any() and np.array_equal(cut, whole) and np.array_equal(few, few_whole)
+    # the records sit at k*S + s whatever batch traced them: those of the points either side of the cut
+    s = starts.reshape(n, samples)
+    w1, _ = tinsel_amd.rng_state(pts["seed"][:, None] + np.arange(samples, dtype=np.uint32)[None, :], 2)
+    assert np.array_equal(s["rng1"], w1) and np.array_equal(s["ox"], np.repeat(pts["px"][:, None], samples, axis=1))
+
+
+# ---------------------------------------------------------------------------
+# 4: the device entry, and what a gather leaves alone
+
+def test_the_device_entry_equals_the_host_entry_and_leaves_the_renderer_alone():
+    import torch
+    pos, nrm = _surface("cornell")
+    n, samples = len(pos), 5
+    pts = tinsel_amd.gather_points(pos, nrm, samples, base_seed=99)
+    scene, r = _renderer("cornell")
+    try:
+        cam, opt = _cam_opt(scene)
+        opt.width, opt.height = 64, 48
+        r.init(64, 48)
+        whole = r.render(cam, opt, passes=2).copy()
+        r.init(64, 48)
+        r.set_pass_index(0)
+        first = r.render(cam, opt, passes=1).copy()
+        before = (r.get_pass_index(), r.get_tuning().as_dict())
+        host, host_starts = r.gather(pts, samples, DEPTH, return_starts=True)
+        s0 = r.stats()
+        dev_pts = torch.from_numpy(pts.view(np.float32).reshape(n, 8).copy()).cuda()
+        dev, dev_starts = r.gather(dev_pts, samples, DEPTH, return_starts=True)
+        assert dev.is_cuda and dev.shape == (n, 4) and dev_starts.is_cuda and dev_starts.shape == (n*samples, 12)
+        dev_only = r.gather(dev_pts, samples, DEPTH)
+        torch.cuda.synchronize()
+        s1 = r.stats()
+        assert s1["samples"] - s0["samples"] == 2*n*samples and s1["rays"] - s0["rays"] >= 2*n*samples
+        assert (r.get_pass_index(), r.get_tuning().as_dict()) == before and before[0] == 1
+        assert r.read_accum().tobytes() == first.tobytes()
+        out = r.render(cam, opt, passes=1)
+        assert r.get_pass_index() == 2
+    finally:
+        r.close()
+    assert host.any() and np.array_equal(dev.cpu().numpy(), host) and np.array_equal(dev_only.cpu().numpy(), host)
+    assert dev_starts.cpu().numpy().tobytes() == host_starts.tobytes()
+    assert not np.array_equal(first, whole) and out.tobytes() == whole.tobytes()
+
+
+# ---------------------------------------------------------------------------
+# 5: bad arguments
+
+def test_bad_arguments_return_minus_one_and_launch_nothing():
+    pos, nrm = _surface("cornell")
+    pts = tinsel_amd.gather_points(pos[:8], nrm[:8], 4)
+    scene, r = _renderer("cornell")
+    try:
+        L, hnd = r._L, r._h
+        r.enable_kernel_timing(True)
+        out = np.full((8, 4), 5.0, np.float32)
+        starts = np.zeros(8*4, abi.PATH_START_DTYPE)
+        pp, op, sp = pts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p)
+        cases = {"null renderer": (None, 0, 8, pp, 4, DEPTH, op, sp), "mode -1": (hnd, -1, 8, pp, 4, DEPTH, op, sp), "mode 2": (hnd, 2, 8, pp, 4, DEPTH, op, sp),
+                 "n < 0": (hnd, 0, -1, pp, 4, DEPTH, op, sp), "n = 2^31": (hnd, 0, 2**31, pp, 4, DEPTH, op, sp),
+                 "samples 0": (hnd, 0, 8, pp, 0, DEPTH, op, sp), "samples 65537": (hnd, 0, 8, pp, 65537, DEPTH, op, sp),
+                 "max_depth 0": (hnd, 0, 8, pp, 4, 0, op, sp), "null points": (hnd, 0, 8, None, 4, DEPTH, op, sp), "null out": (hnd, 0, 8, pp, 4, DEPTH, None, sp)}
+        for what, case in cases.items():
+            assert L.tinsel_hip_gather_radiance(*case) == -1, what
+            assert L.tinsel_hip_last_error().startswith(b"gather_radiance:"), what
+            assert L.tinsel_hip_gather_radiance_device(*case, None) == -1, what
+            assert L.tinsel_hip_last_error().startswith(b"gather_radiance_device:"), what
+        # between a move and the rebuild the scene is not in force
+        last = scene.desc.num_primitives - 1
+        t = abi.Transform.from_buffer_copy(bytes(C.cast(scene.desc.primitives, C.POINTER(abi.Primitive))[last].start_transform))
+        t.p.x += 0.25
+        r.set_primitive_transform(last, t, t)
+        assert L.tinsel_hip_gather_radiance(hnd, 0, 8, pp, 4, DEPTH, op, sp) == -1
+        msg = L.tinsel_hip_last_error()
+        assert msg.startswith(b"gather_radiance:") and b"call tinsel_hip_rebuild_scene first" in msg
+        assert L.tinsel_hip_gather_radiance_device(hnd, 0, 8, pp, 4, DEPTH, op, sp, None) == -1
+        msg = L.tinsel_hip_last_error()
+        assert msg.startswith(b"gather_radiance_device:") and b"call tinsel_hip_rebuild_scene first" in msg
+        # (the scene is judged before n: with a moved primitive n == 0 is refused too, as the header says)
+        assert L.tinsel_hip_gather_radiance(hnd, 0, 0, None, 4, DEPTH, None, None) == -1
+        # n == 0 is not an error, with or without arrays
+        assert r.kernel_times() == {} and (out == 5.0).all() and not starts.view(np.uint32).any()
+        r.rebuild_scene()
+        assert L.tinsel_hip_gather_radiance(hnd, 0, 0, None, 4, DEPTH, None, None) == 0
+        assert L.tinsel_hip_gather_radiance_device(hnd, 1, 0, None, 4, DEPTH, None, None, None) == 0
+        assert r.gather(pts[:0], 4, DEPTH).shape == (0, 4)
+        assert r.kernel_times() == {} and (out == 5.0).all()
+        # and the same call with good arguments answers
+        assert L.tinsel_hip_gather_radiance(hnd, 0, 8, pp, 4, DEPTH, op, sp) == 0
+        times = r.kernel_times()
+        assert times["k_generate_gather"][0] == 1 and times["k_gather_reduce"][0] == 1 and times["k_gather_reduce"][1] > 0, times
+        assert not (out[:, 3] != 0).any() and (out[:, :3] != 5.0).all() and starts["rng1"].all()
+    finally:
+        r.close()
+
+
+# ---------------------------------------------------------------------------
+# 6: the headless tool
+
+def test_headless_irradiance_is_the_gather_times_pi(tmp_path):
+    from tinsel_amd import headless
+    spp = 8
+    path = str(tmp_path / "bake.npz")
+    pack = os.path.join(oa.GOLDEN, "cornell.pack")
+    assert headless.main(["headless", "-irradiance=" + path, "-irradiance_spp=%d" % spp, "-width=%d" % W, "-height=%d" % H, "-maxdepth=%d" % DEPTH, pack]) == 0
+    got = np.load(path)
+    assert sorted(got.files) == ["irradiance", "normal", "primitive", "t"]
+    assert got["irradiance"].shape == (H, W, 3) and got["irradiance"].dtype == np.float32
+    assert got["t"].shape == (H, W) and got["primitive"].shape == (H, W) and got["normal"].shape == (H, W, 3)
+    scene, r = _renderer("cornell")
+    try:
+        cam, _ = _cam_opt(scene)
+        points, t, primitive, normal = r.first_hit_points(cam, W, H)
+        hit = primitive >= 0
+        mean = r.gather(tinsel_amd.gather_points(points[hit], normal[hit], spp), spp, DEPTH, "cosine")
+    finally:
+        r.close()
+    want = np.zeros((H, W, 3), np.float32)
+    want[hit] = mean[:, :3]*np.float32(np.pi)
+    assert np.array_equal(got["primitive"], primitive) and np.array_equal(got["t"], t) and np.array_equal(got["normal"], normal)
+    assert want[hit].any() and np.array_equal(got["irradiance"], want) and not got["irradiance"][~hit].any()

@@ -153,6 +153,18 @@ PATH_START_DTYPE = [("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("time", "<f4")
                     ("rng1", "<u4"), ("rng2", "<u4"), ("reserved1", "<u4"), ("reserved2", "<u4")]
 
 
+class GatherPoint(C.Structure):
+    """tinsel_gather_point: a surface point a gather query starts `samples` paths from -- position (the origin as given), shutter time,
+    normal (unit length, used as given) and the seed of its first sample (sample s draws from Random(seed + s))"""
+    _fields_ = [("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("time", C.c_float),
+                ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float), ("seed", C.c_uint32)]
+
+
+# an (n, 8) array of 32-bit words viewed as GATHER_POINT_DTYPE is a tinsel_gather_point[n]
+GATHER_POINT_DTYPE = [("px", "<f4"), ("py", "<f4"), ("pz", "<f4"), ("time", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("seed", "<u4")]
+GATHER_COSINE, GATHER_SPHERE = 0, 1
+
+
 class KernelTimeV1(C.Structure):
     """tinsel_kernel_time as libraries built before round 4 wrote it (no busy_ms): renderer.HipRenderer.kernel_times"""
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_float)]

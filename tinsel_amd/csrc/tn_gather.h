@@ -1,0 +1,136 @@
+// tn_gather.h -- gather queries (tinsel_hip_gather_radiance*): S paths from each of n surface points, one mean radiance per point back.
+// k_generate_gather is the third generation kernel beside k_generate (the camera's paths) and k_generate_rays (paths the caller starts):
+// a point (tinsel_gather_point, 32 bytes: position, shutter time, normal, seed) and a sample index give the path -- generator
+// Random(seed + s), two draws, a direction about the normal (BasisFromVector + CosineSampleHemisphere, composed as disney.h:256-258 does:
+// U*d.x + V*d.y + N*d.z, summed left to right) or on the sphere (UniformSampleSphere) -- and everything downstream reads buffer 0 of the
+// dense state as it does after k_generate.  k_gather_reduce, behind the pipeline, sums a point's S results in ascending s and divides.
+//
+// The slot <-> (point, sample) map inside a batch of P whole points is SAMPLE-major: slot = s*P + point.  A wave of k_generate_gather then
+// reads 64 consecutive points (2 KiB contiguous, two 16-byte loads per lane typed as HBM like k_generate_rays' records), and a wave of
+// k_gather_reduce, one lane per point, reads 1 KiB contiguous of the batch's radiance per sample; point-major, each of its lanes would
+// stride by 16*S bytes.  The map shows nowhere outside: `startsOut`, where asked for, is written at point*S + s, and a point's sum does not
+// depend on which batch it fell into.  What the map costs: neighbouring lanes hold the same sample of consecutive points, so a wave's three
+// `startsOut` stores land 48*S bytes apart, not coalesced at all -- accepted for a hook the tests and a firefly hunt use; a bake passes null,
+// and the recorded measurement (profiles/r11_gather_query.md) is taken without it.
+#pragma once
+
+#include "tn_radiance.h"
+#include "tn_query.h"
+
+namespace tn {
+
+enum GatherMode : uint32_t { kGatherCosine = 0, kGatherSphere = 1 };
+
+struct GatherJob
+{
+    const void* points;     // tinsel_gather_point[first + count], 16-byte aligned
+    void* startsOut;        // tinsel_path_start[(first + count)*samples], or null: the generated record of path (k, s) at k*samples + s
+    void* out;              // float4[first + count]: k_gather_reduce's means
+    uint32_t first;         // the point of the batch's point 0 (a query of more paths than a batch holds runs as several)
+    uint32_t count;         // whole points of the batch: the batch's paths are slots [0, count*samples), slot = s*count + point
+    uint32_t samples;
+    uint32_t mode;          // GatherMode
+};
+
+__global__ __launch_bounds__(kBlock, 4) void k_generate_gather(SplitState ss, QueueCtl q, GatherJob job, const PrimBox* __restrict__ primBoxes, BinPrims bp)
+{
+    const uint32_t lane = __lane_id();
+    const GlobalF4 points = as_global(job.points) + (size_t)job.first*2u;
+    const GlobalF4Out startsOut = (GlobalF4Out)(uintptr_t)job.startsOut + (size_t)job.first*job.samples*3u;
+    const uint32_t paths = job.count*job.samples;
+    uint32_t samples = 0;
+    for (uint32_t r = blockIdx.x*(kBlock/kWave) + wave_in_block(); r < ss.numRegions; r += gridDim.x*(kBlock/kWave))
+    {
+        const uint32_t begin = region_base(ss, r), rLen = region_len(ss, r);
+        RegionAppend out = { begin, rLen, 0u, 0u };
+        const uint32_t end = (begin + rLen) < paths ? (begin + rLen) : paths;
+        for (uint32_t i0 = begin; i0 < end; i0 += kWave)
+        {
+            const uint32_t slot = i0 + lane;
+            const bool live = slot < end;
+            bool front = true;
+            PathRegs p;
+            if (live)
+            {
+                const uint32_t s = slot/job.count, k = slot - s*job.count;
+                const GlobalF4 rec = points + (size_t)k*2u;
+                const WalkF4 pa = rec[0], pb = rec[1];
+                Rng rng = Rng::seeded(__float_as_uint(pb.w) + s);
+                const float u1 = rng.randf();
+                const float u2 = rng.randf();
+                V3 d;
+                if (job.mode == kGatherSphere)
+                    d = uniform_sample_sphere(u1, u2);
+                else
+                {
+                    const V3 n(pb.x, pb.y, pb.z);
+                    V3 u, v;
+                    basis_from_vector(n, u, v);
+                    const V3 c = cosine_sample_hemisphere(u1, u2);
+                    d = u*c.x + v*c.y + n*c.z;
+                }
+                path_begin(p, V3(pa.x, pa.y, pa.z), d, pa.w, rng);
+                // rays that enter a mesh in HBM in front (k_walk takes those), as k_generate sorts the camera's
+                front = bp.count == 0 || ray_enters_big_mesh(primBoxes, bp, p.o, p.d);
+                samples++;
+                if (job.startsOut)
+                {
+                    const GlobalF4Out so = startsOut + ((size_t)k*job.samples + s)*3u;
+                    WalkF4 w0, w1, w2;
+                    w0.x = p.o.x; w0.y = p.o.y; w0.z = p.o.z; w0.w = p.time;
+                    w1.x = p.d.x; w1.y = p.d.y; w1.z = p.d.z; w1.w = 0.0f;
+                    w2.x = __uint_as_float(rng.s1); w2.y = __uint_as_float(rng.s2); w2.z = 0.0f; w2.w = 0.0f;
+                    so[0] = w0;
+                    so[1] = w1;
+                    so[2] = w2;
+                }
+            }
+            const uint32_t pos = out.push(live, front);
+            if (live)
+            {
+                // ray and RNG only, as k_generate: the rest of a fresh path's state is constant and k_shade knows it (ShadeFetch::issue)
+                ss.rayO[0][pos] = make_float4(p.o.x, p.o.y, p.o.z, p.time);
+                ss.rayD[0][pos] = make_float4(p.d.x, p.d.y, p.d.z, p.bsdfPdf);
+                ss.rngId[0][pos] = make_float4(__uint_as_float(p.rng.s1), __uint_as_float(p.rng.s2), __uint_as_float(slot), __int_as_float(-1));
+            }
+        }
+        if (lane == 0)
+        {
+            ss.segFront[r] = out.nFront;
+            ss.segBack[r] = out.nBack;
+        }
+    }
+    wave_add_stat(q.stats, 1, samples);
+}
+
+// One lane per point of the batch: out[first + k] = (rad[k] + rad[count + k] + ... in ascending s, fp32) / (float)samples, word 3 zero.
+// The additions stay in order; four loads are in flight ahead of them.
+__global__ __launch_bounds__(kBlock) void k_gather_reduce(const float4* __restrict__ rad, GatherJob job)
+{
+    const uint32_t k = blockIdx.x*kBlock + threadIdx.x;
+    if (k >= job.count)
+        return;
+    const GlobalF4 src = as_global(rad) + k;
+    const size_t stride = job.count;
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+    uint32_t s = 0;
+    for (; s + 4 <= job.samples; s += 4)
+    {
+        const WalkF4 a = src[(size_t)s*stride], b = src[(size_t)(s + 1)*stride], c = src[(size_t)(s + 2)*stride], d = src[(size_t)(s + 3)*stride];
+        x = x + a.x; y = y + a.y; z = z + a.z;
+        x = x + b.x; y = y + b.y; z = z + b.z;
+        x = x + c.x; y = y + c.y; z = z + c.z;
+        x = x + d.x; y = y + d.y; z = z + d.z;
+    }
+    for (; s < job.samples; ++s)
+    {
+        const WalkF4 a = src[(size_t)s*stride];
+        x = x + a.x; y = y + a.y; z = z + a.z;
+    }
+    const float count = (float)job.samples;
+    WalkF4 mean;
+    mean.x = x/count; mean.y = y/count; mean.z = z/count; mean.w = 0.0f;
+    ((GlobalF4Out)(uintptr_t)job.out)[(size_t)job.first + k] = mean;
+}
+
+} // namespace tn

@@ -193,6 +193,59 @@ int tinsel_hip_trace_radiance(tinsel_hip* r, long long n, const tinsel_path_star
     return 0;
 }
 
+// Gather queries (tn_gather.h, tn_host_gather.h): `samples` paths from each point, drawn on the device, one mean per point.  As radiance
+// queries: nothing of the renderer's frame state is touched, rays and samples are counted.
+int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
+                                      float* out_rgbx_dev, tinsel_path_start* starts_out_dev, void* stream)
+{
+    if (gather_args(r, mode, n, points_dev, samples, max_depth, out_rgbx_dev, "gather_radiance_device"))
+        return -1;
+    const uintptr_t arr[3] = { (uintptr_t)points_dev, (uintptr_t)out_rgbx_dev, (uintptr_t)starts_out_dev };
+    const uintptr_t bytes[3] = { (uintptr_t)n*sizeof(tinsel_gather_point), (uintptr_t)n*sizeof(float4),
+                                 starts_out_dev ? (uintptr_t)n*(uintptr_t)samples*sizeof(tinsel_path_start) : 0 };
+    for (int i = 0; i < 3; ++i)
+    {
+        if (arr[i] & 15u)
+            return fail("gather_radiance_device: the arrays must be 16-byte aligned");
+        for (int j = 0; j < i; ++j)
+            if (bytes[i] && bytes[j] && arr[i] < arr[j] + bytes[j] && arr[j] < arr[i] + bytes[i])
+                return fail("gather_radiance_device: the arrays overlap");
+    }
+    if (query_ready(r, "gather_radiance_device"))
+        return -1;
+    if (n == 0)
+        return 0;
+    return trace_gather(r, mode, (size_t)n, points_dev, samples, max_depth, (float4*)out_rgbx_dev, starts_out_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
+                               float* out_rgbx_host, tinsel_path_start* starts_out_host)
+{
+    if (gather_args(r, mode, n, points_host, samples, max_depth, out_rgbx_host, "gather_radiance") || query_ready(r, "gather_radiance"))
+        return -1;
+    const size_t chunk = gather_chunk((size_t)n, samples, starts_out_host != nullptr);
+    if (chunk == 0)
+        return 0;
+    const size_t startBytes = sizeof(tinsel_path_start)*(size_t)samples;
+    if (query_buffer(r->queryRaysDev, chunk*sizeof(tinsel_gather_point)) || query_buffer(r->queryOutDev, chunk*sizeof(float4)) ||
+        (starts_out_host && query_buffer(r->gatherStartsDev, chunk*startBytes)))
+        return -1;
+    unsigned char* const pointsDev = r->queryRaysDev.get();
+    float4* const outDev = (float4*)r->queryOutDev.get();
+    unsigned char* const startsDev = starts_out_host ? r->gatherStartsDev.get() : nullptr;
+    for (size_t done = 0; done < (size_t)n; done += chunk)
+    {
+        const size_t m = std::min(chunk, (size_t)n - done);
+        HIP_TRY(hipMemcpy(pointsDev, points_host + done, m*sizeof(tinsel_gather_point), hipMemcpyHostToDevice));
+        if (trace_gather(r, mode, m, pointsDev, samples, max_depth, outDev, startsDev, nullptr))
+            return -1;
+        HIP_TRY(hipMemcpy(out_rgbx_host + done*4, outDev, m*sizeof(float4), hipMemcpyDeviceToHost));
+        if (startsDev)
+            HIP_TRY(hipMemcpy((unsigned char*)starts_out_host + done*startBytes, startsDev, m*startBytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -1076,8 +1076,9 @@ int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L
         *grid = std::max(1, std::min(*grid, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
     if (cut_batch(p, L, a, slots, grid))
         return -1;
-    // (the plan says which paths: the camera's, or a radiance query's -- k_generate_rays reads a.radiance and no camera)
-    ScopedTimer t(r, p.generate == PK_GENERATE_RAYS ? KN_GENERATE_RAYS : KN_GENERATE, st);
+    // (the plan says which paths: the camera's, a radiance query's -- k_generate_rays reads a.radiance and no camera -- or a gather
+    // query's: k_generate_gather reads a.gather)
+    ScopedTimer t(r, p.generate == PK_GENERATE_RAYS ? KN_GENERATE_RAYS : p.generate == PK_GENERATE_GATHER ? KN_GENERATE_GATHER : KN_GENERATE, st);
     a.grid = *grid;
     a.variant = p.generate;
     a.ldsBytes = 0;
@@ -1276,13 +1277,21 @@ size_t batch_frame(const tinsel_hip* r, FrameParams& fp)
     return slots;
 }
 
-// The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
-// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance query, tn_host_radiance.h -- the split or the paired pipeline
-// behind k_generate_rays, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
-int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
-                size_t slots, const RadianceJob* starts = nullptr)
+// The paths of a batch that the camera does not produce, by the generation kernel that makes them: exactly one is set
+struct CallerPaths
 {
-    if (starts && (p.generate != PK_GENERATE_RAYS || (p.pipeline != TINSEL_PIPELINE_WAVEFRONT_SPLIT && p.pipeline != TINSEL_PIPELINE_WAVEFRONT_PAIRED)))
+    const RadianceJob* rays = nullptr;      // a radiance query's records (k_generate_rays, tn_host_radiance.h)
+    const GatherJob* gather = nullptr;      // a gather query's points (k_generate_gather, tn_host_gather.h)
+    int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : PK_NONE; }
+};
+
+// The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
+// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query -- the split or the paired pipeline
+// behind k_generate_rays / k_generate_gather, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
+int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
+                size_t slots, const CallerPaths* starts = nullptr)
+{
+    if (starts && (p.generate != starts->generate() || (p.pipeline != TINSEL_PIPELINE_WAVEFRONT_SPLIT && p.pipeline != TINSEL_PIPELINE_WAVEFRONT_PAIRED)))
         return fail("trace_batch: caller-started paths run the split or the paired pipeline");
     r->lastPipeline = p.pipeline;
 
@@ -1294,8 +1303,10 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     a.ctl = r->ctl;
     if (cam)
         a.cam = *cam;
-    if (starts)
-        a.radiance = *starts;
+    if (starts && starts->rays)
+        a.radiance = *starts->rays;
+    if (starts && starts->gather)
+        a.gather = *starts->gather;
     a.fp = fp;
     a.passSeeds = r->passSeeds;
     a.walkRec = p.walk ? L.walkRec : nullptr;

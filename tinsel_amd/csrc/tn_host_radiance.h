@@ -51,10 +51,12 @@ int trace_radiance(tinsel_hip* r, size_t n, const void* starts, float4* out, int
     {
         const size_t m = std::min(perBatch, n - done);
         const RadianceJob job = { starts, (uint32_t)done, (uint32_t)m };
+        CallerPaths paths;
+        paths.rays = &job;
         fp.genCount = (uint32_t)m;
         r->lastLane = 0;
         // (ss.radOut is the caller's array at the batch's first record: a finished path writes out[done + slot] itself)
-        if (trace_batch(r, plan, r->lane[0], st, nullptr, fp, out + done, m, &job))
+        if (trace_batch(r, plan, r->lane[0], st, nullptr, fp, out + done, m, &paths))
             return -1;
     }
     HIP_TRY(hipGetLastError());

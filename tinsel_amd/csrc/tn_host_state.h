@@ -170,6 +170,9 @@ struct tinsel_hip
     Event batchFence, queryFork[2];
     hipStream_t batchFenceStream = nullptr;
     bool batchFencePending = false;
+    // gather queries (tinsel_hip_gather_radiance*, tn_host_gather.h): the radiance of a batch's paths by slot, which k_gather_reduce reads;
+    // grown on demand, and the host entry's tinsel_path_start records where the caller asks for them
+    DevBuf<unsigned char> gatherRad, gatherStartsDev;
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)

@@ -3,6 +3,7 @@
     python -m tinsel_amd.headless [-spp=N] [-width=W] [-height=H] [-exposure=E] [-maxdepth=D]
                                   [-nlm=RADIUS[,FALLOFF]] [-rr=BOUNCE] [-out=image.png|image.pfm] [-save=state.npz] [-resume=state.npz]
                                   [-complexity=rays|nodes|tris|prims] [-firsthit=buffers.npz]
+                                  [-irradiance=bake.npz] [-irradiance_spp=N]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -31,6 +32,11 @@ frame's mean per sample of all four channels is printed.
 -firsthit=FILE.npz writes the first-hit buffers of the scene's camera at the frame size (HipRenderer.first_hit: `t` [H, W], `primitive`
 [H, W], -1 where the ray leaves the scene, `normal` [H, W, 3] turned towards the camera; the pose of time 1, as the normals view) and
 exits without rendering: what a denoiser or a compositor reads beside the image.
+-irradiance=FILE.npz bakes the irradiance at those first-hit points (HipRenderer.first_hit_points: moved off the surface along the turned
+normal by the reference's ray epsilon) with a gather query in cosine mode, -irradiance_spp paths per point (default 64) to -maxdepth:
+`irradiance` [H, W, 3] = the mean radiance * pi, 0 where the ray left the scene, with `t`, `primitive` and `normal` beside it; point k
+(the hit pixels in row order) draws from the seeds k*spp .. k*spp + spp - 1.  Exits without rendering, like -firsthit: the options that
+belong to a render (-out, -save, -resume, -nlm, -spp), -firsthit, -complexity and batch mode are refused beside it.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -42,7 +48,7 @@ import numpy as np
 
 from . import abi
 from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
-from .renderer import Scene, create_gpu_renderer
+from .renderer import Scene, create_gpu_renderer, gather_points
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
 
@@ -50,7 +56,8 @@ FRAME_PASSES = 16          # numSamples of main.cpp:240
 def parse_args(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
-    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "over": {}}
+    cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
+           "irradiance_spp": 64, "over": {}}
     for a in argv[1:-1]:
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
@@ -64,8 +71,12 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance"):
             cfg[k] = v
+        elif k == "irradiance_spp":
+            cfg[k] = int(v)
+            if not 1 <= cfg[k] <= 65536:
+                raise SystemExit("-irradiance_spp=%s: want 1 .. 65536" % v)
         elif k == "complexity":
             if v not in COST_CHANNELS:
                 raise SystemExit("-complexity=%s: want one of %s" % (v, "|".join(COST_CHANNELS)))
@@ -166,12 +177,30 @@ def complexity(r, cam, opt, cfg):
         print("wrote %s" % cfg["out"])
 
 
+def irradiance(r, cam, opt, cfg):
+    """-irradiance: a gather query in cosine mode at the frame's first-hit points"""
+    spp = cfg["irradiance_spp"]
+    points, t, primitive, normal = r.first_hit_points(cam, opt.width, opt.height)
+    hit = primitive >= 0
+    ts = time.perf_counter()
+    mean = r.gather(gather_points(points[hit], normal[hit], spp), spp, opt.max_depth, "cosine")
+    ms = (time.perf_counter() - ts)*1000.0
+    out = np.zeros((opt.height, opt.width, 3), np.float32)
+    out[hit] = mean[:, :3]*np.float32(np.pi)
+    np.savez(cfg["irradiance"], irradiance=out, t=t, primitive=primitive, normal=normal)
+    print("wrote %s: %dx%d, %d points x %d paths in %.3fms" % (cfg["irradiance"], opt.width, opt.height, int(hit.sum()), spp, ms))
+
+
 def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
     if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
         raise SystemExit("-complexity renders one cost map: no batch mode, -save or -resume")
     if cfg["firsthit"] and ("%" in cfg["file"] or cfg["complexity"]):
         raise SystemExit("-firsthit writes one frame's buffers: no batch mode, no -complexity")
+    if cfg["irradiance"] and ("%" in cfg["file"] or cfg["complexity"] or cfg["firsthit"] or cfg["out"] or cfg["save"] or cfg["resume"] or
+                              cfg["nlm"] or "spp" in cfg["over"]):
+        raise SystemExit("-irradiance bakes one frame's points and renders nothing: no batch mode, no -complexity, -firsthit, -out, -save, "
+                         "-resume, -nlm or -spp (the paths per point are -irradiance_spp)")
     if "%" in cfg["file"]:
         return batch(cfg)
     t0 = time.perf_counter()
@@ -188,6 +217,10 @@ def main(argv=None):
         return 0
     if over.get("rr", 0) > 0:
         r.set_russian_roulette(over["rr"])       # opt-in; not the reference's behaviour (tinsel_hip.h)
+    if cfg["irradiance"]:
+        irradiance(r, cam, opt, cfg)
+        r.close()
+        return 0
     r.init(opt.width, opt.height)
     print("Created renderer in %fms" % ((time.perf_counter() - t0)*1000.0))
     if cfg["complexity"]:

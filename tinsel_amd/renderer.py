@@ -93,6 +93,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_trace_radiance"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_trace_radiance.argtypes = [vp, C.c_longlong, vp, ci, vp]
         L.tinsel_hip_trace_radiance_device.argtypes = [vp, C.c_longlong, vp, ci, vp, vp]
+    if hasattr(L, "tinsel_hip_gather_radiance"):
+        L.tinsel_hip_gather_radiance.argtypes = [vp, ci, C.c_longlong, vp, ci, ci, vp, vp]
+        L.tinsel_hip_gather_radiance_device.argtypes = [vp, ci, C.c_longlong, vp, ci, ci, vp, vp, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -169,6 +172,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_comm_unique_id", "tinsel_hip_comm_init", "tinsel_hip_comm_size", "tinsel_hip_comm_reduce_accum",
     "tinsel_hip_trace_rays", "tinsel_hip_trace_rays_device", "tinsel_hip_trace_camera",
     "tinsel_hip_trace_radiance", "tinsel_hip_trace_radiance_device",
+    "tinsel_hip_gather_radiance", "tinsel_hip_gather_radiance_device",
 ]
 
 
@@ -183,6 +187,44 @@ def rng_state(seed, skip=0):
         s1 = (s2 ^ ((s1 << np.uint32(5)) | (s1 >> np.uint32(27)))) ^ (s1*s2)
         s2 = s1 ^ ((s2 << np.uint32(12)) | (s2 >> np.uint32(20)))
     return s1.reshape(shape), s2.reshape(shape)
+
+
+RAY_EPSILON = 1e-4         # the reference's kRayEpsilon (render.cpp:11): how far a path's next origin is moved off the surface it left
+
+
+def camera_rays(camera, width, height):
+    """CameraSampler::GenerateRay(i, j) of every pixel of a width x height frame (util.h:45-79; the raster position is the pixel's integer
+    corner, as trace_camera / first_hit shoot it), restated in float64: (origin [3], unit directions [H, W, 3]).  For placing points on what
+    first_hit saw -- the device's own rays are float32, so origin + direction*t lies on the surface to rounding, not to the bit."""
+    jj, ii = np.mgrid[0:int(height), 0:int(width)].astype(np.float64)
+    f = np.tan(np.float64(camera.fov)*0.5)
+    v = np.stack([f*(float(width)/float(height))*(2.0*ii/width - 1.0), f*(1.0 - 2.0*jj/height), -np.ones_like(ii)], axis=-1)
+    q = np.array([camera.rotation.x, camera.rotation.y, camera.rotation.z], np.float64)
+    w = np.float64(camera.rotation.w)
+    t = 2.0*np.cross(q, v)
+    d = v + w*t + np.cross(q, t)
+    origin = np.array([camera.position.x, camera.position.y, camera.position.z], np.float64)
+    return origin, d/np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+GATHER_MODES = {"cosine": abi.GATHER_COSINE, "sphere": abi.GATHER_SPHERE}
+
+
+def gather_points(positions, normals, samples, time=1.0, base_seed=0, seeds=None):
+    """The point array of a gather query (abi.GATHER_POINT_DTYPE, one record per row of `positions`): positions [n, 3] (the origins as
+    given: offset them off the surface first), normals [n, 3] (unit length), `time` a scalar or [n], and the seeds -- by default
+    seed_k = base_seed + k*samples modulo 2^32, so that the points' streams (seed_k + s, s < samples) do not meet; `seeds` [n] overrides."""
+    positions = np.asarray(positions, np.float32).reshape(-1, 3)
+    n = positions.shape[0]
+    pts = np.zeros(n, abi.GATHER_POINT_DTYPE)
+    pts["px"], pts["py"], pts["pz"] = positions[:, 0], positions[:, 1], positions[:, 2]
+    normals = np.asarray(normals, np.float32).reshape(n, 3)
+    pts["nx"], pts["ny"], pts["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
+    pts["time"] = np.asarray(time, np.float32)
+    if seeds is None:
+        seeds = (int(base_seed) + np.arange(n, dtype=np.uint64)*np.uint64(int(samples))) & np.uint64(0xffffffff)
+    pts["seed"] = np.asarray(seeds).astype(np.uint32)
+    return pts
 
 
 def _check(rc, what):
@@ -564,6 +606,47 @@ class HipRenderer:
         _check(self._L.tinsel_hip_trace_radiance(self._h, n, keep_s.ctypes.data_as(C.c_void_p), max_depth, keep_o.ctypes.data_as(C.c_void_p)), "tinsel_hip_trace_radiance")
         return out
 
+    def gather(self, points, samples, max_depth, mode="cosine", return_starts=False):
+        """Gather queries on the resident scene (tinsel_hip_gather_radiance*): `samples` paths from each point, drawn on the device --
+        sample s of point k from Random(seed_k + s), two draws, a cosine-weighted direction about the normal (mode "cosine": mean * pi is
+        the irradiance) or a uniform one on the sphere ("sphere": the mean incident radiance) -- path-traced as radiance() traces them and
+        summed in ascending s: float32 (n, 4) = mean radiance rgb + 0.  `points`: a numpy array of abi.GATHER_POINT_DTYPE (gather_points)
+        or an (n, 8) array of 32-bit words holding the same 32-byte records, the host entry; a contiguous (n, 8) float32 / int32 torch
+        tensor on this renderer's device goes to the device entry on torch's current stream, no copy made and not waited for, and a
+        device tensor comes back.  return_starts: also the generated abi.PathStart records, path (k, s) at k*samples + s -- a numpy
+        array of abi.PATH_START_DTYPE, or an (n*samples, 12) float32 tensor -- which radiance() accepts as they are.  Scene, settings,
+        statistics and what is left alone: as radiance()."""
+        samples, max_depth, m = int(samples), int(max_depth), GATHER_MODES[mode] if isinstance(mode, str) else int(mode)
+        if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):
+            import torch
+            if points.dtype not in (torch.float32, torch.int32) or points.dim() != 2 or points.shape[1] != 8 or not points.is_contiguous() or not points.is_cuda:
+                raise ValueError("gather: a contiguous (n, 8) float32 or int32 tensor on the GPU is expected")
+            if points.device.index != self.device:
+                raise ValueError("gather: the tensor is on %s, the renderer on device %d" % (points.device, self.device))
+            n = int(points.shape[0])
+            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            starts = torch.empty((n*max(samples, 0), 12), dtype=torch.float32, device=points.device) if return_starts else None
+            if n:
+                stream = torch.cuda.current_stream(points.device).cuda_stream
+                _check(self._L.tinsel_hip_gather_radiance_device(self._h, m, n, points.data_ptr(), samples, max_depth, out.data_ptr(),
+                                                                 starts.data_ptr() if return_starts else None, stream), "tinsel_hip_gather_radiance_device")
+            return (out, starts) if return_starts else out
+        points = np.asarray(points)
+        if points.dtype == np.dtype(abi.GATHER_POINT_DTYPE) and points.ndim == 1:
+            words = np.ascontiguousarray(points)
+        elif points.dtype.itemsize == 4 and points.dtype.kind in "fiu" and points.ndim == 2 and points.shape[1] == 8:
+            words = np.ascontiguousarray(points)
+        else:
+            raise ValueError("gather: an array of abi.GATHER_POINT_DTYPE or an (n, 8) array of 32-bit words is expected")
+        n = words.shape[0]
+        out = np.zeros((n, 4), np.float32)
+        starts = np.zeros(n*max(samples, 0), abi.PATH_START_DTYPE) if return_starts else None
+        # (an empty array's data pointer may be null: hand the library addresses it can check)
+        keep_p, keep_o = (words, out) if n else (np.zeros((1, 8), np.float32), np.zeros((1, 4), np.float32))
+        _check(self._L.tinsel_hip_gather_radiance(self._h, m, n, keep_p.ctypes.data_as(C.c_void_p), samples, max_depth, keep_o.ctypes.data_as(C.c_void_p),
+                                                  starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), "tinsel_hip_gather_radiance")
+        return (out, starts) if return_starts else out
+
     def trace_camera(self, camera, width, height, time=1.0):
         """tinsel_hip_trace_camera: the closest hit of GenerateRay(i, j) of every pixel (no jitter), an [H, W] record array of abi.RAY_HIT_DTYPE"""
         out = np.zeros((int(height), int(width)), abi.RAY_HIT_DTYPE)
@@ -577,6 +660,15 @@ class HipRenderer:
         rec = self.trace_camera(camera, width, height, time)
         normal = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1)
         return np.ascontiguousarray(rec["t"]), np.ascontiguousarray(rec["primitive"]), normal
+
+    def first_hit_points(self, camera, width, height, time=1.0, epsilon=RAY_EPSILON):
+        """The surface points a frame's camera rays reach first, ready for gather(): (points [H, W, 3] float32 = origin + direction*t moved
+        `epsilon` along the normal turned towards the camera, 0 at a miss; t, primitive, normal as first_hit gives them)"""
+        t, primitive, normal = self.first_hit(camera, width, height, time)
+        origin, d = camera_rays(camera, width, height)
+        hit = primitive >= 0
+        points = origin + d*np.where(hit, t, 0.0)[..., None] + normal.astype(np.float64)*float(epsilon)
+        return np.where(hit[..., None], points, 0.0).astype(np.float32), t, primitive, normal
 
     def enable_kernel_timing(self, on):
         _check(self._L.tinsel_hip_enable_kernel_timing(self._h, int(on)), "tinsel_hip_enable_kernel_timing")
