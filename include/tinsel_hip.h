@@ -206,7 +206,7 @@ typedef struct tinsel_hip_tuning {
     int32_t overlap;            /* -1 auto | 0 / 1: a batch's passes as two overlapped chunks on two streams: never / wherever it has two passes */
     int32_t scene_walk;         /* -1 auto | 0: scenes beyond the flat scan through k_extend / k_shadow instead of k_swalk */
     int32_t swalk_lds;          /* -1 auto | 0: k_swalk's 256-thread generic-pointer variant */
-    int32_t accumulate;         /* 0 auto | TINSEL_ACCUMULATE_TILED / _WIDE / _PIPED (filter widths up to 1) */
+    int32_t accumulate;         /* 0 auto | TINSEL_ACCUMULATE_TILED / _WIDE / _PIPED (filter widths up to 1) | _FULL_WINDOW: auto, but never the support form */
     int32_t walk_block;         /* 0 auto | 256 / 1024: k_walk's workgroup size */
     int32_t walk_single;        /* -1 auto | 0: per-lane tree pointers (k_walk_rays) also for ONE walked primitive */
     int32_t walk_lds_stack;     /* -1 default (8) | stack entries per lane kept in LDS (0: all of them, one workgroup per CU) */
@@ -216,7 +216,7 @@ typedef struct tinsel_hip_tuning {
     int32_t quads_in_scan;      /* -1 auto | 0: a quad (two-triangle mesh: a lamp) beside meshes walked by k_walk sends the scene to the general scan kernels (inline mesh walk compiled in) */
     int32_t bounce_fit;         /* -1 auto | 0: k_bounce's general instance even where one compiled for the scene's feature set exists */
 } tinsel_hip_tuning;
-enum { TINSEL_ACCUMULATE_AUTO = 0, TINSEL_ACCUMULATE_TILED = 1, TINSEL_ACCUMULATE_WIDE = 2, TINSEL_ACCUMULATE_PIPED = 3 };
+enum { TINSEL_ACCUMULATE_AUTO = 0, TINSEL_ACCUMULATE_TILED = 1, TINSEL_ACCUMULATE_WIDE = 2, TINSEL_ACCUMULATE_PIPED = 3, TINSEL_ACCUMULATE_FULL_WINDOW = 4 };
 
 /* Fills `t` with the defaults ("the library decides" everywhere). */
 void tinsel_hip_tuning_init(tinsel_hip_tuning* t);
@@ -642,6 +642,20 @@ int tinsel_hip_selftest_arith(int device_index, int op, int variant, unsigned lo
  * out[i] = in[0] + .. + in[i - 1]. */
 int tinsel_hip_selftest_sort(int device_index, unsigned long long* keys, unsigned long long n, int begin_bit, int end_bit);
 int tinsel_hip_selftest_scan(int device_index, const int* in, int* out, unsigned long long n);
+/* Does the accumulate stage take its support form for this filter (1) or not (0)?  The form gathers, per pixel, only the samples generated at the
+ * pixel and its upper / left neighbours: a Gaussian filter of width <= 1 with offset > 0 whose weight max(0, expf(a) - offset) is +0 by
+ * construction from one pixel away on -- a = -falloff*x*x <= *out_arg_zero = log(offset) - 1e-6 (double, rounded down to float) for |x| >= 1.
+ * Host arithmetic only; out_arg_zero may be NULL. */
+int tinsel_hip_accumulate_support(int filter_type, float filter_width, float filter_falloff, float filter_offset, float* out_arg_zero);
+/* The accumulate stage (the reference's CpuRenderer::AddSample, render.cpp:401-445, over whole passes) on caller data, for tests: the paths of pass s
+ * generated at pixel (i, j) have the raster position Random(i + j*width + pass_seeds[s]) draws and the radiance radiance[(s*height + j)*width + i]
+ * (rgbx); they are added to accum[height*width] (rgba, in/out) by exactly the launch a render of such a frame makes on this device (one shard).
+ * choice: tinsel_hip_tuning::accumulate.  form 0: as the library decides | 1: the full candidate window | 2: the support form (Gaussian filters
+ * whose weight is +0 by construction a pixel away from the sample; an error where the filter or the chosen kernel has no such form).
+ * *out_form: what ran -- 0 k_accumulate | 1 k_accumulate_tiled, 256 threads | 2 the same, 512 | 3 k_accumulate_piped | 4 / 5 the support form of 1 / 2. */
+int tinsel_hip_selftest_accumulate(int device_index, int width, int height, int filter_type, float filter_width, float filter_falloff, float filter_offset,
+                                   float clamp, const unsigned int* pass_seeds, int passes, const float* radiance, float* accum, int choice, int form,
+                                   int* out_form);
 
 /* Yard-sticks measured on the GPU itself, for bench.py's roofline (not part of the render path): kind 0 = a float4 stream
  * copy of `bytes` bytes (*out_units = bytes read + written); kinds 1..3 = dependent chases through a table of 64-B records

@@ -216,7 +216,33 @@ class Tuning(C.Structure):
         return {k: getattr(self, k) for k in self._DEFAULTS}
 
 
-ACCUMULATE_AUTO, ACCUMULATE_TILED, ACCUMULATE_WIDE, ACCUMULATE_PIPED = 0, 1, 2, 3
+ACCUMULATE_AUTO, ACCUMULATE_TILED, ACCUMULATE_WIDE, ACCUMULATE_PIPED, ACCUMULATE_FULL_WINDOW = 0, 1, 2, 3, 4
+# tinsel_hip_selftest_accumulate: the form asked for, the form that ran
+ACCUMULATE_FORM_AUTO, ACCUMULATE_FORM_FULL_WINDOW, ACCUMULATE_FORM_SUPPORT = 0, 1, 2
+ACCUMULATE_RAN_UNTILED, ACCUMULATE_RAN_TILED, ACCUMULATE_RAN_WIDE, ACCUMULATE_RAN_PIPED, ACCUMULATE_RAN_SUPPORT_TILED, ACCUMULATE_RAN_SUPPORT_WIDE = 0, 1, 2, 3, 4, 5
+SELFTEST_ACCUMULATE_ARGTYPES = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_int, C.c_int, C.POINTER(C.c_int)]
+
+
+def accumulate_arg_zero(offset):
+    """The expf argument at and below which Filter::Gaussian's weight max(0, expf(a) - offset) is +0 by construction: log(offset) - 1e-6 in
+    double, rounded down to float (launch_accumulate's rule, tn_host_batch.h)."""
+    import math
+    import numpy as np
+    z = math.log(float(np.float32(offset))) - 1e-6
+    f = np.float32(z)
+    if float(f) > z:
+        f = np.nextafter(f, np.float32(-np.inf))
+    return f
+
+
+def accumulate_takes_support_form(filter_type, width, falloff, offset):
+    """launch_accumulate's rule (accumulate_support_rule, tn_host_batch.h) restated: does k_accumulate_tiled run in its support form for this filter?"""
+    import numpy as np
+    width, falloff, offset = np.float32(width), np.float32(falloff), np.float32(offset)
+    if filter_type == FILTER_BOX or not (offset > 0 and np.isfinite(offset)) or not (falloff > 0 and np.isfinite(falloff)) or not (0 < width <= 1):
+        return False
+    return bool(-falloff <= accumulate_arg_zero(offset))
 COMM_ID_BYTES = 128
 MODE_NORMALS, MODE_COMPLEXITY, MODE_PATHTRACE = 0, 1, 2
 BVH_REFERENCE, BVH_LBVH, BVH_PLOC = 0, 1, 2

@@ -570,7 +570,7 @@ int tinsel_hip_set_tuning(tinsel_hip* r, const tinsel_hip_tuning* tuning)
     lookahead_cancel(r);
     tinsel_hip_tuning t = tuning_from_caller(tuning);
     if (t.grid_mult < 0 || t.grid_mult > 256 || (t.walk_block != 0 && t.walk_block != 256 && t.walk_block != 1024) ||
-        t.accumulate < TINSEL_ACCUMULATE_AUTO || t.accumulate > TINSEL_ACCUMULATE_PIPED || t.walk_refill_min > 64 || t.walk_leaf_min > 64 || t.walk_grid_mult < 0 || t.walk_grid_mult > 64 ||
+        t.accumulate < TINSEL_ACCUMULATE_AUTO || t.accumulate > TINSEL_ACCUMULATE_FULL_WINDOW || t.walk_refill_min > 64 || t.walk_leaf_min > 64 || t.walk_grid_mult < 0 || t.walk_grid_mult > 64 ||
         (t.tail_split > 0 && (!(t.tail_share >= 0.0f) || t.tail_divide < 1)) || (t.batch_paths != 0 && t.batch_paths < 1024))
         return fail("set_tuning: a field is out of range");
     HIP_TRY(hipSetDevice(r->device));
@@ -851,6 +851,73 @@ int tinsel_hip_selftest_scan(int device_index, const int* in, int* out, unsigned
     exclusive_scan(a.get(), a.get(), (size_t)n, scratch.get(), nullptr);         // (in place, as the builder's radix passes use it)
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(out, a.get(), n*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         return fail("selftest_scan: kernels failed");
+    return 0;
+}
+
+// launch_accumulate's rule (accumulate_support_rule), for callers and tests: host arithmetic only
+int tinsel_hip_accumulate_support(int filter_type, float filter_width, float filter_falloff, float filter_offset, float* out_arg_zero)
+{
+    float z = 0.0f;
+    const bool takes = accumulate_support_rule(filter_type, filter_width, filter_falloff, filter_offset, &z);
+    if (out_arg_zero)
+        *out_arg_zero = z;
+    return takes ? 1 : 0;
+}
+
+// The accumulate stage on caller data: radiance[passes][height][width] (rgbx) added to accum[height][width] (rgba) by exactly the launch
+// launch_accumulate makes for such a frame on this device (one shard).  choice: tinsel_hip_tuning::accumulate; form 0: as the library
+// decides, 1: the full window, 2: the support form (an error where the filter or the chosen kernel has none).  *out_form: what ran.
+int tinsel_hip_selftest_accumulate(int device_index, int width, int height, int filter_type, float filter_width, float filter_falloff, float filter_offset,
+                                   float clamp, const unsigned int* pass_seeds, int passes, const float* radiance, float* accum, int choice, int form,
+                                   int* out_form)
+{
+    if (width < 1 || height < 1 || passes < 1 || !pass_seeds || !radiance || !accum || !out_form || form < 0 || form > 2 ||
+        choice < TINSEL_ACCUMULATE_AUTO || choice > TINSEL_ACCUMULATE_FULL_WINDOW || (size_t)width*height*passes >= ((size_t)1 << 31))
+        return fail("selftest_accumulate: bad arguments");
+    HIP_TRY(hipSetDevice(device_index));
+    int numCUs = 0;
+    HIP_TRY(hipDeviceGetAttribute(&numCUs, hipDeviceAttributeMultiprocessorCount, device_index));
+    const size_t npix = (size_t)width*height;
+    FrameParams fp = {};                    // (frame_params + batch_frame for one unsharded batch of `passes` passes)
+    fp.width = width;
+    fp.height = height;
+    fp.npixM = 0xffffffffu/(uint32_t)npix;
+    fp.widthM = 0xffffffffu/(uint32_t)width;
+    fp.shardRank = 0; fp.shardWorld = 1; fp.shardTile = 32;
+    fp.shardPerPass = (uint32_t)npix;
+    fp.filterType = filter_type;
+    fp.filterWidth = filter_width;
+    fp.filterFalloff = filter_falloff;
+    fp.filterOffset = filter_offset;
+    fp.clampLen = clamp;
+    fp.passBase = 0;
+    fp.numPasses = passes;
+    fp.accBegin = 0;
+    fp.accEnd = passes;
+    DevBuf<float4> rad, acc;
+    DevBuf<uint32_t> seeds;
+    if (rad.alloc(npix*passes) || acc.alloc(npix) || seeds.alloc((size_t)passes))
+        return fail("selftest_accumulate: allocation failed");
+    if (hipMemcpy(rad.get(), radiance, npix*passes*sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(acc.get(), accum, npix*sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(seeds.get(), pass_seeds, (size_t)passes*sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return fail("selftest_accumulate: upload failed");
+    int ran = ACC_FORM_UNTILED;
+    if (accumulate_tiled_fits(fp))
+    {
+        const int tiles = ((width + kAccTile - 1)/kAccTile)*((height + kAccTile - 1)/kAccTile);
+        ran = launch_accumulate_kernels(numCUs, choice, form != 1, seeds.get(), nullptr, tiles, nullptr, fp, rad.get(), acc.get());
+    }
+    else
+    {
+        const PathState ps = { rad.get() };
+        hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((npix + kBlock - 1)/kBlock)), dim3(kBlock), 0, nullptr, ps, fp, acc.get(), seeds.get());
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(accum, acc.get(), npix*sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("selftest_accumulate: kernel failed");
+    *out_form = ran;
+    if (form == 2 && ran != ACC_FORM_SUPPORT_TILED && ran != ACC_FORM_SUPPORT_WIDE)
+        return fail("selftest_accumulate: no support form for this filter and kernel choice");
     return 0;
 }
 

@@ -997,14 +997,93 @@ size_t slots_per_pass(const tinsel_hip* r, int width, int height, int* tilesXOut
     return std::max<size_t>(1, (size_t)owned*r->shardTile*r->shardTile);
 }
 
+// The support form of k_accumulate_tiled (tn_accumulate.h) adds nothing but what the full window adds when the filter's weight is +0 by
+// construction from one pixel away on: Filter::Gaussian is max(0, expf(a) - offset) with a = -falloff*x*x, and for a <= argZero =
+// log(offset) - 1e-6 (in double, rounded DOWN to float) e^a <= offset*(1 - 1e-6) while expf is off by less than an ulp (1.2e-7): the float
+// expf(a) is below offset and the weight +0.  With falloff > 0 the argument falls with |x|, so -falloff*1*1 <= argZero puts every column a
+// pixel or more from the sample there: of a path generated at pixel i, all but i and i + 1.  Widths up to 1 (the compile-time windows).
+bool accumulate_support_rule(int filterType, float width, float falloff, float offset, float* argZero)
+{
+    *argZero = 0.0f;
+    if (filterType == 0 || !(offset > 0.0f) || !std::isfinite(offset) || !(falloff > 0.0f) || !std::isfinite(falloff) || !(width > 0.0f) || !(width <= 1.0f))
+        return false;
+    const double z = std::log((double)offset) - 1e-6;
+    float f = (float)z;
+    if ((double)f > z)
+        f = std::nextafterf(f, -INFINITY);
+    *argZero = f;
+    return -falloff*1.0f*1.0f <= f;
+}
+
+enum { ACC_FORM_UNTILED = 0, ACC_FORM_TILED, ACC_FORM_WIDE, ACC_FORM_PIPED, ACC_FORM_SUPPORT_TILED, ACC_FORM_SUPPORT_WIDE };
+
+// The accumulate launch itself: `choice` is tinsel_hip_tuning::accumulate; `tiles` blocks (a shard: those of `tileList`); allowSupport = false
+// keeps the full window whatever the filter (tinsel_hip_selftest_accumulate's other arm).  Returns the form it ran.
+int launch_accumulate_kernels(int numCUs, int choice, bool allowSupport, const uint32_t* passSeeds, const int* tileList, int tiles, hipStream_t st,
+                              const FrameParams& fp, float4* rad, float4* target)
+{
+    const PathState ps = { rad };
+    const int span = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth) + 1;     // reachLo + reachHi + 1
+    // Which kernel (the same adds in the same order, tests/test_gpu_switches.py):
+    //   a block per CU or less: staging of pass s + 1 overlapped with the gather of pass s (k_accumulate_piped: the launch is as long as
+    //     one tile's pass loop; cornell 256^2 x 16 passes 0.053 -> 0.037 ms, profiles/r05_q_ab_acc_piped.md; at 1024 tiles 0.100 -> 0.107,
+    //     one shard of 8 of cornell 1024^2 0.565 -> 0.525 at 64-pixel tiles but 0.563 -> 0.613 at 32: not used there);
+    //   up to a wave per SIMD: 512-thread workgroups, the second half only stages (profiles/r03_y_ab_acc_wide.md);
+    //   else 256-thread workgroups.
+    // The two k_accumulate_tiled launches take the support form where the filter allows it (accumulate_support_rule), unless the tuning
+    // asks for the full window; k_accumulate_piped and k_accumulate have no such form.
+    bool piped = tiles <= numCUs;
+    bool wide = tiles <= numCUs*4;
+    if (choice != TINSEL_ACCUMULATE_AUTO && choice != TINSEL_ACCUMULATE_FULL_WINDOW)
+    {
+        piped = choice == TINSEL_ACCUMULATE_PIPED;
+        wide = choice == TINSEL_ACCUMULATE_WIDE;
+    }
+    float argZero = 0.0f;
+    const bool support = accumulate_support_rule(fp.filterType, fp.filterWidth, fp.filterFalloff, fp.filterOffset, &argZero) &&
+                         allowSupport && choice != TINSEL_ACCUMULATE_FULL_WINDOW && (span == 3 || span == 4);
+    if (span == 3 && piped)
+        hipLaunchKernelGGL((k_accumulate_piped<3>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, passSeeds, tileList);
+    else if (span == 4 && piped)
+        hipLaunchKernelGGL((k_accumulate_piped<4>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, passSeeds, tileList);
+    else if (span == 3 && wide && support)
+        hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock, true>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
+    else if (span == 4 && wide && support)
+        hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock, true>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
+    else if (span == 3 && support)
+        hipLaunchKernelGGL((k_accumulate_tiled<3, kBlock, true>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
+    else if (span == 4 && support)
+        hipLaunchKernelGGL((k_accumulate_tiled<4, kBlock, true>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
+    else if (span == 3 && wide)
+        hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
+    else if (span == 4 && wide)
+        hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
+    else if (span == 3)
+        hipLaunchKernelGGL((k_accumulate_tiled<3>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
+    else if (span == 4)
+        hipLaunchKernelGGL((k_accumulate_tiled<4>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
+    else
+        hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
+    if ((span == 3 || span == 4) && piped)
+        return ACC_FORM_PIPED;
+    if (span == 3 || span == 4)
+        return wide ? (support ? ACC_FORM_SUPPORT_WIDE : ACC_FORM_WIDE) : (support ? ACC_FORM_SUPPORT_TILED : ACC_FORM_TILED);
+    return ACC_FORM_TILED;
+}
+
+// Does the frame go through the tiled kernels (the footprint halo fits, 16-bit pixel coordinates)?
+bool accumulate_tiled_fits(const FrameParams& fp)
+{
+    const int halo = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth);
+    return halo <= kAccMaxHalo && fp.filterWidth >= 0.0f && fp.width < 65536 && fp.height < 65536;
+}
+
 // The accumulate stage of a traced batch: adds the batch passes [fp.accBegin, fp.accEnd), their radiance at `rad`, to `target`.
 int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* rad, float4* target)
 {
-    const PathState ps = { rad };
     const size_t npix = (size_t)fp.width*fp.height;
     ScopedTimer t(r, KN_ACCUMULATE, st);
-    const int halo = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth);
-    if (halo <= kAccMaxHalo && fp.filterWidth >= 0.0f && fp.width < 65536 && fp.height < 65536)
+    if (accumulate_tiled_fits(fp))
     {
         int tiles = ((fp.width + kAccTile - 1)/kAccTile)*((fp.height + kAccTile - 1)/kAccTile);
         const int* tileList = nullptr;
@@ -1016,39 +1095,11 @@ int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, floa
             tiles = r->accTilesCount;
         }
         if (tiles > 0)
-        {
-            const int span = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth) + 1;     // reachLo + reachHi + 1
-            // Which kernel (the same adds in the same order, tests/test_gpu_switches.py):
-            //   a block per CU or less: staging of pass s + 1 overlapped with the gather of pass s (k_accumulate_piped: the launch is as long as
-            //     one tile's pass loop; cornell 256^2 x 16 passes 0.053 -> 0.037 ms, profiles/r05_q_ab_acc_piped.md; at 1024 tiles 0.100 -> 0.107,
-            //     one shard of 8 of cornell 1024^2 0.565 -> 0.525 at 64-pixel tiles but 0.563 -> 0.613 at 32: not used there);
-            //   up to a wave per SIMD: 512-thread workgroups, the second half only stages (profiles/r03_y_ab_acc_wide.md);
-            //   else 256-thread workgroups.
-            bool piped = tiles <= r->numCUs;
-            bool wide = tiles <= r->numCUs*4;
-            if (r->tune.accumulate != TINSEL_ACCUMULATE_AUTO)
-            {
-                piped = r->tune.accumulate == TINSEL_ACCUMULATE_PIPED;
-                wide = r->tune.accumulate == TINSEL_ACCUMULATE_WIDE;
-            }
-            if (span == 3 && piped)
-                hipLaunchKernelGGL((k_accumulate_piped<3>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else if (span == 4 && piped)
-                hipLaunchKernelGGL((k_accumulate_piped<4>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else if (span == 3 && wide)
-                hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else if (span == 4 && wide)
-                hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else if (span == 3)
-                hipLaunchKernelGGL((k_accumulate_tiled<3>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else if (span == 4)
-                hipLaunchKernelGGL((k_accumulate_tiled<4>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
-            else
-                hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds, tileList);
-        }
+            launch_accumulate_kernels(r->numCUs, r->tune.accumulate, true, r->passSeeds, tileList, tiles, st, fp, rad, target);
     }
     else
     {
+        const PathState ps = { rad };
         const int gridPix = (int)((npix + kBlock - 1)/kBlock);
         hipLaunchKernelGGL(k_accumulate, dim3(gridPix), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds);
     }

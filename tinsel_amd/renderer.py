@@ -148,6 +148,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_selftest_sort"):          # (absent from libraries built before round 5: TINSEL_HIP_LIB)
         L.tinsel_hip_selftest_sort.argtypes = [ci, vp, C.c_ulonglong, ci, ci]
         L.tinsel_hip_selftest_scan.argtypes = [ci, vp, vp, C.c_ulonglong]
+    if hasattr(L, "tinsel_hip_selftest_accumulate"):    # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_selftest_accumulate.argtypes = abi.SELFTEST_ACCUMULATE_ARGTYPES
+        L.tinsel_hip_accumulate_support.argtypes = [ci, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]
     L.tinsel_hip_plan_regions.argtypes = [C.c_ulonglong, ci, ci, ci, C.POINTER(C.c_uint)]
     L.tinsel_hip_last_error.restype = C.c_char_p
     L.tinsel_pack_open.argtypes = [vp, C.c_size_t, C.POINTER(abi.SceneDesc), C.POINTER(abi.Camera), C.POINTER(abi.Options)]
@@ -167,7 +170,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_set_primitive_transform", "tinsel_hip_rebuild_scene",
     "tinsel_hip_group_create", "tinsel_hip_group_destroy", "tinsel_hip_group_init", "tinsel_hip_group_render", "tinsel_hip_group_present",
     "tinsel_hip_group_size", "tinsel_hip_group_member", "tinsel_hip_group_set_lookahead", "tinsel_hip_ubench",
-    "tinsel_hip_selftest_arith", "tinsel_hip_selftest_sort", "tinsel_hip_selftest_scan", "tinsel_hip_plan_regions",
+    "tinsel_hip_selftest_arith", "tinsel_hip_selftest_sort", "tinsel_hip_selftest_scan", "tinsel_hip_selftest_accumulate", "tinsel_hip_accumulate_support", "tinsel_hip_plan_regions",
     "tinsel_hip_tuning_init", "tinsel_hip_create_tuned", "tinsel_hip_set_tuning", "tinsel_hip_get_tuning", "tinsel_hip_group_create_tuned",
     "tinsel_hip_comm_unique_id", "tinsel_hip_comm_init", "tinsel_hip_comm_size", "tinsel_hip_comm_reduce_accum",
     "tinsel_hip_trace_rays", "tinsel_hip_trace_rays_device", "tinsel_hip_trace_camera",
@@ -877,6 +880,23 @@ def selftest_scan(values, device=0):
     out = np.empty_like(a)
     _check(L.tinsel_hip_selftest_scan(int(device), a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), a.size), "tinsel_hip_selftest_scan")
     return out
+
+
+def selftest_accumulate(radiance, accum, pass_seeds, filter, clamp, choice=abi.ACCUMULATE_AUTO, form=abi.ACCUMULATE_FORM_AUTO, device=0):
+    """tinsel_hip_selftest_accumulate: radiance[passes, H, W, 4] added to a copy of accum[H, W, 4] by the launch a render of such a frame makes;
+    filter = (type, width, falloff, offset).  Returns (the new accumulator, the form that ran: abi.ACCUMULATE_RAN_*)."""
+    L = load_library()
+    rad = np.ascontiguousarray(radiance, np.float32)
+    out = np.array(accum, np.float32, order="C")
+    seeds = np.ascontiguousarray(pass_seeds, np.uint32)
+    passes, H, W = rad.shape[0], rad.shape[1], rad.shape[2]
+    if rad.shape != (passes, H, W, 4) or out.shape != (H, W, 4) or seeds.shape != (passes,):
+        raise ValueError("selftest_accumulate: radiance[passes, H, W, 4], accum[H, W, 4], pass_seeds[passes]")
+    ran = C.c_int(-1)
+    _check(L.tinsel_hip_selftest_accumulate(int(device), W, H, int(filter[0]), float(filter[1]), float(filter[2]), float(filter[3]), float(clamp),
+                                            _host_ptr(seeds), passes, _host_ptr(rad), _host_ptr(out), int(choice), int(form), C.byref(ran)),
+           "tinsel_hip_selftest_accumulate")
+    return out, ran.value
 
 
 def selftest_arith(op, variant=-1, device=0):
