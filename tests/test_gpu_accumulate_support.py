@@ -58,6 +58,17 @@ def _accum(W, H, seed):
     return np.random.default_rng(seed).random((H, W, 4)).astype(np.float32)
 
 
+def _not_finite(rad):
+    """rad[3, H, W, 4] with an inf, a NaN or a -inf component at five spots (a frame's corners, both sides of a tile's edge) and one huge finite
+    sample; returns it and the (pass, row, column) of the spots"""
+    H, W = rad.shape[1:3]
+    spots = [(0, 0, 0), (1, min(H - 1, 15), min(W - 1, 16)), (2, H - 1, W - 1), (1, H//2, min(W - 1, 15)), (0, min(H - 1, 16), min(W - 1, 3))]
+    for n, (s, j, i) in enumerate(spots):
+        rad[s, j, i, n % 3] = [np.inf, np.nan, -np.inf][n % 3]
+    rad[2, min(H - 1, 1), min(W - 1, 1), :3] = 3.0e38
+    return rad, spots
+
+
 def _check_forms(rad, acc0, seeds, filt, clamp, equal_nan=False):
     """full window == AddSample, support == full window bit for bit, for both workgroup sizes; returns the result"""
     want = add_passes(acc0, rad, seeds, filt, clamp)
@@ -133,11 +144,7 @@ def test_samples_that_are_not_finite_go_through_the_full_window(name, frame):
     W, H = frame
     filt = FILTERS[name][0]
     seeds = _seeds(W, H, 3)
-    rad = _radiance(W, H, 3, 21)
-    spots = [(0, 0, 0), (1, min(H - 1, 15), min(W - 1, 16)), (2, H - 1, W - 1), (1, H//2, min(W - 1, 15)), (0, min(H - 1, 16), 3)]
-    for n, (s, j, i) in enumerate(spots):
-        rad[s, j, i, n % 3] = [np.inf, np.nan, -np.inf][n % 3]
-    rad[2, 1, 1, :3] = 3.0e38
+    rad, _ = _not_finite(_radiance(W, H, 3, 21))
     for clamp in (4.0, NO_CLAMP):
         want = _check_forms(rad, _accum(W, H, 6), seeds, filt, clamp, equal_nan=True)
         assert np.isnan(want).any() and np.isfinite(want[..., 3]).all()
@@ -172,3 +179,40 @@ def test_negative_samples(frame):
     for name in ("cornell", "half"):
         _check_forms(rad, _accum(W, H, 32) - 0.5, seeds, FILTERS[name][0], NO_CLAMP)
         _check_forms(rad, np.zeros((H, W, 4), np.float32), seeds, FILTERS[name][0], 4.0)
+
+
+FULL_WINDOW_RUNS = [(abi.ACCUMULATE_TILED, abi.ACCUMULATE_FORM_FULL_WINDOW, abi.ACCUMULATE_RAN_TILED),
+                    (abi.ACCUMULATE_WIDE, abi.ACCUMULATE_FORM_FULL_WINDOW, abi.ACCUMULATE_RAN_WIDE),
+                    (abi.ACCUMULATE_PIPED, abi.ACCUMULATE_FORM_FULL_WINDOW, abi.ACCUMULATE_RAN_PIPED),
+                    (abi.ACCUMULATE_AUTO, abi.ACCUMULATE_FORM_AUTO, abi.ACCUMULATE_RAN_PIPED)]      # (a handful of tiles: a block per CU or less)
+
+
+@pytest.mark.parametrize("frame", [(1, 1), (17, 16), (33, 19)], ids=lambda f: "%dx%d" % f)
+@pytest.mark.parametrize("name", ["cornell", "default", "one", "box"])
+def test_every_full_window_kernel_adds_the_same_whatever_the_samples(name, frame):
+    """The full window of k_accumulate_tiled at both workgroup sizes and k_accumulate_piped (which the tests above reach with finite samples
+    and one filter only) stage and add with the same arithmetic: samples that are not finite, an accumulator with -0 entries, the Gaussian
+    of both compile-time windows, the borderline Gaussian and the box.  GPU against GPU every bit compares, the sign of a NaN too; against
+    AddSample every bit of every number, and the same components NaN (the sign of the NaN an invalid operation makes is the processor's)."""
+    W, H = frame
+    filt = FILTERS[name][0]
+    seeds = _seeds(W, H, 3)
+    rad, spots = _not_finite(_radiance(W, H, 3, 41))
+    acc0 = _accum(W, H, 42)
+    acc0[::2, ::3] = -0.0
+    acc0[H - 1, W - 1, 1] = -0.0
+    near = np.zeros((H, W), bool)           # what a sample generated at a spot can reach: at most two pixels away (filter widths up to 1)
+    for _, j, i in spots:
+        near[max(0, j - 2):j + 3, max(0, i - 2):i + 3] = True
+    for clamp in (4.0, NO_CLAMP):
+        want = add_passes(acc0, rad, seeds, filt, clamp)
+        nan = np.isnan(want)
+        assert nan.any() and not nan[~near].any()
+        got = []
+        for choice, form, ran_want in FULL_WINDOW_RUNS:
+            out, ran = tinsel_amd.selftest_accumulate(rad, acc0, seeds, filt, clamp, choice, form)
+            assert ran == ran_want
+            got.append(out)
+        for out in got:
+            assert np.array_equal(_bits(out), _bits(got[0]))
+        assert np.array_equal(np.isnan(got[0]), nan) and np.array_equal(_bits(got[0])[~nan], _bits(want)[~nan])

@@ -97,6 +97,20 @@ def test_the_scan_kernels_spill_nothing():
     assert k["k_shadow<0,1,1,1>"]["waves_per_simd"] >= 7
 
 
+def test_the_accumulate_kernels_keep_their_waves():
+    """Every accumulate kernel (tn_accumulate.h) without scratch and at no fewer waves per SIMD than profiles/r13_accumulate_support.md
+    measured them at: the support form's 256-thread kernels at six (what its __launch_bounds__ asks for), the full window's at seven (SPAN 3)
+    and six (SPAN 4), the 512-thread ones and k_accumulate_piped (ten waves a tile) at eight; the run-time window's kernel had five and
+    k_accumulate eight in that build."""
+    k = _resources()
+    waves = {"k_accumulate": 8, "k_accumulate_piped<3>": 8, "k_accumulate_piped<4>": 8, "k_accumulate_tiled<0,256,0>": 5,
+             "k_accumulate_tiled<3,256,0>": 7, "k_accumulate_tiled<4,256,0>": 6, "k_accumulate_tiled<3,256,1>": 6, "k_accumulate_tiled<4,256,1>": 6,
+             "k_accumulate_tiled<3,512,0>": 8, "k_accumulate_tiled<4,512,0>": 8, "k_accumulate_tiled<3,512,1>": 8, "k_accumulate_tiled<4,512,1>": 8}
+    assert sorted(n for n in k if n.startswith("k_accumulate")) == sorted(waves)
+    for n, w in waves.items():
+        assert k[n]["scratch_bytes"] == 0 and k[n]["waves_per_simd"] >= w, (n, k[n])
+
+
 def test_the_build_parses_the_compiler_remarks():
     """build.py's reading of -Rpass-analysis=kernel-resource-usage (no compiler needed: canned text)"""
     import sys

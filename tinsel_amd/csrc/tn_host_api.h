@@ -902,17 +902,7 @@ int tinsel_hip_selftest_accumulate(int device_index, int width, int height, int 
         hipMemcpy(acc.get(), accum, npix*sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(seeds.get(), pass_seeds, (size_t)passes*sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
         return fail("selftest_accumulate: upload failed");
-    int ran = ACC_FORM_UNTILED;
-    if (accumulate_tiled_fits(fp))
-    {
-        const int tiles = ((width + kAccTile - 1)/kAccTile)*((height + kAccTile - 1)/kAccTile);
-        ran = launch_accumulate_kernels(numCUs, choice, form != 1, seeds.get(), nullptr, tiles, nullptr, fp, rad.get(), acc.get());
-    }
-    else
-    {
-        const PathState ps = { rad.get() };
-        hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((npix + kBlock - 1)/kBlock)), dim3(kBlock), 0, nullptr, ps, fp, acc.get(), seeds.get());
-    }
+    const int ran = launch_accumulate_kernels(numCUs, choice, form != 1, seeds.get(), nullptr, -1, nullptr, fp, rad.get(), acc.get());
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess || hipMemcpy(accum, acc.get(), npix*sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
         return fail("selftest_accumulate: kernel failed");
     *out_form = ran;

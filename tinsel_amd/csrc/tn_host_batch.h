@@ -1017,60 +1017,6 @@ bool accumulate_support_rule(int filterType, float width, float falloff, float o
 
 enum { ACC_FORM_UNTILED = 0, ACC_FORM_TILED, ACC_FORM_WIDE, ACC_FORM_PIPED, ACC_FORM_SUPPORT_TILED, ACC_FORM_SUPPORT_WIDE };
 
-// The accumulate launch itself: `choice` is tinsel_hip_tuning::accumulate; `tiles` blocks (a shard: those of `tileList`); allowSupport = false
-// keeps the full window whatever the filter (tinsel_hip_selftest_accumulate's other arm).  Returns the form it ran.
-int launch_accumulate_kernels(int numCUs, int choice, bool allowSupport, const uint32_t* passSeeds, const int* tileList, int tiles, hipStream_t st,
-                              const FrameParams& fp, float4* rad, float4* target)
-{
-    const PathState ps = { rad };
-    const int span = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth) + 1;     // reachLo + reachHi + 1
-    // Which kernel (the same adds in the same order, tests/test_gpu_switches.py):
-    //   a block per CU or less: staging of pass s + 1 overlapped with the gather of pass s (k_accumulate_piped: the launch is as long as
-    //     one tile's pass loop; cornell 256^2 x 16 passes 0.053 -> 0.037 ms, profiles/r05_q_ab_acc_piped.md; at 1024 tiles 0.100 -> 0.107,
-    //     one shard of 8 of cornell 1024^2 0.565 -> 0.525 at 64-pixel tiles but 0.563 -> 0.613 at 32: not used there);
-    //   up to a wave per SIMD: 512-thread workgroups, the second half only stages (profiles/r03_y_ab_acc_wide.md);
-    //   else 256-thread workgroups.
-    // The two k_accumulate_tiled launches take the support form where the filter allows it (accumulate_support_rule), unless the tuning
-    // asks for the full window; k_accumulate_piped and k_accumulate have no such form.
-    bool piped = tiles <= numCUs;
-    bool wide = tiles <= numCUs*4;
-    if (choice != TINSEL_ACCUMULATE_AUTO && choice != TINSEL_ACCUMULATE_FULL_WINDOW)
-    {
-        piped = choice == TINSEL_ACCUMULATE_PIPED;
-        wide = choice == TINSEL_ACCUMULATE_WIDE;
-    }
-    float argZero = 0.0f;
-    const bool support = accumulate_support_rule(fp.filterType, fp.filterWidth, fp.filterFalloff, fp.filterOffset, &argZero) &&
-                         allowSupport && choice != TINSEL_ACCUMULATE_FULL_WINDOW && (span == 3 || span == 4);
-    if (span == 3 && piped)
-        hipLaunchKernelGGL((k_accumulate_piped<3>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, passSeeds, tileList);
-    else if (span == 4 && piped)
-        hipLaunchKernelGGL((k_accumulate_piped<4>), dim3(tiles), dim3(kAccPipeThreads), 0, st, ps, fp, target, passSeeds, tileList);
-    else if (span == 3 && wide && support)
-        hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock, true>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
-    else if (span == 4 && wide && support)
-        hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock, true>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
-    else if (span == 3 && support)
-        hipLaunchKernelGGL((k_accumulate_tiled<3, kBlock, true>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
-    else if (span == 4 && support)
-        hipLaunchKernelGGL((k_accumulate_tiled<4, kBlock, true>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, argZero);
-    else if (span == 3 && wide)
-        hipLaunchKernelGGL((k_accumulate_tiled<3, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
-    else if (span == 4 && wide)
-        hipLaunchKernelGGL((k_accumulate_tiled<4, 2*kBlock>), dim3(tiles), dim3(2*kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
-    else if (span == 3)
-        hipLaunchKernelGGL((k_accumulate_tiled<3>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
-    else if (span == 4)
-        hipLaunchKernelGGL((k_accumulate_tiled<4>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
-    else
-        hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);
-    if ((span == 3 || span == 4) && piped)
-        return ACC_FORM_PIPED;
-    if (span == 3 || span == 4)
-        return wide ? (support ? ACC_FORM_SUPPORT_WIDE : ACC_FORM_WIDE) : (support ? ACC_FORM_SUPPORT_TILED : ACC_FORM_TILED);
-    return ACC_FORM_TILED;
-}
-
 // Does the frame go through the tiled kernels (the footprint halo fits, 16-bit pixel coordinates)?
 bool accumulate_tiled_fits(const FrameParams& fp)
 {
@@ -1078,31 +1024,79 @@ bool accumulate_tiled_fits(const FrameParams& fp)
     return halo <= kAccMaxHalo && fp.filterWidth >= 0.0f && fp.width < 65536 && fp.height < 65536;
 }
 
+// What every tiled accumulate launch is given: `tiles` blocks (a shard: those of `tileList`); argZero: the support form's, else 0
+struct AccLaunch { const uint32_t* passSeeds; const int* tileList; int tiles; hipStream_t st; PathState ps; const FrameParams& fp; float4* target; float argZero; };
+
+// The compile-time windows (SPAN 3 and 4).  Which kernel (the same adds in the same order, tests/test_gpu_switches.py):
+//   piped: staging of pass s + 1 overlapped with the gather of pass s (k_accumulate_piped: the launch is as long as one tile's pass loop;
+//     cornell 256^2 x 16 passes 0.053 -> 0.037 ms, profiles/r05_q_ab_acc_piped.md; at 1024 tiles 0.100 -> 0.107, one shard of 8 of cornell
+//     1024^2 0.565 -> 0.525 at 64-pixel tiles but 0.563 -> 0.613 at 32: not used there);
+//   wide: 512-thread workgroups, the second half only stages (profiles/r03_y_ab_acc_wide.md);
+//   else 256-thread workgroups.
+// SUPPORT: the support form of the two k_accumulate_tiled launches; k_accumulate_piped has no such form.  Returns the form it ran.
+template <int SPAN, bool SUPPORT>
+int launch_accumulate_span(const AccLaunch& a, bool piped, bool wide)
+{
+    if (piped)
+    {
+        hipLaunchKernelGGL((k_accumulate_piped<SPAN>), dim3(a.tiles), dim3(kAccPipeThreads), 0, a.st, a.ps, a.fp, a.target, a.passSeeds, a.tileList);
+        return ACC_FORM_PIPED;
+    }
+    if (wide)
+    {
+        hipLaunchKernelGGL((k_accumulate_tiled<SPAN, 2*kBlock, SUPPORT>), dim3(a.tiles), dim3(2*kBlock), 0, a.st, a.ps, a.fp, a.target, a.passSeeds, a.tileList, a.argZero);
+        return SUPPORT ? ACC_FORM_SUPPORT_WIDE : ACC_FORM_WIDE;
+    }
+    hipLaunchKernelGGL((k_accumulate_tiled<SPAN, kBlock, SUPPORT>), dim3(a.tiles), dim3(kBlock), 0, a.st, a.ps, a.fp, a.target, a.passSeeds, a.tileList, a.argZero);
+    return SUPPORT ? ACC_FORM_SUPPORT_TILED : ACC_FORM_TILED;
+}
+
+// The accumulate launch itself, for a render and for tinsel_hip_selftest_accumulate alike: `choice` is tinsel_hip_tuning::accumulate;
+// shardTiles >= 0: a shard's launch, that many blocks, those of `tileList`; < 0: a block for every tile of the frame; allowSupport = false
+// keeps the full window whatever the filter (the selftest's other arm).  Returns the form it ran.
+int launch_accumulate_kernels(int numCUs, int choice, bool allowSupport, const uint32_t* passSeeds, const int* tileList, int shardTiles, hipStream_t st,
+                              const FrameParams& fp, float4* rad, float4* target)
+{
+    const PathState ps = { rad };
+    if (!accumulate_tiled_fits(fp))
+    {
+        hipLaunchKernelGGL(k_accumulate, dim3((unsigned)(((size_t)fp.width*fp.height + kBlock - 1)/kBlock)), dim3(kBlock), 0, st, ps, fp, target, passSeeds);
+        return ACC_FORM_UNTILED;
+    }
+    const int tiles = shardTiles >= 0 ? shardTiles : ((fp.width + kAccTile - 1)/kAccTile)*((fp.height + kAccTile - 1)/kAccTile);
+    if (tiles == 0)
+        return ACC_FORM_TILED;      // (a shard without a candidate in the frame: nothing to add)
+    const int span = 1 + (int)floorf(fp.filterWidth) + (int)ceilf(fp.filterWidth) + 1;     // reachLo + reachHi + 1
+    // a block per CU or less: piped; up to a wave per SIMD: wide -- unless the tuning names the kernel
+    bool piped = tiles <= numCUs;
+    bool wide = tiles <= numCUs*4;
+    if (choice != TINSEL_ACCUMULATE_AUTO && choice != TINSEL_ACCUMULATE_FULL_WINDOW)
+    {
+        piped = choice == TINSEL_ACCUMULATE_PIPED;
+        wide = choice == TINSEL_ACCUMULATE_WIDE;
+    }
+    // the support form where the filter allows it (accumulate_support_rule), unless the tuning asks for the full window
+    float argZero = 0.0f;
+    const bool support = accumulate_support_rule(fp.filterType, fp.filterWidth, fp.filterFalloff, fp.filterOffset, &argZero) &&
+                         allowSupport && choice != TINSEL_ACCUMULATE_FULL_WINDOW;
+    const AccLaunch a = { passSeeds, tileList, tiles, st, ps, fp, target, support ? argZero : 0.0f };
+    if (span == 3)
+        return support ? launch_accumulate_span<3, true>(a, piped, wide) : launch_accumulate_span<3, false>(a, piped, wide);
+    if (span == 4)
+        return support ? launch_accumulate_span<4, true>(a, piped, wide) : launch_accumulate_span<4, false>(a, piped, wide);
+    hipLaunchKernelGGL((k_accumulate_tiled<0>), dim3(tiles), dim3(kBlock), 0, st, ps, fp, target, passSeeds, tileList, 0.0f);     // (widths beyond 1: the window's bounds at run time)
+    return ACC_FORM_TILED;
+}
+
 // The accumulate stage of a traced batch: adds the batch passes [fp.accBegin, fp.accEnd), their radiance at `rad`, to `target`.
 int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* rad, float4* target)
 {
-    const size_t npix = (size_t)fp.width*fp.height;
     ScopedTimer t(r, KN_ACCUMULATE, st);
-    if (accumulate_tiled_fits(fp))
-    {
-        int tiles = ((fp.width + kAccTile - 1)/kAccTile)*((fp.height + kAccTile - 1)/kAccTile);
-        const int* tileList = nullptr;
-        if (fp.shardWorld > 1)
-        {
-            if (accumulate_tile_list(r, fp))
-                return -1;
-            tileList = r->accTilesDev.get();
-            tiles = r->accTilesCount;
-        }
-        if (tiles > 0)
-            launch_accumulate_kernels(r->numCUs, r->tune.accumulate, true, r->passSeeds, tileList, tiles, st, fp, rad, target);
-    }
-    else
-    {
-        const PathState ps = { rad };
-        const int gridPix = (int)((npix + kBlock - 1)/kBlock);
-        hipLaunchKernelGGL(k_accumulate, dim3(gridPix), dim3(kBlock), 0, st, ps, fp, target, r->passSeeds);
-    }
+    const bool listed = fp.shardWorld > 1 && accumulate_tiled_fits(fp);         // a shard's launch: the tiles that have candidates of its own
+    if (listed && accumulate_tile_list(r, fp))
+        return -1;
+    launch_accumulate_kernels(r->numCUs, r->tune.accumulate, true, r->passSeeds, listed ? r->accTilesDev.get() : nullptr, listed ? r->accTilesCount : -1, st, fp,
+                              rad, target);
     HIP_TRY(hipGetLastError());
     return 0;
 }
