@@ -512,6 +512,40 @@ int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinse
 int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
                                       float* out_rgbx_dev, tinsel_path_start* starts_out_dev /* may be NULL */, void* stream);
 
+/* SH gather queries: a gather query whose paths are projected onto the real spherical harmonics of bands 0 .. order instead of averaged
+ * to one colour -- what a light probe keeps of its directions.  `order` is the highest band, 0, 1 or 2; C = (order + 1)^2 coefficients
+ * per channel come back.  The point record, the modes, the seeds, the two draws, the directions, starts_out, the batch rule (whole points
+ * only), the stream ordering, what is left untouched, the statistics and the bad-argument rules are those of tinsel_hip_gather_radiance*;
+ * in addition an order outside 0 .. TINSEL_GATHER_SH_MAX_ORDER returns -1 (judged with the other arguments, before n is looked at).
+ * out holds n*C float4: out[(k*C + i)*4 + c] is coefficient i, channel c (0, 1, 2 = r, g, b) of point k; word 3 of every float4 is
+ * written as 0.  The value is the plain mean, no 4 pi or pi folded in:
+ *     acc[i][c] = acc[i][c] + L[s][c] * Y_i(d_s)   for s = 0 .. samples - 1 in ascending order, then acc[i][c] / (float)samples
+ * -- the product rounded to fp32, then the sum, no contraction, and an IEEE divide (TINSEL_ARITH_EXACT) -- where L[s] is what PathTrace
+ * returns for sample s and d_s = (x, y, z) the direction the path was generated with: the bits of starts_out[k*samples + s].dx, dy, dz.
+ * The basis is the real orthonormal one of the graphics convention, in fp32 and in this operation order:
+ *     Y0 = 0.28209479f
+ *     Y1 = 0.48860251f*y        Y2 = 0.48860251f*z        Y3 = 0.48860251f*x
+ *     Y4 = (1.0925484f*x)*y     Y5 = (1.0925484f*y)*z     Y7 = (1.0925484f*x)*z
+ *     Y6 = 0.31539157f*((3.0f*z)*z - 1.0f)
+ *     Y8 = 0.54627422f*(x*x - y*y)
+ * What the means are: TINSEL_GATHER_SPHERE draws with density 1/(4 pi), so 4 pi * mean_i are the SH coefficients of the incident radiance
+ * (convolved with the cosine lobe -- factors pi, 2 pi/3, pi/4 for bands 0, 1, 2 -- they give the irradiance for any normal);
+ * TINSEL_GATHER_COSINE draws with density cos/pi about the normal, so pi * mean_i are the coefficients of the cosine-weighted incident
+ * radiance about that normal, and pi * mean_0 / Y0 is the irradiance.
+ * Kernels: "k_generate_gather" in front, the pipeline, and "k_gather_sh_reduce" behind it ("k_gather_reduce" does not run); the reduction
+ * derives every path's direction again from the point record and s, nothing is stored per path beyond the 16 bytes of radiance a gather
+ * query keeps, in the same buffer.  The host entry stages as tinsel_hip_gather_radiance does, under the same 64 MB ceiling: a chunk is
+ * min(2^20, floor(64 MB / (32 + 16*C [+ 48*samples with starts_out]))) points. */
+#define TINSEL_GATHER_SH_MAX_ORDER 2
+
+/* host arrays (staged in chunks); returns when `out_host` (and `starts_out_host`) is written */
+int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_host,
+                         int samples, int max_depth, float* out_host, tinsel_path_start* starts_out_host /* may be NULL */);
+/* device arrays, 16-byte aligned, not overlapping; enqueued on `stream` (NULL: the default stream) and not waited for, ordered against the
+ * renderer's own work as tinsel_hip_trace_radiance_device is */
+int tinsel_hip_gather_sh_device(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_dev,
+                                int samples, int max_depth, float* out_dev, tinsel_path_start* starts_out_dev /* may be NULL */, void* stream);
+
 /* Allocates the per-batch path buffers a later render of `passes` passes at `max_depth` will need, so that the first
  * such call does not pay for hipMalloc (tinsel_hip_render* allocate on demand otherwise). */
 int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth);

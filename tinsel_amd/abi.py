@@ -163,6 +163,7 @@ class GatherPoint(C.Structure):
 # an (n, 8) array of 32-bit words viewed as GATHER_POINT_DTYPE is a tinsel_gather_point[n]
 GATHER_POINT_DTYPE = [("px", "<f4"), ("py", "<f4"), ("pz", "<f4"), ("time", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("seed", "<u4")]
 GATHER_COSINE, GATHER_SPHERE = 0, 1
+GATHER_SH_MAX_ORDER = 2       # tinsel_hip_gather_sh*: bands 0 .. order, (order + 1)^2 coefficients per channel
 
 
 class KernelTimeV1(C.Structure):

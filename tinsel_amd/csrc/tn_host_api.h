@@ -166,7 +166,7 @@ int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, cons
         return -1;
     if (n == 0)
         return 0;
-    return trace_gather(r, mode, (size_t)n, points_dev, samples, max_depth, (float4*)out_rgbx_dev, starts_out_dev, (hipStream_t)stream);
+    return trace_gather(r, mode, kGatherMean, (size_t)n, points_dev, samples, max_depth, (float4*)out_rgbx_dev, starts_out_dev, (hipStream_t)stream);
 }
 
 int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
@@ -177,7 +177,37 @@ int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinse
     return staged_chunks((size_t)n, gather_chunk((size_t)n, samples, starts_out_host != nullptr), { points_host, &r->queryRaysDev, sizeof(tinsel_gather_point) },
                          { out_rgbx_host, &r->queryOutDev, sizeof(float4) }, { starts_out_host, &r->gatherStartsDev, sizeof(tinsel_path_start)*(size_t)samples },
                          [&](size_t, size_t m) {
-        return trace_gather(r, mode, m, r->queryRaysDev.get(), samples, max_depth, (float4*)r->queryOutDev.get(),
+        return trace_gather(r, mode, kGatherMean, m, r->queryRaysDev.get(), samples, max_depth, (float4*)r->queryOutDev.get(),
+                            starts_out_host ? r->gatherStartsDev.get() : nullptr, nullptr);
+    });
+}
+
+// SH gather queries: a gather query reduced to the (order + 1)^2 coefficients of bands 0 .. order per point instead of the mean
+// (k_gather_sh_reduce behind the same batches); everything else as above.
+int tinsel_hip_gather_sh_device(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
+                                float* out_dev, tinsel_path_start* starts_out_dev, void* stream)
+{
+    if (gather_sh_order(order, "gather_sh_device") || gather_args(r, mode, n, points_dev, samples, max_depth, out_dev, "gather_sh_device"))
+        return -1;
+    if (query_arrays({ { points_dev, (size_t)n*sizeof(tinsel_gather_point) }, { out_dev, (size_t)n*gather_out_each(order)*sizeof(float4) },
+                       { starts_out_dev, starts_out_dev ? (size_t)n*(size_t)samples*sizeof(tinsel_path_start) : 0 } }, "gather_sh_device") ||
+        query_ready(r, "gather_sh_device"))
+        return -1;
+    if (n == 0)
+        return 0;
+    return trace_gather(r, mode, order, (size_t)n, points_dev, samples, max_depth, (float4*)out_dev, starts_out_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
+                         float* out_host, tinsel_path_start* starts_out_host)
+{
+    if (gather_sh_order(order, "gather_sh") || gather_args(r, mode, n, points_host, samples, max_depth, out_host, "gather_sh") || query_ready(r, "gather_sh"))
+        return -1;
+    const size_t each = gather_out_each(order);
+    return staged_chunks((size_t)n, gather_chunk((size_t)n, samples, starts_out_host != nullptr, each), { points_host, &r->queryRaysDev, sizeof(tinsel_gather_point) },
+                         { out_host, &r->queryOutDev, sizeof(float4)*each }, { starts_out_host, &r->gatherStartsDev, sizeof(tinsel_path_start)*(size_t)samples },
+                         [&](size_t, size_t m) {
+        return trace_gather(r, mode, order, m, r->queryRaysDev.get(), samples, max_depth, (float4*)r->queryOutDev.get(),
                             starts_out_host ? r->gatherStartsDev.get() : nullptr, nullptr);
     });
 }

@@ -11,7 +11,7 @@
 //   tn_accumulate.h   AddSample as an order-preserving gather: k_accumulate, k_accumulate_tiled, k_accumulate_piped
 //   tn_query.h        k_query: ray queries on the resident scene (closest hit / occlusion of caller rays, closest hit of the camera's)
 //   tn_radiance.h     k_generate_rays: radiance queries -- the split and paired pipelines entered with paths the caller starts
-//   tn_gather.h       k_generate_gather, k_gather_reduce: gather queries -- S paths per surface point drawn on the device, one mean per point
+//   tn_gather.h       k_generate_gather, k_gather_reduce, k_gather_sh_reduce: gather queries -- S paths per surface point drawn on the device, one mean (or its SH projection) per point
 //   here              k_mega (one lane per whole path: the A/B arm), k_cost (its counters as a per-pixel map), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
 //
 // Every pipeline runs the same per-path arithmetic (tn_integrator.h, tn_bsdf.h, tn_isect.h) and leaves a finished path's radiance in

@@ -89,7 +89,8 @@ namespace tn {
     X(PK_QUERYR_OCCLUDED,       kBlock, 0, QUERY,    k_query_refill<kQueryOccluded, false>)                         \
     X(PK_GENERATE_RAYS,         kBlock, 0, GENERATE_RAYS, k_generate_rays)                                          \
     X(PK_GENERATE_GATHER,       kBlock, 0, GENERATE_GATHER, k_generate_gather)                                      \
-    X(PK_GATHER_REDUCE,         kBlock, 0, GATHER_REDUCE, k_gather_reduce)
+    X(PK_GATHER_REDUCE,         kBlock, 0, GATHER_REDUCE, k_gather_reduce)                                          \
+    X(PK_GATHER_SH_REDUCE,      kShWave, 0, GATHER_SH_REDUCE, k_gather_sh_reduce)
 
 enum PathKernel : int
 {
@@ -123,7 +124,8 @@ struct LaunchArgs
     uint32_t* cost;                 // k_cost: the cost map's four planes
     QueryJob query;                 // k_query
     RadianceJob radiance;           // k_generate_rays
-    GatherJob gather;               // k_generate_gather, k_gather_reduce
+    GatherJob gather;               // k_generate_gather, k_gather_reduce, k_gather_sh_reduce
+    int shOrder;                    // k_gather_sh_reduce: the highest band
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -141,6 +143,7 @@ struct LaunchArgs
 #define TN_ARGS_GENERATE_RAYS a.ss, a.ctl, a.radiance, a.scene.primBoxes, a.bins
 #define TN_ARGS_GENERATE_GATHER a.ss, a.ctl, a.gather, a.scene.primBoxes, a.bins
 #define TN_ARGS_GATHER_REDUCE a.ps.rad, a.gather
+#define TN_ARGS_GATHER_SH_REDUCE a.ps.rad, a.gather, a.shOrder
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

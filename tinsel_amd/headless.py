@@ -4,6 +4,7 @@
                                   [-nlm=RADIUS[,FALLOFF]] [-rr=BOUNCE] [-out=image.png|image.pfm] [-save=state.npz] [-resume=state.npz]
                                   [-complexity=rays|nodes|tris|prims] [-firsthit=buffers.npz]
                                   [-irradiance=bake.npz] [-irradiance_spp=N]
+                                  [-probes=probes.npz -probes_at=positions.npy] [-probes_spp=N] [-probes_order=0|1|2]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -37,6 +38,12 @@ normal by the reference's ray epsilon) with a gather query in cosine mode, -irra
 `irradiance` [H, W, 3] = the mean radiance * pi, 0 where the ray left the scene, with `t`, `primitive` and `normal` beside it; point k
 (the hit pixels in row order) draws from the seeds k*spp .. k*spp + spp - 1.  Exits without rendering, like -firsthit: the options that
 belong to a render (-out, -save, -resume, -nlm, -spp), -firsthit, -complexity and batch mode are refused beside it.
+-probes=FILE.npz bakes light probes at the positions of -probes_at=FILE.npy ([n, 3], scene units) with an SH gather query
+(HipRenderer.gather_sh) in sphere mode, -probes_spp paths per probe (default 1024, 1 .. 65536) to -maxdepth, bands 0 .. -probes_order
+(default 2): `sh` [n, C, 3] float32, C = (order + 1)^2 = 4 pi * the mean of radiance * Y_i over the probe's paths, the product taken in
+float32 -- the SH coefficients of the incident radiance, which tinsel_amd.sh_irradiance turns into the irradiance for any normal -- with
+`positions` beside it; probe k draws from the seeds k*spp .. k*spp + spp - 1 at time 1.  Exits without rendering: the options -irradiance
+refuses are refused beside it, and so is -irradiance.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -57,7 +64,7 @@ def parse_args(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
-           "irradiance_spp": 64, "over": {}}
+           "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "over": {}}
     for a in argv[1:-1]:
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
@@ -71,8 +78,16 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at"):
             cfg[k] = v
+        elif k == "probes_spp":
+            cfg[k] = int(v)
+            if not 1 <= cfg[k] <= 65536:
+                raise SystemExit("-probes_spp=%s: want 1 .. 65536" % v)
+        elif k == "probes_order":
+            if v not in ("0", "1", "2"):
+                raise SystemExit("-probes_order=%s: want 0, 1 or 2" % v)
+            cfg[k] = int(v)
         elif k == "irradiance_spp":
             cfg[k] = int(v)
             if not 1 <= cfg[k] <= 65536:
@@ -191,6 +206,20 @@ def irradiance(r, cam, opt, cfg):
     print("wrote %s: %dx%d, %d points x %d paths in %.3fms" % (cfg["irradiance"], opt.width, opt.height, int(hit.sum()), spp, ms))
 
 
+def probes(r, opt, cfg):
+    """-probes: an SH gather query in sphere mode at the given positions"""
+    spp, order = cfg["probes_spp"], cfg["probes_order"]
+    pos = np.load(cfg["probes_at"])
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise SystemExit("-probes_at=%s: want an [n, 3] array of positions, got %s" % (cfg["probes_at"], pos.shape))
+    pos = np.ascontiguousarray(pos, np.float32)
+    ts = time.perf_counter()
+    mean = r.gather_sh(gather_points(pos, np.zeros_like(pos), spp), spp, opt.max_depth, order, "sphere")
+    ms = (time.perf_counter() - ts)*1000.0
+    np.savez(cfg["probes"], sh=mean[:, :, :3]*np.float32(4.0*np.pi), positions=pos)
+    print("wrote %s: %d probes x %d paths, bands 0..%d in %.3fms" % (cfg["probes"], len(pos), spp, order, ms))
+
+
 def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
     if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
@@ -201,6 +230,12 @@ def main(argv=None):
                               cfg["nlm"] or "spp" in cfg["over"]):
         raise SystemExit("-irradiance bakes one frame's points and renders nothing: no batch mode, no -complexity, -firsthit, -out, -save, "
                          "-resume, -nlm or -spp (the paths per point are -irradiance_spp)")
+    if bool(cfg["probes"]) != bool(cfg["probes_at"]):
+        raise SystemExit("-probes=OUT.npz and -probes_at=IN.npy go together")
+    if cfg["probes"] and ("%" in cfg["file"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["out"] or cfg["save"] or cfg["resume"] or
+                          cfg["nlm"] or "spp" in cfg["over"]):
+        raise SystemExit("-probes bakes light probes and renders nothing: no batch mode, no -complexity, -firsthit, -irradiance, -out, -save, "
+                         "-resume, -nlm or -spp (the paths per probe are -probes_spp)")
     if "%" in cfg["file"]:
         return batch(cfg)
     t0 = time.perf_counter()
@@ -220,6 +255,12 @@ def main(argv=None):
     if cfg["irradiance"]:
         irradiance(r, cam, opt, cfg)
         r.close()
+        return 0
+    if cfg["probes"]:
+        try:
+            probes(r, opt, cfg)
+        finally:
+            r.close()
         return 0
     r.init(opt.width, opt.height)
     print("Created renderer in %fms" % ((time.perf_counter() - t0)*1000.0))

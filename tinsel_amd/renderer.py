@@ -96,6 +96,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_gather_radiance"):
         L.tinsel_hip_gather_radiance.argtypes = [vp, ci, C.c_longlong, vp, ci, ci, vp, vp]
         L.tinsel_hip_gather_radiance_device.argtypes = [vp, ci, C.c_longlong, vp, ci, ci, vp, vp, vp]
+    if hasattr(L, "tinsel_hip_gather_sh"):
+        L.tinsel_hip_gather_sh.argtypes = [vp, ci, ci, C.c_longlong, vp, ci, ci, vp, vp]
+        L.tinsel_hip_gather_sh_device.argtypes = [vp, ci, ci, C.c_longlong, vp, ci, ci, vp, vp, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -176,6 +179,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_trace_rays", "tinsel_hip_trace_rays_device", "tinsel_hip_trace_camera",
     "tinsel_hip_trace_radiance", "tinsel_hip_trace_radiance_device",
     "tinsel_hip_gather_radiance", "tinsel_hip_gather_radiance_device",
+    "tinsel_hip_gather_sh", "tinsel_hip_gather_sh_device",
 ]
 
 
@@ -228,6 +232,53 @@ def gather_points(positions, normals, samples, time=1.0, base_seed=0, seeds=None
         seeds = (int(base_seed) + np.arange(n, dtype=np.uint64)*np.uint64(int(samples))) & np.uint64(0xffffffff)
     pts["seed"] = np.asarray(seeds).astype(np.uint32)
     return pts
+
+
+def sh_basis(directions, order=2):
+    """The real orthonormal spherical harmonics of bands 0 .. order (graphics convention) at unit directions [..., 3] -> [..., (order + 1)^2],
+    in float32 and in the operation order include/tinsel_hip.h states: the mirror of what tinsel_hip_gather_sh multiplies a path's radiance by."""
+    order = int(order)
+    if not 0 <= order <= abi.GATHER_SH_MAX_ORDER:
+        raise ValueError("sh_basis: order is 0, 1 or 2")
+    d = np.asarray(directions, np.float32)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("sh_basis: directions [..., 3] are expected")
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    f = np.float32
+    Y = [np.full(x.shape, f(0.28209479), np.float32)]
+    if order >= 1:
+        Y += [f(0.48860251)*y, f(0.48860251)*z, f(0.48860251)*x]
+    if order >= 2:
+        Y += [(f(1.0925484)*x)*y, (f(1.0925484)*y)*z, f(0.31539157)*((f(3.0)*z)*z - f(1.0)), (f(1.0925484)*x)*z, f(0.54627422)*(x*x - y*y)]
+    out = np.stack(Y, axis=-1)
+    assert out.dtype == np.float32
+    return out
+
+
+SH_COSINE_LOBE = (np.pi, 2.0*np.pi/3.0, np.pi/4.0)        # the clamped cosine's zonal factors A_l of bands 0, 1, 2
+
+
+def sh_irradiance(coeffs, normals):
+    """Irradiance from SH radiance coefficients, in float64: E(n) = sum_i A_l(i) c_i Y_i(n), A = pi, 2 pi/3, pi/4 for bands 0, 1, 2.
+    `coeffs` [n, C, 3] (or [C, 3]: one probe) are the coefficients of the incident radiance, already scaled -- 4 pi * the means of a
+    sphere-mode gather_sh; `normals` [n, 3] unit vectors, one per probe, or [m, 3] against one probe.  Returns [n, 3] (or [m, 3])."""
+    c = np.asarray(coeffs, np.float64)
+    nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or c.shape[1] not in (1, 4, 9) or c.shape[2] != 3 or (c.shape[0] != 1 and c.shape[0] != nrm.shape[0]):
+        raise ValueError("sh_irradiance: coeffs [n, C, 3] with C = 1, 4 or 9 and normals [n, 3] (or [m, 3] against one probe) are expected")
+    order = {1: 0, 4: 1, 9: 2}[c.shape[1]]
+    x, y, z = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    Y = [np.full(x.shape, 0.5*np.sqrt(1.0/np.pi))]
+    if order >= 1:
+        k = np.sqrt(3.0/(4.0*np.pi))
+        Y += [k*y, k*z, k*x]
+    if order >= 2:
+        k = 0.5*np.sqrt(15.0/np.pi)
+        Y += [k*x*y, k*y*z, 0.25*np.sqrt(5.0/np.pi)*(3.0*z*z - 1.0), k*x*z, 0.5*k*(x*x - y*y)]
+    band = np.array([SH_COSINE_LOBE[l] for l in (0, 1, 1, 1, 2, 2, 2, 2, 2)][:c.shape[1]])
+    return np.einsum("ni,nic->nc", np.stack(Y, axis=-1)*band, np.broadcast_to(c, (nrm.shape[0],) + c.shape[1:]))
 
 
 def _check(rc, what):
@@ -638,6 +689,30 @@ class HipRenderer:
         starts = np.zeros(n*max(samples, 0), abi.PATH_START_DTYPE) if return_starts else None
         _check(self._L.tinsel_hip_gather_radiance(self._h, m, n, ptr, samples, max_depth, _host_ptr(out),
                                                   starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), "tinsel_hip_gather_radiance")
+        return (out, starts) if return_starts else out
+
+    def gather_sh(self, points, samples, max_depth, order=2, mode="sphere", return_starts=False):
+        """SH gather queries on the resident scene (tinsel_hip_gather_sh*): gather()'s paths, point by point and draw by draw, projected
+        onto the real spherical harmonics of bands 0 .. order instead of averaged: float32 (n, C, 4), C = (order + 1)^2, entry [k, i, c]
+        the mean over s, summed in ascending s, of radiance_c * Y_i(direction) (sh_basis), word 3 zero; no 4 pi or pi folded in -- for
+        mode "sphere" 4 pi * the means are the SH coefficients of the incident radiance (sh_irradiance takes those), for "cosine" pi * the
+        means those of the cosine-weighted radiance about the normal.  `points`, the host and the device entry, return_starts and what is
+        left alone: as gather()."""
+        samples, max_depth, order, m = int(samples), int(max_depth), int(order), GATHER_MODES[mode] if isinstance(mode, str) else int(mode)
+        coeffs = (order + 1)**2 if 0 <= order <= abi.GATHER_SH_MAX_ORDER else 1       # (an order out of range is the library's to refuse)
+        n, ptr, device, stream = self._records("gather_sh", points, 8, "GATHER_POINT_DTYPE")
+        if device is not None:
+            import torch
+            out = torch.empty((n, coeffs, 4), dtype=torch.float32, device=device)
+            starts = torch.empty((n*max(samples, 0), 12), dtype=torch.float32, device=device) if return_starts else None
+            if n:
+                _check(self._L.tinsel_hip_gather_sh_device(self._h, m, order, n, ptr, samples, max_depth, out.data_ptr(),
+                                                           starts.data_ptr() if return_starts else None, stream), "tinsel_hip_gather_sh_device")
+            return (out, starts) if return_starts else out
+        out = np.zeros((n, coeffs, 4), np.float32)
+        starts = np.zeros(n*max(samples, 0), abi.PATH_START_DTYPE) if return_starts else None
+        _check(self._L.tinsel_hip_gather_sh(self._h, m, order, n, ptr, samples, max_depth, _host_ptr(out),
+                                            starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), "tinsel_hip_gather_sh")
         return (out, starts) if return_starts else out
 
     def trace_camera(self, camera, width, height, time=1.0):
