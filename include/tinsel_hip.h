@@ -417,6 +417,45 @@ int tinsel_hip_set_detail_counters(tinsel_hip* r, int enable);
 int tinsel_hip_render_cost(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
                            uint32_t pass_begin, int passes, uint32_t* out_host);
 
+/* Feature buffers: the guide images a denoiser or a compositor takes beside the beauty -- albedo, shading normal, depth, coverage --
+ * reconstructed EXACTLY as the beauty is.  For every path of the passes [pass_begin, pass_begin + passes) -- pass s at pixel (i, j): the
+ * generator Random(i + j*W + pass_seed(pass_begin + s)), draws x, y, t, raster position (x + i, y + j), shutter time
+ * Lerp(shutter_start, shutter_end, t): the beauty's own camera sample -- one closest-hit Trace() at that time gives per requested plane
+ *   TINSEL_FEATURE_ALBEDO   the hit primitive's tinsel_material.color, bit for bit
+ *   TINSEL_FEATURE_NORMAL   FaceForward(n, -direction): what tinsel_ray_hit carries for that ray
+ *   TINSEL_FEATURE_DEPTH    (t, t*t, 1.0f), t*t one fp32 multiply
+ * and (0, 0, 0) at a miss, and each plane is accumulated by AddSample's arithmetic (render.cpp:401-445) with options->filter at the path's
+ * raster position: the same weights, in the same order, as the beauty's.  The clamp is +infinity; options->clamp, max_depth, exposure and
+ * limit are ignored.  The albedo is the first surface's: specular surfaces are not looked through.
+ * `out` holds popcount(features) planes of W*H float4 in ascending bit order, out[(p*H*W + j*W + i)*4 + c]: xyz the weighted sum, w the
+ * weight sum, as in the accumulator; every plane starts from zero, so the call overwrites.  albedo = xyz/w; the mean normal is xyz/w,
+ * renormalised by the caller; of DEPTH z/w is the coverage (alpha), x/z the mean depth over hits, y/z - (x/z)^2 its variance.
+ * The seeds are a table of the call's own; the renderer's generator is only read.  The call respects the shard as a render does: a rank
+ * generates the samples of the pixels it owns and adds them wherever their footprints reach, and the sum over the ranks is the whole
+ * frame's planes up to fp32 summation order.  The scene is the one in force; tinsel_hip_set_arithmetic's arm traces the rays (the
+ * accumulate stage is the same in both).  The accumulator, the pass index, the pass seeds, the statistics, the tuning, look-ahead and the
+ * path buffers are left as they were, and tinsel_hip_stats does not count the call.  Kernels "k_features" (once per batch) and
+ * "k_accumulate" (once per plane and batch) in tinsel_hip_kernel_times (with kernel timing on, the call starts a new record like a render).
+ * Needs options->mode == TINSEL_MODE_PATHTRACE and the frame size of the last tinsel_hip_init.  Returns -1 and writes nothing for: a null
+ * argument, passes < 1, features == 0 or features > 7, another mode, a frame size that does not match (or no tinsel_hip_init), a moved
+ * primitive without tinsel_hip_rebuild_scene, and for the device entry an out_dev that is not 16-byte aligned.
+ * Memory, kept until tinsel_hip_destroy: 16 bytes x popcount(features) per path slot of a batch -- a batch holds whole passes,
+ * max(1, floor(batch_paths / slots per pass)) of them and no more than `passes`, a pass W*H slots (a shard: its own tiles); 1024 x 1024,
+ * 16 passes, three planes: 768 MB -- plus 4 bytes per pass for the seeds, and for the host entry popcount(features)*W*H*16 bytes of planes.
+ * Batches run one after the other and the result does not depend on the cut. */
+#define TINSEL_FEATURE_ALBEDO 1u   /* bit 0 */
+#define TINSEL_FEATURE_NORMAL 2u   /* bit 1 */
+#define TINSEL_FEATURE_DEPTH  4u   /* bit 2 */
+
+/* host array of popcount(features)*W*H*4 floats; returns when it is written */
+int tinsel_hip_render_features(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                               uint32_t pass_begin, int passes, unsigned features, float* out_host);
+/* device array, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for.  The call works in buffers of its own
+ * and only reads the scene, like a ray query: it waits for nothing the renderer has in flight and nothing of the renderer's waits for it;
+ * a later features call on another stream waits, on the device, for this one. */
+int tinsel_hip_render_features_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                      uint32_t pass_begin, int passes, unsigned features, float* out_dev, void* stream);
+
 /* Ray queries on the resident scene: the reference's Trace() (render.cpp:17-62) for rays the caller chooses.
  * TINSEL_QUERY_CLOSEST: the smallest t > 0 over the primitives the ray reaches (an exact tie: the one the scene BVH walk meets first),
  * that primitive's index and its normal turned towards the ray, FaceForward(n, -direction); a miss is t = FLT_MAX, primitive = -1,

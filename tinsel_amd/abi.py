@@ -164,6 +164,9 @@ class GatherPoint(C.Structure):
 GATHER_POINT_DTYPE = [("px", "<f4"), ("py", "<f4"), ("pz", "<f4"), ("time", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("seed", "<u4")]
 GATHER_COSINE, GATHER_SPHERE = 0, 1
 GATHER_SH_MAX_ORDER = 2       # tinsel_hip_gather_sh*: bands 0 .. order, (order + 1)^2 coefficients per channel
+# tinsel_hip_render_features*: the planes a call asks for, by bit; the output holds them in ascending bit order (FEATURE_NAMES' order)
+FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 1, 2, 4
+FEATURE_NAMES = ("albedo", "normal", "depth")
 
 
 class KernelTimeV1(C.Structure):

@@ -212,6 +212,32 @@ int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const 
     });
 }
 
+// Feature buffers (tn_features.h, tn_host_features.h): the first-hit albedo, normal and depth of the camera's own paths, reconstructed as the
+// beauty is.  Own seeds, own buffers: nothing of the renderer's frame state is written, look-ahead work in flight is left alone, no statistics.
+int tinsel_hip_render_features_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                      unsigned features, float* out_dev, void* stream)
+{
+    if (features_args(r, camera, options, passes, features, out_dev, "render_features_device"))
+        return -1;
+    if (query_arrays({ { out_dev, (size_t)r->width*r->height*sizeof(float4)*(size_t)__builtin_popcount(features) } }, "render_features_device") ||
+        query_ready(r, "render_features_device"))
+        return -1;
+    return features_enqueue(r, camera, options, pass_begin, passes, features, (float4*)out_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_features(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                               unsigned features, float* out_host)
+{
+    if (features_args(r, camera, options, passes, features, out_host, "render_features") || query_ready(r, "render_features"))
+        return -1;
+    const size_t bytes = (size_t)r->width*r->height*sizeof(float4)*(size_t)__builtin_popcount(features);
+    if (query_buffer(r->featOut, bytes) || features_enqueue(r, camera, options, pass_begin, passes, features, (float4*)r->featOut.get(), nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_host, r->featOut.get(), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

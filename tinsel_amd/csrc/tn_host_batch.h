@@ -1089,13 +1089,14 @@ int launch_accumulate_kernels(int numCUs, int choice, bool allowSupport, const u
 }
 
 // The accumulate stage of a traced batch: adds the batch passes [fp.accBegin, fp.accEnd), their radiance at `rad`, to `target`.
-int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* rad, float4* target)
+// passSeeds: the seed table fp.passBase indexes -- the render call's (null), or a table of the caller's own (feature buffers)
+int launch_accumulate(tinsel_hip* r, hipStream_t st, const FrameParams& fp, float4* rad, float4* target, const uint32_t* passSeeds = nullptr)
 {
     ScopedTimer t(r, KN_ACCUMULATE, st);
     const bool listed = fp.shardWorld > 1 && accumulate_tiled_fits(fp);         // a shard's launch: the tiles that have candidates of its own
     if (listed && accumulate_tile_list(r, fp))
         return -1;
-    launch_accumulate_kernels(r->numCUs, r->tune.accumulate, true, r->passSeeds, listed ? r->accTilesDev.get() : nullptr, listed ? r->accTilesCount : -1, st, fp,
+    launch_accumulate_kernels(r->numCUs, r->tune.accumulate, true, passSeeds ? passSeeds : r->passSeeds, listed ? r->accTilesDev.get() : nullptr, listed ? r->accTilesCount : -1, st, fp,
                               rad, target);
     HIP_TRY(hipGetLastError());
     return 0;

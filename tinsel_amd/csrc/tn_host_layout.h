@@ -298,8 +298,8 @@ constexpr size_t kArenaLdsLimit = 32768;        // arenas up to this size are st
 
 const char* kKernelNames[] = { "k_generate", "k_extend", "k_shade", "k_shadow", "k_accumulate", "k_mega", "k_normals", "k_bounce",
                                "k_present", "k_nlm_means", "k_nlm", "k_walk", "k_lights", "k_seg", "k_step", "k_cost", "k_query", "k_generate_rays",
-                               "k_generate_gather", "k_gather_reduce", "k_gather_sh_reduce" };
-enum { KN_GENERATE = 0, KN_EXTEND, KN_SHADE, KN_SHADOW, KN_ACCUMULATE, KN_MEGA, KN_NORMALS, KN_BOUNCE, KN_PRESENT, KN_NLM_MEANS, KN_NLM, KN_WALK, KN_LIGHTS, KN_SEG, KN_STEP, KN_COST, KN_QUERY, KN_GENERATE_RAYS, KN_GENERATE_GATHER, KN_GATHER_REDUCE, KN_GATHER_SH_REDUCE, KN_COUNT };
+                               "k_generate_gather", "k_gather_reduce", "k_gather_sh_reduce", "k_features" };
+enum { KN_GENERATE = 0, KN_EXTEND, KN_SHADE, KN_SHADOW, KN_ACCUMULATE, KN_MEGA, KN_NORMALS, KN_BOUNCE, KN_PRESENT, KN_NLM_MEANS, KN_NLM, KN_WALK, KN_LIGHTS, KN_SEG, KN_STEP, KN_COST, KN_QUERY, KN_GENERATE_RAYS, KN_GENERATE_GATHER, KN_GATHER_REDUCE, KN_GATHER_SH_REDUCE, KN_FEATURES, KN_COUNT };
 
 struct TimedSpan { int kernel; Event start, stop; };
 

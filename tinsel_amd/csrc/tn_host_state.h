@@ -173,6 +173,14 @@ struct tinsel_hip
     // gather queries (tinsel_hip_gather_radiance*, tn_host_gather.h): the radiance of a batch's paths by slot, which k_gather_reduce reads;
     // grown on demand, and the host entry's tinsel_path_start records where the caller asks for them
     DevBuf<unsigned char> gatherRad, gatherStartsDev;
+    // feature buffers (tinsel_hip_render_features*, tn_host_features.h): k_features' records of a batch (16 bytes per requested plane and
+    // path slot), the call's own seed table, the host entry's planes -- grown on demand, freed with the renderer -- and the event behind the
+    // last call's last launch, which a call on another stream waits for before it writes them
+    DevBuf<unsigned char> featRec, featOut;
+    DevBuf<uint32_t> featSeeds;
+    Event featFence;
+    hipStream_t featFenceStream = nullptr;
+    bool featFencePending = false;
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)

@@ -12,6 +12,7 @@
 //   tn_query.h        k_query: ray queries on the resident scene (closest hit / occlusion of caller rays, closest hit of the camera's)
 //   tn_radiance.h     k_generate_rays: radiance queries -- the split and paired pipelines entered with paths the caller starts
 //   tn_gather.h       k_generate_gather, k_gather_reduce, k_gather_sh_reduce: gather queries -- S paths per surface point drawn on the device, one mean (or its SH projection) per point
+//   tn_features.h     k_features: the first-hit features (albedo, normal, depth) of the camera's own paths, by slot, for the accumulate kernels
 //   here              k_mega (one lane per whole path: the A/B arm), k_cost (its counters as a per-pixel map), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
 //
 // Every pipeline runs the same per-path arithmetic (tn_integrator.h, tn_bsdf.h, tn_isect.h) and leaves a finished path's radiance in
@@ -31,6 +32,7 @@
 #include "tn_query.h"
 #include "tn_radiance.h"
 #include "tn_gather.h"
+#include "tn_features.h"
 
 namespace tn {
 

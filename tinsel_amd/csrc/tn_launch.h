@@ -90,7 +90,9 @@ namespace tn {
     X(PK_GENERATE_RAYS,         kBlock, 0, GENERATE_RAYS, k_generate_rays)                                          \
     X(PK_GENERATE_GATHER,       kBlock, 0, GENERATE_GATHER, k_generate_gather)                                      \
     X(PK_GATHER_REDUCE,         kBlock, 0, GATHER_REDUCE, k_gather_reduce)                                          \
-    X(PK_GATHER_SH_REDUCE,      kShWave, 0, GATHER_SH_REDUCE, k_gather_sh_reduce)
+    X(PK_GATHER_SH_REDUCE,      kShWave, 0, GATHER_SH_REDUCE, k_gather_sh_reduce)                                   \
+    X(PK_FEATURES_LDS,          kBlock, 0, FEATURES, k_features<true>)                                              \
+    X(PK_FEATURES,              kBlock, 0, FEATURES, k_features<false>)
 
 enum PathKernel : int
 {
@@ -126,6 +128,7 @@ struct LaunchArgs
     RadianceJob radiance;           // k_generate_rays
     GatherJob gather;               // k_generate_gather, k_gather_reduce, k_gather_sh_reduce
     int shOrder;                    // k_gather_sh_reduce: the highest band
+    FeatureJob features;            // k_features
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -144,6 +147,7 @@ struct LaunchArgs
 #define TN_ARGS_GENERATE_GATHER a.ss, a.ctl, a.gather, a.scene.primBoxes, a.bins
 #define TN_ARGS_GATHER_REDUCE a.ps.rad, a.gather
 #define TN_ARGS_GATHER_SH_REDUCE a.ps.rad, a.gather, a.shOrder
+#define TN_ARGS_FEATURES a.scene, a.features, a.cam, a.fp, a.passSeeds, a.stackEntries
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

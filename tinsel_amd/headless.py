@@ -5,6 +5,7 @@
                                   [-complexity=rays|nodes|tris|prims] [-firsthit=buffers.npz]
                                   [-irradiance=bake.npz] [-irradiance_spp=N]
                                   [-probes=probes.npz -probes_at=positions.npy] [-probes_spp=N] [-probes_order=0|1|2]
+                                  [-features=features.npz] [-features_spp=N]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -44,6 +45,12 @@ belong to a render (-out, -save, -resume, -nlm, -spp), -firsthit, -complexity an
 float32 -- the SH coefficients of the incident radiance, which tinsel_amd.sh_irradiance turns into the irradiance for any normal -- with
 `positions` beside it; probe k draws from the seeds k*spp .. k*spp + spp - 1 at time 1.  Exits without rendering: the options -irradiance
 refuses are refused beside it, and so is -irradiance.
+-features=FILE.npz writes, beside a normal render, the guide buffers a denoiser or a compositor takes (HipRenderer.features): the first-hit
+albedo, shading normal and depth of the render's own camera samples of passes [0, -features_spp) (default min(spp, 16)), reconstructed with
+the render's filter exactly as the image is.  The file holds the raw planes `albedo_plane`, `normal_plane`, `depth_plane` ([H, W, 4]
+float32: weighted sum xyz, weight sum w) and tinsel_amd.feature_images of them: `albedo` [H, W, 3], `normal` [H, W, 3] (unit length),
+`depth`, `depth_variance`, `coverage` [H, W], and `passes`.  Refused with batch mode, -resume (its passes are not [0, N)), -complexity,
+-firsthit, -irradiance and -probes, which render no image.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -55,7 +62,7 @@ import numpy as np
 
 from . import abi
 from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
-from .renderer import Scene, create_gpu_renderer, gather_points
+from .renderer import Scene, create_gpu_renderer, feature_images, gather_points
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
 
@@ -64,7 +71,8 @@ def parse_args(argv):
     if len(argv) < 2:
         raise SystemExit(__doc__)
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
-           "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "over": {}}
+           "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
+           "over": {}}
     for a in argv[1:-1]:
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
@@ -78,8 +86,12 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features"):
             cfg[k] = v
+        elif k == "features_spp":
+            cfg[k] = int(v)
+            if cfg[k] < 1:
+                raise SystemExit("-features_spp=%s: want 1 or more" % v)
         elif k == "probes_spp":
             cfg[k] = int(v)
             if not 1 <= cfg[k] <= 65536:
@@ -220,8 +232,25 @@ def probes(r, opt, cfg):
     print("wrote %s: %d probes x %d paths, bands 0..%d in %.3fms" % (cfg["probes"], len(pos), spp, order, ms))
 
 
+def features(r, cam, opt, cfg):
+    """-features: the guide buffers of the render's own samples of passes [0, N) (tinsel_hip_render_features)"""
+    n = cfg["features_spp"] if cfg["features_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
+    ts = time.perf_counter()
+    planes = r.features(cam, opt, 0, n)
+    ms = (time.perf_counter() - ts)*1000.0
+    images = feature_images(planes)
+    np.savez(cfg["features"], passes=np.int64(n), **{k + "_plane": v for k, v in planes.items()}, **images)
+    print("wrote %s: %dx%d, %d passes in %.3fms, coverage %.4f" % (cfg["features"], opt.width, opt.height, n, ms, float(images["coverage"].mean())))
+
+
 def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
+    if cfg["features_spp"] and not cfg["features"]:
+        raise SystemExit("-features_spp goes with -features=OUT.npz")
+    if cfg["features"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                            cfg["probes_at"]):
+        raise SystemExit("-features writes the guide buffers of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
+                         "-firsthit, -irradiance or -probes")
     if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
         raise SystemExit("-complexity renders one cost map: no batch mode, -save or -resume")
     if cfg["firsthit"] and ("%" in cfg["file"] or cfg["complexity"]):
@@ -277,6 +306,8 @@ def main(argv=None):
 
     image, samples = render_frame(r, cam, opt, cfg, samples)
 
+    if cfg["features"]:
+        features(r, cam, opt, cfg)
     if cfg["save"]:
         np.savez(cfg["save"], accum=r.read_accum(), samples=np.int64(samples))
     if cfg["out"]:

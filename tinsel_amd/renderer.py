@@ -99,6 +99,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_gather_sh"):
         L.tinsel_hip_gather_sh.argtypes = [vp, ci, ci, C.c_longlong, vp, ci, ci, vp, vp]
         L.tinsel_hip_gather_sh_device.argtypes = [vp, ci, ci, C.c_longlong, vp, ci, ci, vp, vp, vp]
+    if hasattr(L, "tinsel_hip_render_features"):       # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_features.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
+        L.tinsel_hip_render_features_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -180,6 +183,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_trace_radiance", "tinsel_hip_trace_radiance_device",
     "tinsel_hip_gather_radiance", "tinsel_hip_gather_radiance_device",
     "tinsel_hip_gather_sh", "tinsel_hip_gather_sh_device",
+    "tinsel_hip_render_features", "tinsel_hip_render_features_device",
 ]
 
 
@@ -279,6 +283,51 @@ def sh_irradiance(coeffs, normals):
         Y += [k*x*y, k*y*z, 0.25*np.sqrt(5.0/np.pi)*(3.0*z*z - 1.0), k*x*z, 0.5*k*(x*x - y*y)]
     band = np.array([SH_COSINE_LOBE[l] for l in (0, 1, 1, 1, 2, 2, 2, 2, 2)][:c.shape[1]])
     return np.einsum("ni,nic->nc", np.stack(Y, axis=-1)*band, np.broadcast_to(c, (nrm.shape[0],) + c.shape[1:]))
+
+
+def feature_mask(which):
+    """The TINSEL_FEATURE_* bits of an iterable of plane names (abi.FEATURE_NAMES) -- or of an int, taken as the mask itself -- and the
+    names of its planes in the order the library writes them (ascending bit order)"""
+    if isinstance(which, (int, np.integer)):
+        mask = int(which)
+    else:
+        names = [which] if isinstance(which, str) else list(which)
+        for n in names:
+            if n not in abi.FEATURE_NAMES:
+                raise ValueError("features: %r is not one of %s" % (n, ", ".join(abi.FEATURE_NAMES)))
+        mask = sum(1 << abi.FEATURE_NAMES.index(n) for n in set(names))
+    return mask, [n for k, n in enumerate(abi.FEATURE_NAMES) if 0 <= mask <= 7 and mask >> k & 1]
+
+
+def feature_images(planes):
+    """The images a denoiser or a compositor takes, from the raw planes of HipRenderer.features (name -> [H, W, 4]: weighted sum xyz,
+    weight sum w), in float64 -- of the planes that are there:
+      "albedo" [H, W, 3]          xyz/w
+      "normal" [H, W, 3]          xyz/w brought to unit length; 0 where the mean is 0
+      "depth" [H, W]              x/z: the mean depth over the samples that hit something
+      "depth_variance" [H, W]     y/z - (x/z)^2
+      "coverage" [H, W]           z/w: the share of the filter weight that hit something (alpha)
+    and 0 wherever the divisor (w, or the depth plane's z) is 0."""
+    def ratio(num, den):
+        den = np.asarray(den, np.float64)
+        ok = den != 0.0
+        return np.where(ok, np.asarray(num, np.float64)/np.where(ok, den, 1.0), 0.0)
+
+    out = {}
+    if "albedo" in planes:
+        a = np.asarray(planes["albedo"], np.float64)
+        out["albedo"] = ratio(a[..., :3], a[..., 3:4])
+    if "normal" in planes:
+        a = np.asarray(planes["normal"], np.float64)
+        mean = ratio(a[..., :3], a[..., 3:4])
+        out["normal"] = ratio(mean, np.sqrt((mean*mean).sum(axis=-1, keepdims=True)))
+    if "depth" in planes:
+        a = np.asarray(planes["depth"], np.float64)
+        mean = ratio(a[..., 0], a[..., 2])
+        out["depth"] = mean
+        out["depth_variance"] = np.where(a[..., 2] != 0.0, ratio(a[..., 1], a[..., 2]) - mean*mean, 0.0)
+        out["coverage"] = ratio(a[..., 2], a[..., 3])
+    return out
 
 
 def _check(rc, what):
@@ -596,6 +645,35 @@ class HipRenderer:
         _check(self._L.tinsel_hip_render_cost(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes),
                                               out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_cost")
         return out
+
+    def features(self, camera, options, pass_begin=0, passes=1, which=abi.FEATURE_NAMES, out=None):
+        """Feature buffers (tinsel_hip_render_features*): the first-hit albedo, shading normal and depth of the beauty's own camera samples
+        of passes [pass_begin, pass_begin + passes), accumulated with options.filter exactly as the beauty is -- a dict name -> [H, W, 4]
+        float32 of the planes `which` names ("albedo", "normal", "depth"): xyz the weighted sum, w the weight sum (feature_images turns them
+        into albedo, unit normal, depth, depth variance and coverage).  `out`: a contiguous float32 torch tensor [planes, H, W, 4] on this
+        renderer's device takes the device entry on torch's current stream, not waited for, and the dict holds views of it; a numpy array
+        of that shape is filled by the host entry.  Needs init() at the options' frame size; leaves the accumulator, pass index, pass
+        seeds, statistics and tuning as they were."""
+        mask, names = feature_mask(which)
+        H, W = int(options.height), int(options.width)
+        shape = (max(len(names), 1), H, W, 4)
+        if out is not None and not isinstance(out, np.ndarray) and hasattr(out, "data_ptr"):
+            import torch
+            if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError("features: a contiguous float32 tensor %s on the GPU is expected" % (shape,))
+            if out.device.index != self.device:
+                raise ValueError("features: the tensor is on %s, the renderer on device %d" % (out.device, self.device))
+            _check(self._L.tinsel_hip_render_features_device(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), mask,
+                                                             out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "tinsel_hip_render_features_device")
+        else:
+            if out is None:
+                out = np.zeros(shape, np.float32)
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("features: a C-contiguous float32 array %s is expected" % (shape,))
+            _check(self._L.tinsel_hip_render_features(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), mask,
+                                                      out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_features")
+        return {n: out[k] for k, n in enumerate(names)}
 
     def _records(self, who, arg, width, record=None):
         """The record array of trace_rays / radiance / gather: (n, its address, torch device, stream).  A contiguous (n, width) torch tensor
