@@ -760,6 +760,27 @@ void ref_leaf_primitive_intersect(void* h, int prim, int n, const float* in, int
     }
 }
 
+// Trace (render.cpp:17-62: QueryBVH over the scene tree, strict `t < minT`) for caller rays; inputs per row: origin(3) dir(3) time ;
+// outputs: the primitive's index (-1: miss), t, and the normal as Trace() returns it, FaceForwarded (render.cpp:59).  A miss leaves
+// t = REAL_MAX (render.cpp:58) and the normal zero (closestNormal is uninitialised there).
+void ref_leaf_trace(void* h, int n, const float* in, int32_t* outPrim, float* outT, float* outN)
+{
+    RefScene* rs = (RefScene*)h;
+    for (int i = 0; i < n; ++i)
+    {
+        const float* r = in + (size_t)i*7;
+        Ray ray(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]), r[6]);
+        float t = 0.0f;
+        Vec3 nrm(0.0f);
+        const Primitive* p = NULL;
+        const bool hit = Trace(rs->scene, ray, t, nrm, &p);
+        if (!hit) nrm = Vec3(0.0f);
+        outPrim[i] = hit ? (int32_t)(p - &rs->scene.primitives[0]) : -1;
+        outT[i] = t;
+        memcpy(outN + (size_t)i*3, &nrm, 12);
+    }
+}
+
 // PrimitiveSample (intersection.h:855-904); per row: time seed ; outputs pos(3) normal(3) rng state
 void ref_leaf_primitive_sample(void* h, int prim, int n, const float* times, const uint32_t* seeds, float* outPos, float* outN, uint32_t* outRngState)
 {

@@ -1388,6 +1388,28 @@ void port_render_normals(void* h, const tinsel_camera* cam, const tinsel_options
         }
 }
 
+/* trace() for caller rays; rows: origin(3) dir(3) time ; outputs: primitive index (-1: miss), t, the normal as Trace() returns it (FaceForwarded,
+ * render.cpp:59).  A miss leaves t = FLT_MAX (render.cpp:58) and the normal zero. */
+void port_leaf_trace(void* h, int n, const float* in, int32_t* outPrim, float* outT, float* outN)
+{
+    const scene_t* sc = (const scene_t*)h;
+    counters ct;
+    memset(&ct, 0, sizeof(ct));
+    for (int i = 0; i < n; ++i)
+    {
+        const float* r = in + (size_t)i*7;
+        ray_t ray = { v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]), r[6] };
+        float t;
+        vec3 nrm;
+        const tinsel_primitive* p = trace(sc, &ray, &t, &nrm, &ct);
+        if (!p)
+            nrm = v3s(0.0f);
+        outPrim[i] = p ? (int32_t)(p - sc->prims) : -1;
+        outT[i] = t;
+        outN[i*3 + 0] = nrm.x; outN[i*3 + 1] = nrm.y; outN[i*3 + 2] = nrm.z;
+    }
+}
+
 /* ---------------------------------------------------------------------------------------------
  * Display stage: what main.cpp does with the accumulated pixels every frame (main.cpp:258-282)
  * and the 8-bit conversion of WritePng (png.cpp:323-343).  powf / expf are the host libm's.

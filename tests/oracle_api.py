@@ -28,6 +28,17 @@ def have_port():
     return os.path.exists(PORT_SO)
 
 
+def have_ref_trace():
+    """oracle/_ref is built AND exports ref_leaf_trace: a library kept from before that export (a box without the reference sources keeps
+    whatever oracle/_ref it was given, oracle/Makefile) answers everything else but not RefOracle.trace"""
+    if not have_ref():
+        return False
+    try:
+        return hasattr(C.CDLL(REF_SO), "ref_leaf_trace")
+    except OSError:
+        return False
+
+
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -242,6 +253,26 @@ def _bounds_api():
 
 
 _bounds_api()
+
+
+def _trace_api():
+    def trace(self, h, rows):
+        """Trace() (render.cpp:17-62) for caller rays; rows: origin(3) dir(3) time -> (primitive index or -1, t, normal as Trace()
+        returns it, FaceForwarded).  A miss has t = FLT_MAX and a zero normal."""
+        fn = getattr(self.lib, self.prefix + "leaf_trace")
+        fn.restype = None
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rows = np.ascontiguousarray(rows, np.float32)
+        n = rows.shape[0]
+        prim = np.zeros(n, np.int32)
+        t = np.zeros(n, np.float32)
+        nrm = np.zeros((n, 3), np.float32)
+        fn(h, n, _fp(rows), _fp(prim), _fp(t), _fp(nrm))
+        return prim, t, nrm
+    _OracleBase.trace = trace
+
+
+_trace_api()
 
 
 class PortOracle(_OracleBase):

@@ -335,9 +335,13 @@ def test_rays_identical_under_all_three_trees(tmp_path, shape, n):
         # the reference's own traversal keeps a 32-entry stack (intersection.h): its chains over degenerate meshes overflow it, so it is
         # asked only where its tree fits
         if m.tree()[1]["stackNeed"] <= 32:
-            want_hit, want_t, _ = m.R.primitive_intersect(m.h, 0, rows)
+            want_hit, want_t, want_n = m.R.primitive_intersect(m.h, 0, rows)
             assert np.array_equal(hit, want_hit != 0)
             assert np.array_equal(out["reference"][hit, 1].view(np.uint32), want_t[hit].view(np.uint32))
+            # ... and the normal: of two triangles with the same t (shared edges, duplicated triangles) only the visit order names the winner
+            differ = (np.ascontiguousarray(out["reference"][hit, 2:5]).view(np.uint32) != np.ascontiguousarray(want_n[hit]).view(np.uint32)).any(axis=1)
+            print("%s-%d: %d of %d normals differ from the reference's" % (shape, n, differ.sum(), hit.sum()))
+            assert not differ.any()
         print("%s-%d: %d rays, %d hits" % (shape, n, len(rows), hit.sum()))
         for label in ("lbvh", "ploc"):
             assert np.array_equal(out[label][:, 0] > 0.5, hit), label

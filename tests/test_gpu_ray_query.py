@@ -273,6 +273,15 @@ def test_closest_hit_and_occlusion_equal_the_reference(ref, name):
         rec = r.trace_rays(rays, "closest")
         table, _ = _check_closest(ref, h, name, rays, rec)
         tmin = table[0]
+        # a second, stronger check: the reference's own Trace() (render.cpp:17-62) on the same rays knows the visit order, so every ray --
+        # those with several primitives at the minimum and those with a near-zero dot included -- has one answer: primitive, t, normal bits
+        # (an oracle/_ref kept from before ref_leaf_trace cannot be asked: the checks above stand alone there, as they did)
+        if oa.have_ref_trace():
+            wp, wt, wn = ref.trace(h, np.ascontiguousarray(rays[:, [0, 1, 2, 4, 5, 6, 3]]))
+            got_n = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=1)
+            differ = (int((rec["primitive"] != wp).sum()), int((rec["t"].view(np.uint32) != wt.view(np.uint32)).sum()),
+                      int((got_n.view(np.uint32) != wn.view(np.uint32)).any(axis=1).sum()))
+            assert differ == (0, 0, 0), "%s: rays that differ from Trace() in (primitive, t, normal): %s" % (name, differ)
         for kind in TMAX_KINDS:
             q = rays.copy()
             q[:, 7] = _tmax(kind, tmin)
