@@ -287,11 +287,14 @@ int tinsel_hip_set_mesh_bvh(tinsel_hip* r, int mode, double* build_ms);
 
 /* Refit for deforming meshes (per-frame vertex animation with unchanged topology; the reference rebuilds with its host SAH
  * sweep, mesh.cpp:314-338 -- 1.1 s for 524k triangles): `primitive`'s mesh gets new vertex positions (num_vertices x 3
- * floats, host; must be the vertex count the mesh was created with) and optionally new vertex normals; the triangle
+ * floats, host; must be the vertex count the mesh was created with) and optionally new vertex normals (num_vertices x 3
+ * floats, host; normals_xyz == NULL keeps the normals the mesh has); the triangle
  * records are re-gathered and every box of the mesh's CURRENT tree (the reference's, or a device-built one) is recomputed
- * bottom-up on the device -- exactly the boxes the reference's builder would store for that tree shape; the area CDF and
- * PrimitiveArea of every instance follow (Mesh::RebuildCDF's serial order).  All instances of the mesh change.  Meshes
- * small enough for the LDS-staged arena are refused (create a new renderer: it costs less than the refit). */
+ * bottom-up on the device -- exactly the boxes the reference's builder would store for that tree shape -- and, while a
+ * device-built tree is in use, of the reference's tree too; the area CDF and PrimitiveArea of every instance follow
+ * (Mesh::RebuildCDF's serial order), and so does the scene level: the leaf box of every instance is PrimitiveBounds under
+ * the transforms in force, its ancestors the union of their children.  All instances of the mesh change.  A mesh small
+ * enough for the LDS-staged arena is refitted like any other, in the arena's copy in HBM that every launch stages from. */
 int tinsel_hip_refit_mesh(tinsel_hip* r, int primitive, const float* positions_xyz, int num_vertices, const float* normals_xyz);
 
 /* Primitives that MOVE between renders, and the scene-level BVH that follows them.  The reference mutates Scene::primitives and
