@@ -136,6 +136,50 @@ def test_no_side_effects(pipeline):
 
 
 @pytest.mark.gpu
+def test_pass_begin_means_the_same_wherever_the_generator_stands():
+    """render_cost and features of passes 5 and 6 take Random(1) advanced 5 times from the renderer's generator where it has not gone past
+    pass 5, else from the seed: every renderer below gives the same bits.  The generator moves only with a render call that the seed table
+    does not cover (the first, a rewind in front of the table, 1024 passes on), to that call's first pass: `fresh`, `rendered` and `back`
+    leave it at 0, `past` takes it to 9 (the restart from the seed) and `rewound` back to 2 (the advance from a generator that has moved)."""
+    scene, cam, opt = _setup("cornell", 50, 37)
+    opt.max_depth = 3
+
+    def made(*script):
+        r = _renderer(scene, opt)
+        for index, passes in script:
+            if index is not None:
+                r.set_pass_index(index)
+            r.render(cam, opt, passes=passes)
+        return r
+
+    def side_passes(r):
+        return r.render_cost(cam, opt, 5, 2), r.features(cam, opt, 5, 2)
+
+    rendered = made((None, 9))
+    renderers = {"fresh": made(), "rendered": rendered, "back": made((None, 9), (2, 1)), "past": made((9, 1)), "rewound": made((9, 1), (2, 1))}
+    try:
+        got = {k: side_passes(r) for k, r in renderers.items()}
+        beauty = rendered.render(cam, opt, passes=2).copy()
+        assert rendered.get_pass_index() == 11
+    finally:
+        for r in renderers.values():
+            r.close()
+    cost, planes = got["fresh"]
+    assert cost.dtype == np.uint32 and cost.any() and all(p.any() for p in planes.values())
+    for k, (c, f) in got.items():
+        assert np.array_equal(c, cost), k
+        assert list(f) == list(planes)
+        for n in planes:
+            assert np.array_equal(np.ascontiguousarray(f[n]).view(np.uint32), np.ascontiguousarray(planes[n]).view(np.uint32)), (k, n)
+    # the calls left the renderer's own passes 9 and 10 what they are without them
+    plain = made((None, 9))
+    try:
+        assert np.array_equal(beauty, plain.render(cam, opt, passes=2))
+    finally:
+        plain.close()
+
+
+@pytest.mark.gpu
 def test_shards_sum_to_the_unsharded_map():
     scene, cam, opt = _setup("many_spheres", 64, 48)
     r = _renderer(scene, opt)

@@ -153,55 +153,28 @@ int tinsel_hip_trace_radiance(tinsel_hip* r, long long n, const tinsel_path_star
     });
 }
 
-// Gather queries (tn_gather.h, tn_host_gather.h): `samples` paths from each point, drawn on the device, one mean per point.  As radiance
+// Gather queries (tn_gather.h, tn_host_gather.h): `samples` paths from each point, drawn on the device, one mean per point -- or, for the SH
+// entries, the (order + 1)^2 coefficients of bands 0 .. order per point (k_gather_sh_reduce behind the same batches).  As radiance
 // queries: nothing of the renderer's frame state is touched, rays and samples are counted.
-int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
-                                      float* out_rgbx_dev, tinsel_path_start* starts_out_dev, void* stream)
+// (order: kGatherMean or, judged by gather_sh_order in the SH entries before they come here, 0 .. 2)
+static int gather_device(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth, float* out_dev,
+                         tinsel_path_start* starts_out_dev, void* stream, const char* who)
 {
-    if (gather_args(r, mode, n, points_dev, samples, max_depth, out_rgbx_dev, "gather_radiance_device"))
-        return -1;
-    if (query_arrays({ { points_dev, (size_t)n*sizeof(tinsel_gather_point) }, { out_rgbx_dev, (size_t)n*sizeof(float4) },
-                       { starts_out_dev, starts_out_dev ? (size_t)n*(size_t)samples*sizeof(tinsel_path_start) : 0 } }, "gather_radiance_device") ||
-        query_ready(r, "gather_radiance_device"))
-        return -1;
-    if (n == 0)
-        return 0;
-    return trace_gather(r, mode, kGatherMean, (size_t)n, points_dev, samples, max_depth, (float4*)out_rgbx_dev, starts_out_dev, (hipStream_t)stream);
-}
-
-int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
-                               float* out_rgbx_host, tinsel_path_start* starts_out_host)
-{
-    if (gather_args(r, mode, n, points_host, samples, max_depth, out_rgbx_host, "gather_radiance") || query_ready(r, "gather_radiance"))
-        return -1;
-    return staged_chunks((size_t)n, gather_chunk((size_t)n, samples, starts_out_host != nullptr), { points_host, &r->queryRaysDev, sizeof(tinsel_gather_point) },
-                         { out_rgbx_host, &r->queryOutDev, sizeof(float4) }, { starts_out_host, &r->gatherStartsDev, sizeof(tinsel_path_start)*(size_t)samples },
-                         [&](size_t, size_t m) {
-        return trace_gather(r, mode, kGatherMean, m, r->queryRaysDev.get(), samples, max_depth, (float4*)r->queryOutDev.get(),
-                            starts_out_host ? r->gatherStartsDev.get() : nullptr, nullptr);
-    });
-}
-
-// SH gather queries: a gather query reduced to the (order + 1)^2 coefficients of bands 0 .. order per point instead of the mean
-// (k_gather_sh_reduce behind the same batches); everything else as above.
-int tinsel_hip_gather_sh_device(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
-                                float* out_dev, tinsel_path_start* starts_out_dev, void* stream)
-{
-    if (gather_sh_order(order, "gather_sh_device") || gather_args(r, mode, n, points_dev, samples, max_depth, out_dev, "gather_sh_device"))
+    if (gather_args(r, mode, n, points_dev, samples, max_depth, out_dev, who))
         return -1;
     if (query_arrays({ { points_dev, (size_t)n*sizeof(tinsel_gather_point) }, { out_dev, (size_t)n*gather_out_each(order)*sizeof(float4) },
-                       { starts_out_dev, starts_out_dev ? (size_t)n*(size_t)samples*sizeof(tinsel_path_start) : 0 } }, "gather_sh_device") ||
-        query_ready(r, "gather_sh_device"))
+                       { starts_out_dev, starts_out_dev ? (size_t)n*(size_t)samples*sizeof(tinsel_path_start) : 0 } }, who) ||
+        query_ready(r, who))
         return -1;
     if (n == 0)
         return 0;
     return trace_gather(r, mode, order, (size_t)n, points_dev, samples, max_depth, (float4*)out_dev, starts_out_dev, (hipStream_t)stream);
 }
 
-int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
-                         float* out_host, tinsel_path_start* starts_out_host)
+static int gather_host(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_host, int samples, int max_depth, float* out_host,
+                       tinsel_path_start* starts_out_host, const char* who)
 {
-    if (gather_sh_order(order, "gather_sh") || gather_args(r, mode, n, points_host, samples, max_depth, out_host, "gather_sh") || query_ready(r, "gather_sh"))
+    if (gather_args(r, mode, n, points_host, samples, max_depth, out_host, who) || query_ready(r, who))
         return -1;
     const size_t each = gather_out_each(order);
     return staged_chunks((size_t)n, gather_chunk((size_t)n, samples, starts_out_host != nullptr, each), { points_host, &r->queryRaysDev, sizeof(tinsel_gather_point) },
@@ -210,6 +183,31 @@ int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const 
         return trace_gather(r, mode, order, m, r->queryRaysDev.get(), samples, max_depth, (float4*)r->queryOutDev.get(),
                             starts_out_host ? r->gatherStartsDev.get() : nullptr, nullptr);
     });
+}
+
+int tinsel_hip_gather_radiance_device(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
+                                      float* out_rgbx_dev, tinsel_path_start* starts_out_dev, void* stream)
+{
+    return gather_device(r, mode, kGatherMean, n, points_dev, samples, max_depth, out_rgbx_dev, starts_out_dev, stream, "gather_radiance_device");
+}
+
+int tinsel_hip_gather_radiance(tinsel_hip* r, int mode, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
+                               float* out_rgbx_host, tinsel_path_start* starts_out_host)
+{
+    return gather_host(r, mode, kGatherMean, n, points_host, samples, max_depth, out_rgbx_host, starts_out_host, "gather_radiance");
+}
+
+int tinsel_hip_gather_sh_device(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_dev, int samples, int max_depth,
+                                float* out_dev, tinsel_path_start* starts_out_dev, void* stream)
+{
+    return gather_sh_order(order, "gather_sh_device") ? -1 :
+           gather_device(r, mode, order, n, points_dev, samples, max_depth, out_dev, starts_out_dev, stream, "gather_sh_device");
+}
+
+int tinsel_hip_gather_sh(tinsel_hip* r, int mode, int order, long long n, const tinsel_gather_point* points_host, int samples, int max_depth,
+                         float* out_host, tinsel_path_start* starts_out_host)
+{
+    return gather_sh_order(order, "gather_sh") ? -1 : gather_host(r, mode, order, n, points_host, samples, max_depth, out_host, starts_out_host, "gather_sh");
 }
 
 // Feature buffers (tn_features.h, tn_host_features.h): the first-hit albedo, normal and depth of the camera's own paths, reconstructed as the
@@ -601,10 +599,7 @@ int tinsel_hip_reserve(tinsel_hip* r, int passes, int max_depth)
         return fail("reserve: bad arguments (Init first)");
     HIP_TRY(hipSetDevice(r->device));
     const size_t perPass = slots_per_pass(r, r->width, r->height);
-    int perBatch = (int)std::max<size_t>(1, batch_slots(r)/perPass);
-    if (perBatch > passes)
-        perBatch = passes;
-    return ensure_batch(r, plan_batch(r, perPass, perBatch, /*mayOverlap*/ false), max_depth);
+    return ensure_batch(r, plan_batch(r, perPass, passes_per_batch(batch_slots(r), perPass, passes), /*mayOverlap*/ false), max_depth);
 }
 
 int tinsel_hip_set_batch_paths(tinsel_hip* r, unsigned long long max_paths)

@@ -233,6 +233,17 @@ int launch_path(tinsel_hip* r, const LaunchArgs& a, hipStream_t st)
     return ok ? 0 : fail("launch: no path-kernel instance " + std::to_string(a.variant));
 }
 
+// What a launch record starts from: zero, the scene in force, traversal stacks of the scene's planned depth and the LDS they take
+LaunchArgs launch_base(const tinsel_hip* r)
+{
+    LaunchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene = r->scene;
+    a.stackEntries = r->stackNeed;
+    a.ldsBytes = (uint32_t)stack_bytes(r);
+    return a;
+}
+
 // What cutting a batch into regions depends on (streaming_grid, cut_regions): plain values, no renderer
 struct RegionSpec
 {
@@ -997,6 +1008,12 @@ size_t slots_per_pass(const tinsel_hip* r, int width, int height, int* tilesXOut
     return std::max<size_t>(1, (size_t)owned*r->shardTile*r->shardTile);
 }
 
+// Whole passes per batch of a call of `passes` under a limit of slotLimit path slots: one at least, however large a pass is
+int passes_per_batch(size_t slotLimit, size_t perPass, int passes)
+{
+    return (int)std::min<size_t>((size_t)passes, std::max<size_t>(1, slotLimit/perPass));
+}
+
 // The support form of k_accumulate_tiled (tn_accumulate.h) adds nothing but what the full window adds when the filter's weight is +0 by
 // construction from one pixel away on: Filter::Gaussian is max(0, expf(a) - offset) with a = -falloff*x*x, and for a <= argZero =
 // log(offset) - 1e-6 (in double, rounded DOWN to float) e^a <= offset*(1 - 1e-6) while expf is off by less than an ulp (1.2e-7): the float
@@ -1363,9 +1380,7 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     r->lastPipeline = p.pipeline;
 
     // what every launch of the batch shares
-    LaunchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = r->scene;
+    LaunchArgs a = launch_base(r);
     a.ps.rad = rad;
     a.ctl = r->ctl;
     if (cam)
@@ -1379,8 +1394,6 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
     a.walkRec = p.walk ? L.walkRec : nullptr;
     a.walkPrims = (uint32_t)r->walkPrims.count;
     a.bins = r->binPrims;
-    a.stackEntries = r->stackNeed;
-    a.ldsBytes = (uint32_t)stack_bytes(r);
     if (p.pipeline == TINSEL_PIPELINE_MEGAKERNEL)
     {
         ScopedTimer t(r, KN_MEGA, st);
@@ -1489,6 +1502,16 @@ void release_spans(tinsel_hip* r)
     r->spans.clear();
 }
 
+// Random(1) advanced `index` times: from the renderer's generator where it has not gone past `index`, else from the seed
+Rng seed_rng_at(const tinsel_hip* r, uint32_t index)
+{
+    const bool behind = r->seedRngIndex <= index;
+    Rng g = behind ? r->seedRng : Rng::seeded(1u);
+    for (uint32_t at = behind ? r->seedRngIndex : 0; at < index; ++at)
+        (void)g.rand();
+    return g;
+}
+
 // The frame of a render call: size, depth, shard, filter (the batch fields: batch_frame)
 FrameParams frame_params(const tinsel_hip* r, const tinsel_options* options)
 {
@@ -1557,13 +1580,8 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
                          (size_t)(r->passIndex - r->passSeedsBase) + (size_t)passes <= r->passSeedsCount;
     if (!covered)
     {
-        if (r->seedRngIndex > r->passIndex)
-        {
-            r->seedRng = Rng::seeded(1u);
-            r->seedRngIndex = 0;
-        }
-        for (; r->seedRngIndex < r->passIndex; ++r->seedRngIndex)
-            (void)r->seedRng.rand();
+        r->seedRng = seed_rng_at(r, r->passIndex);
+        r->seedRngIndex = r->passIndex;
         if (r->passSeedsDev)
             HIP_TRY(hipDeviceSynchronize());
         const size_t want = (size_t)passes + kSeedsAhead;
@@ -1581,9 +1599,7 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     r->passSeeds = r->passSeedsDev.get() + (r->passIndex - r->passSeedsBase);
 
     const size_t perPass = slots_per_pass(r, fp.width, fp.height);
-    int perBatch = (int)std::max<size_t>(1, batch_slots(r)/perPass);
-    if (perBatch > passes)
-        perBatch = passes;
+    const int perBatch = passes_per_batch(batch_slots(r), perPass, passes);
 
     const BatchPlan plan = plan_batch(r, perPass, perBatch, !traceOnly);
     if (ensure_batch(r, plan, fp.maxDepth) || batch_fence_wait(r, st))
@@ -1656,6 +1672,33 @@ int render_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options
     return 0;
 }
 
+// The batches of a side pass over the camera's own paths (the cost map, the feature buffers): `passes` passes of frame fp, perBatch whole
+// passes at a time, their seeds from the table `seeds` (seeds[s]: pass s of the call).  Per batch the launch record of a one-path-per-lane
+// kernel -- the LDS or the plain variant by the scene's residency -- goes to launch(a, fp), which sets its job, times and launches.
+template <class Launch>
+int side_pass_batches(tinsel_hip* r, const CameraParams& cam, FrameParams fp, int passes, int perBatch, const uint32_t* seeds, int variantLds,
+                      int variantPlain, const char* who, Launch launch)
+{
+    const int variant = residency(r->scene, r->scene.arenaLdsBytes) == RES_LDS ? variantLds : variantPlain;
+    for (int done = 0; done < passes; done += perBatch)
+    {
+        fp.passBase = done;
+        fp.numPasses = std::min(perBatch, passes - done);
+        const size_t slots = batch_frame(r, fp);
+        if (!slots)
+            return fail(std::string(who) + ": batch too large");
+        LaunchArgs a = launch_base(r);
+        a.cam = cam;
+        a.fp = fp;
+        a.passSeeds = seeds;
+        a.grid = (int)((slots + kBlock - 1)/kBlock);
+        a.variant = variant;
+        if (launch(a, fp))
+            return -1;
+    }
+    return 0;
+}
+
 // tinsel_hip_render_cost: k_cost over the passes [passBegin, passBegin + passes), in batches under the megakernel's slot limit.  The seeds
 // are the call's own (pass_seed(passBegin + s), the renderer's table and generator are only read) and so is the map: four planes on the
 // device, interleaved per pixel on the host.  No path state, accumulator, pass index or statistics are touched.
@@ -1681,21 +1724,10 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
         return 0;
     }
 
-    // Random(1) advanced passBegin times: from the renderer's generator where it has not gone past passBegin (a copy of it)
     std::vector<uint32_t> seeds((size_t)passes);
-    {
-        Rng g = Rng::seeded(1u);
-        uint32_t at = 0;
-        if (r->seedRngIndex <= passBegin)
-        {
-            g = r->seedRng;
-            at = r->seedRngIndex;
-        }
-        for (; at < passBegin; ++at)
-            (void)g.rand();
-        for (uint32_t& v : seeds)
-            v = g.rand();
-    }
+    Rng g = seed_rng_at(r, passBegin);
+    for (uint32_t& v : seeds)
+        v = g.rand();
 
     DevBuf<uint32_t> seedsDev, costDev;
     if (seedsDev.alloc(seeds.size()) || costDev.alloc(4*npix))
@@ -1708,33 +1740,18 @@ int render_cost_impl(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     FrameParams fp = frame_params(r, options);
 
     const size_t perPass = slots_per_pass(r, fp.width, fp.height);
-    const int perBatch = (int)std::min<size_t>((size_t)passes, std::max<size_t>(1, r->maxBatchSlots/perPass));
+    // (k_cost runs k_mega's path with counting on -- the scene BVH walk, stacks r->stackNeed deep -- so it takes the megakernel's limit)
+    const int perBatch = passes_per_batch(r->maxBatchSlots, perPass, passes);
     const hipStream_t st = nullptr;
-    for (int done = 0; done < passes; done += perBatch)
-    {
-        fp.passBase = done;
-        fp.numPasses = std::min(perBatch, passes - done);
-        const size_t slots = batch_frame(r, fp);
-        if (!slots)
-            return fail("render_cost: batch too large");
-
-        // k_mega's launch (render_batch) with counting on: the scene BVH walk, stacks r->stackNeed deep
-        LaunchArgs a;
-        memset(&a, 0, sizeof(a));
-        a.scene = r->scene;
-        a.cam = cam;
-        a.fp = fp;
-        a.passSeeds = seedsDev.get();
-        a.stackEntries = r->stackNeed;
-        a.ldsBytes = (uint32_t)stack_bytes(r);
-        a.cost = costDev.get();
-        a.grid = (int)((slots + kBlock - 1)/kBlock);
-        a.variant = residency(r->scene, r->scene.arenaLdsBytes) == RES_LDS ? PK_COST_LDS : PK_COST;
-        ScopedTimer t(r, KN_COST, st);
-        if (launch_path(r, a, st))
-            return -1;
-        HIP_TRY(hipGetLastError());
-    }
+    if (side_pass_batches(r, cam, fp, passes, perBatch, seedsDev.get(), PK_COST_LDS, PK_COST, "render_cost", [&](LaunchArgs& a, const FrameParams&) {
+            a.cost = costDev.get();
+            ScopedTimer t(r, KN_COST, st);
+            if (launch_path(r, a, st))
+                return -1;
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }))
+        return -1;
 
     std::vector<uint32_t> planes(4*npix);
     HIP_TRY(hipMemcpy(planes.data(), costDev.get(), sizeof(uint32_t)*planes.size(), hipMemcpyDeviceToHost));

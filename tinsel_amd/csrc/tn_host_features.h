@@ -5,13 +5,13 @@
 namespace {
 
 // Enqueues on st: the planes `features` asks for of the passes [passBegin, passBegin + passes) into target[plane][H][W] (device, 16-byte
-// aligned), each plane from zero.  Per batch of whole passes -- max(1, floor(batch_slots / slots per pass)) of them -- k_features writes one
+// aligned), each plane from zero.  Per batch of whole passes (passes_per_batch, side_pass_batches) k_features writes one
 // 16-byte record per requested plane and path slot into r->featRec (tn_features.h), and one launch_accumulate per plane adds that plane's
 // records to its part of `target` exactly as a render adds a batch's radiance to the accumulator: the call's own seeds for the raster
 // positions, options->filter for the weights, and a clamp of +infinity, which ClampLength's `l > max` never meets.  Batches follow each
 // other on st and every pixel's adds stay in pass order, so the cut shows nowhere.
-// The seeds are the call's own table, pass_seed(passBegin + s), made on the device by k_pass_seeds from a COPY of the renderer's generator
-// (render_cost_impl's rule); the records and the table are the call's own buffers, kept until tinsel_hip_destroy, so neither the path
+// The seeds are the call's own table, pass_seed(passBegin + s), made on the device by k_pass_seeds from seed_rng_at's copy of the
+// renderer's generator; the records and the table are the call's own buffers, kept until tinsel_hip_destroy, so neither the path
 // buffers nor the renderer's seed table are touched and nothing of a render or a look-ahead in flight has to be waited for.  Two calls on
 // two streams share those buffers: the later one's stream waits for the event behind the earlier one's last launch.
 int features_enqueue(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t passBegin, int passes, unsigned features,
@@ -26,7 +26,7 @@ int features_enqueue(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     fp.clampLen = INFINITY;
 
     const size_t perPass = slots_per_pass(r, fp.width, fp.height);
-    const int perBatch = (int)std::min<size_t>((size_t)passes, std::max<size_t>(1, batch_slots(r)/perPass));
+    const int perBatch = passes_per_batch(batch_slots(r), perPass, passes);
     const size_t stride = perPass*(size_t)perBatch;
     if (stride >= (size_t)0xffffffffu)
         return fail("render_features: batch too large");
@@ -46,54 +46,26 @@ int features_enqueue(tinsel_hip* r, const tinsel_camera* camera, const tinsel_op
     if (r->featFencePending && r->featFenceStream != st)
         HIP_TRY(hipStreamWaitEvent(st, r->featFence, 0));
 
-    // Random(1) advanced passBegin times: from the renderer's generator where it has not gone past passBegin (a copy of it)
-    {
-        Rng g = Rng::seeded(1u);
-        uint32_t at = 0;
-        if (r->seedRngIndex <= passBegin)
-        {
-            g = r->seedRng;
-            at = r->seedRngIndex;
-        }
-        for (; at < passBegin; ++at)
-            (void)g.rand();
-        hipLaunchKernelGGL(k_pass_seeds, dim3(1), dim3(1), 0, st, g.s1, g.s2, passes, r->featSeeds.get());
-    }
+    const Rng g = seed_rng_at(r, passBegin);
+    hipLaunchKernelGGL(k_pass_seeds, dim3(1), dim3(1), 0, st, g.s1, g.s2, passes, r->featSeeds.get());
     HIP_TRY(hipMemsetAsync(target, 0, sizeof(float4)*npix*(size_t)planes, st));
 
     float4* const rec = (float4*)r->featRec.get();
-    const Residency res = residency(r->scene, r->scene.arenaLdsBytes);      // (as plan_query places a camera frame's k_query)
-    int rc = 0;
-    for (int done = 0; done < passes && !rc; done += perBatch)
-    {
-        fp.passBase = done;
-        fp.numPasses = std::min(perBatch, passes - done);
-        const size_t slots = batch_frame(r, fp);
-        if (!slots)
-        {
-            rc = fail("render_features: batch too large");
-            break;
-        }
-        LaunchArgs a;
-        memset(&a, 0, sizeof(a));
-        a.scene = r->scene;
-        a.cam = cam;
-        a.fp = fp;
-        a.passSeeds = r->featSeeds.get();
+    const int rc = side_pass_batches(r, cam, fp, passes, perBatch, r->featSeeds.get(), PK_FEATURES_LDS, PK_FEATURES, "render_features",
+                                     [&](LaunchArgs& a, const FrameParams& batch) {
         a.features.out = rec;
         a.features.planeStride = (uint32_t)stride;
         a.features.mask = features;
-        a.stackEntries = r->stackNeed;
-        a.ldsBytes = (uint32_t)stack_bytes(r);
-        a.grid = (int)((slots + kBlock - 1)/kBlock);
-        a.variant = res == RES_LDS ? PK_FEATURES_LDS : PK_FEATURES;
         {
             ScopedTimer t(r, KN_FEATURES, st);
-            rc = launch_path(r, a, st);
+            if (launch_path(r, a, st))
+                return -1;
         }
-        for (int p = 0; p < planes && !rc; ++p)
-            rc = launch_accumulate(r, st, fp, rec + (size_t)p*stride, target + (size_t)p*npix, r->featSeeds.get());
-    }
+        for (int p = 0; p < planes; ++p)
+            if (launch_accumulate(r, st, batch, rec + (size_t)p*stride, target + (size_t)p*npix, r->featSeeds.get()))
+                return -1;
+        return 0;
+    });
     // (whatever was enqueued reads the call's buffers: the next call waits for it, failed or not)
     if (hipEventRecord(r->featFence, st) == hipSuccess)
     {

@@ -55,9 +55,7 @@ int launch_query(tinsel_hip* r, int mode, size_t n, const void* rays, void* out,
                  uint32_t first = 0)
 {
     const QueryPlan plan = plan_query(r, mode);
-    LaunchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = r->scene;
+    LaunchArgs a = launch_base(r);
     a.scene.arenaLdsBytes = plan.arenaLds;
     if (cam)
         a.cam = *cam;

@@ -753,21 +753,7 @@ class HipRenderer:
         device tensor comes back.  return_starts: also the generated abi.PathStart records, path (k, s) at k*samples + s -- a numpy
         array of abi.PATH_START_DTYPE, or an (n*samples, 12) float32 tensor -- which radiance() accepts as they are.  Scene, settings,
         statistics and what is left alone: as radiance()."""
-        samples, max_depth, m = int(samples), int(max_depth), GATHER_MODES[mode] if isinstance(mode, str) else int(mode)
-        n, ptr, device, stream = self._records("gather", points, 8, "GATHER_POINT_DTYPE")
-        if device is not None:
-            import torch
-            out = torch.empty((n, 4), dtype=torch.float32, device=device)
-            starts = torch.empty((n*max(samples, 0), 12), dtype=torch.float32, device=device) if return_starts else None
-            if n:
-                _check(self._L.tinsel_hip_gather_radiance_device(self._h, m, n, ptr, samples, max_depth, out.data_ptr(),
-                                                                 starts.data_ptr() if return_starts else None, stream), "tinsel_hip_gather_radiance_device")
-            return (out, starts) if return_starts else out
-        out = np.zeros((n, 4), np.float32)
-        starts = np.zeros(n*max(samples, 0), abi.PATH_START_DTYPE) if return_starts else None
-        _check(self._L.tinsel_hip_gather_radiance(self._h, m, n, ptr, samples, max_depth, _host_ptr(out),
-                                                  starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), "tinsel_hip_gather_radiance")
-        return (out, starts) if return_starts else out
+        return self._gather("gather", points, int(samples), int(max_depth), None, GATHER_MODES[mode] if isinstance(mode, str) else int(mode), return_starts)
 
     def gather_sh(self, points, samples, max_depth, order=2, mode="sphere", return_starts=False):
         """SH gather queries on the resident scene (tinsel_hip_gather_sh*): gather()'s paths, point by point and draw by draw, projected
@@ -776,21 +762,27 @@ class HipRenderer:
         mode "sphere" 4 pi * the means are the SH coefficients of the incident radiance (sh_irradiance takes those), for "cosine" pi * the
         means those of the cosine-weighted radiance about the normal.  `points`, the host and the device entry, return_starts and what is
         left alone: as gather()."""
-        samples, max_depth, order, m = int(samples), int(max_depth), int(order), GATHER_MODES[mode] if isinstance(mode, str) else int(mode)
-        coeffs = (order + 1)**2 if 0 <= order <= abi.GATHER_SH_MAX_ORDER else 1       # (an order out of range is the library's to refuse)
-        n, ptr, device, stream = self._records("gather_sh", points, 8, "GATHER_POINT_DTYPE")
+        return self._gather("gather_sh", points, int(samples), int(max_depth), int(order), GATHER_MODES[mode] if isinstance(mode, str) else int(mode),
+                            return_starts)
+
+    def _gather(self, who, points, samples, max_depth, order, m, return_starts):
+        """gather() (order None: tinsel_hip_gather_radiance*, an (n, 4) result) and gather_sh() (tinsel_hip_gather_sh*, (n, C, 4))"""
+        entry, lead = ("tinsel_hip_gather_radiance", (m,)) if order is None else ("tinsel_hip_gather_sh", (m, order))
+        # (an order out of range is the library's to refuse)
+        shape = () if order is None else ((order + 1)**2 if 0 <= order <= abi.GATHER_SH_MAX_ORDER else 1,)
+        n, ptr, device, stream = self._records(who, points, 8, "GATHER_POINT_DTYPE")
         if device is not None:
             import torch
-            out = torch.empty((n, coeffs, 4), dtype=torch.float32, device=device)
+            out = torch.empty((n,) + shape + (4,), dtype=torch.float32, device=device)
             starts = torch.empty((n*max(samples, 0), 12), dtype=torch.float32, device=device) if return_starts else None
             if n:
-                _check(self._L.tinsel_hip_gather_sh_device(self._h, m, order, n, ptr, samples, max_depth, out.data_ptr(),
-                                                           starts.data_ptr() if return_starts else None, stream), "tinsel_hip_gather_sh_device")
+                _check(getattr(self._L, entry + "_device")(self._h, *lead, n, ptr, samples, max_depth, out.data_ptr(),
+                                                           starts.data_ptr() if return_starts else None, stream), entry + "_device")
             return (out, starts) if return_starts else out
-        out = np.zeros((n, coeffs, 4), np.float32)
+        out = np.zeros((n,) + shape + (4,), np.float32)
         starts = np.zeros(n*max(samples, 0), abi.PATH_START_DTYPE) if return_starts else None
-        _check(self._L.tinsel_hip_gather_sh(self._h, m, order, n, ptr, samples, max_depth, _host_ptr(out),
-                                            starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), "tinsel_hip_gather_sh")
+        _check(getattr(self._L, entry)(self._h, *lead, n, ptr, samples, max_depth, _host_ptr(out),
+                                       starts.ctypes.data_as(C.c_void_p) if return_starts and starts.size else None), entry)
         return (out, starts) if return_starts else out
 
     def trace_camera(self, camera, width, height, time=1.0):
