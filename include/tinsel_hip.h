@@ -459,6 +459,63 @@ int tinsel_hip_render_features(tinsel_hip* r, const tinsel_camera* camera, const
 int tinsel_hip_render_features_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
                                       uint32_t pass_begin, int passes, unsigned features, float* out_dev, void* stream);
 
+/* Feature-guided denoise: a joint non-local-means filter on LINEAR radiance, in front of the display stage, guided by the planes above.
+ * With features == 0 and demodulate == 0 it is NonLocalMeansFilter (nlm.cpp:35-77) on the normalised colour, bit for bit, falloff =
+ * k_color and AverageFilter's radius = patch_radius; the guide terms add to the exponent.  Everything is fp32, one rounding per
+ * operation (no FMA), IEEE divide, expf as glibc 2.35 evaluates it; tinsel_hip_set_arithmetic does not change the stage.
+ * Inputs, all W*H float4 in accumulator form: the beauty B (xyz the sum, w the weight) and popcount(features) planes in ascending bit
+ * order -- the layout tinsel_hip_render_features returns: A albedo, N normal, D depth.
+ * Prepare, per pixel p: colour c = B.xyz/B.w (0 where B.w == 0), albedo a = A.xyz/A.w, normal n = N.xyz/N.w (the mean normal, not
+ *   renormalised), depth z = D.x/D.z -- each 0 where its divisor is 0 or its plane is absent.  With demodulate: d_k = (a_k < albedo_floor)
+ *   ? albedo_floor : a_k and u_k = c_k/d_k; without: u = c, d = 1.  U = (u, 0).
+ * Means: M = AverageFilter(U, patch_radius) (nlm.cpp:4-33).
+ * Filter, per pixel p, over the window of `radius` clipped to the frame, fx ascending outside, fy ascending inside, tap q:
+ *   e = k_color*LengthSq(M_p - M_q)                                         (dx*dx + dy*dy + dz*dz + dw*dw, left to right)
+ *   ALBEDO: e = e + k_albedo*LengthSq(a_p - a_q)     NORMAL: e = e + k_normal*LengthSq(n_p - n_q)           (three components each)
+ *   DEPTH:  den = z_p*z_p + z_q*z_q, dz = z_p - z_q, e = e + k_depth*((den != 0) ? dz*dz/den : 0)
+ *   weight = expf(-e); sum_k += u_q,k*weight; total += weight               (the term of an absent plane is skipped)
+ * Output: (sum_k*(1.0f/total))*d_p,k in xyz and 1.0f in w: denoised radiance as an accumulator of weight one, which
+ *   tinsel_hip_present_image_device takes.  A pixel with B.w == 0 takes part with colour 0.
+ * The stage is meant for a WHOLE frame: a shard's accumulator holds its own tiles only -- reduce across the ranks first
+ * (tinsel_hip_comm_reduce_accum, or a group's reduced frame) and denoise the sum.
+ * beauty == NULL is the renderer's own accumulator; width and height must then be those of the last tinsel_hip_init.  planes may be
+ * NULL only when features == 0.  The stage works in buffers of its own, owned by the renderer and kept until tinsel_hip_destroy (four
+ * W*H float4 images, and for the host entry the inputs and the output); it leaves the accumulator, the pass index, the statistics, the
+ * tuning and look-ahead as they were.  Returns -1 and writes nothing for: a null argument, a parameter out of range, features > 7,
+ * demodulate without TINSEL_FEATURE_ALBEDO, a non-positive size, for the device entry a pointer that is not 16-byte aligned, and
+ * beauty == NULL without a tinsel_hip_init or with another size.
+ * Timing: the stage's kernels (k_denoise_prepare, k_nlm_means, k_denoise) have no class in tinsel_hip_kernel_times; time the device
+ * entry with events on the stream it is given (profiles/denoise_measure.py). */
+typedef struct tinsel_hip_denoise_params {   /* 32 bytes */
+    int radius;                     /* 1 .. 8: the search window */
+    int patch_radius;               /* 0 .. 4: AverageFilter's radius */
+    float k_color, k_albedo, k_normal, k_depth;   /* finite, >= 0 */
+    int demodulate;                 /* 0 | 1; 1 needs TINSEL_FEATURE_ALBEDO */
+    float albedo_floor;             /* finite, > 0 */
+} tinsel_hip_denoise_params;
+
+/* the defaults (profiles/denoise_defaults.md) */
+void tinsel_hip_denoise_params_init(tinsel_hip_denoise_params* p);
+
+/* host arrays; returns when out_host (W*H*4 floats) is written */
+int tinsel_hip_denoise(tinsel_hip* r, const float* beauty_host, const float* planes_host,
+                       unsigned features, int width, int height,
+                       const tinsel_hip_denoise_params* p, float* out_host);
+/* device arrays, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for, as tinsel_hip_render_features_device:
+ * the call waits for nothing the renderer has in flight -- with beauty_dev == NULL the caller orders it behind the render, as with
+ * tinsel_hip_present_async -- and a later denoise call on another stream waits, on the device, for this one.  Every input is read by
+ * the first kernel and out_dev written by the last: out_dev may be one of the inputs. */
+int tinsel_hip_denoise_device(tinsel_hip* r, const float* beauty_dev, const float* planes_dev,
+                              unsigned features, int width, int height,
+                              const tinsel_hip_denoise_params* p, float* out_dev, void* stream);
+
+/* tinsel_hip_present_async with the source made an argument: any accumulator-form image of the init size on the device, 16-byte
+ * aligned -- the denoised image, a reduced frame.  tinsel_hip_present_async is this call with the renderer's accumulator;
+ * tinsel_hip_present_device_ptr names the result of either. */
+int tinsel_hip_present_image_device(tinsel_hip* r, const float* image_dev,
+                                    const tinsel_options* options, int nlm_width,
+                                    float nlm_falloff, void* stream);
+
 /* Ray queries on the resident scene: the reference's Trace() (render.cpp:17-62) for rays the caller chooses.
  * TINSEL_QUERY_CLOSEST: the smallest t > 0 over the primitives the ray reaches (an exact tie: the one the scene BVH walk meets first),
  * that primitive's index and its normal turned towards the ray, FaceForward(n, -direction); a miss is t = FLT_MAX, primitive = -1,

@@ -169,6 +169,18 @@ FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 1, 2, 4
 FEATURE_NAMES = ("albedo", "normal", "depth")
 
 
+class DenoiseParams(C.Structure):
+    """tinsel_hip_denoise_params: the search window's radius (1 .. 8), AverageFilter's radius (0 .. 4), the coefficients of the colour,
+    albedo, normal and depth terms of the exponent (finite, >= 0), demodulation by the albedo (0 | 1; needs the albedo plane) and the
+    floor of its divisor (> 0).  tinsel_amd.denoise_params(**fields) starts from the library's defaults."""
+    _fields_ = [("radius", C.c_int32), ("patch_radius", C.c_int32),
+                ("k_color", C.c_float), ("k_albedo", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float),
+                ("demodulate", C.c_int32), ("albedo_floor", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KernelTimeV1(C.Structure):
     """tinsel_kernel_time as libraries built before round 4 wrote it (no busy_ms): renderer.HipRenderer.kernel_times"""
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_float)]
@@ -261,5 +273,5 @@ PIPELINE_WAVEFRONT, PIPELINE_MEGAKERNEL, PIPELINE_WAVEFRONT_SPLIT, PIPELINE_AUTO
 assert C.sizeof(Transform) == 32 and C.sizeof(BVHNode) == 32 and C.sizeof(Camera) == 40 and C.sizeof(Node64) == 64
 assert C.sizeof(Material) == 128 and C.sizeof(MeshGeometry) == 64 and C.sizeof(Primitive) == 272
 assert C.sizeof(Filter) == 16 and C.sizeof(Options) == 48 and C.sizeof(PackHeader) == 256
-assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32 and C.sizeof(DenoiseParams) == 32
 assert Primitive.geo.offset == 72 and Primitive.material.offset == 136 and Primitive.light_samples.offset == 264

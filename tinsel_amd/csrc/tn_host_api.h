@@ -248,17 +248,66 @@ int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)
     return 0;
 }
 
-// The display stage of the reference's frame loop (main.cpp:258-282) on the device accumulator.
-int tinsel_hip_present_async(tinsel_hip* r, const tinsel_options* options, int nlm_width, float nlm_falloff, void* stream)
+// The feature-guided denoise stage (tn_denoise.h, tn_host_denoise.h): a joint non-local-means filter on linear radiance.  Own buffers:
+// nothing of the renderer's frame state is written, no statistics, no class in tinsel_hip_kernel_times.
+void tinsel_hip_denoise_params_init(tinsel_hip_denoise_params* p)
 {
-    if (!r || !r->accum || !options || nlm_width < 0)
-        return fail("present: bad arguments (Init and Render first)");
+    if (p)
+        *p = denoise_defaults();
+}
+
+int tinsel_hip_denoise_device(tinsel_hip* r, const float* beauty_dev, const float* planes_dev, unsigned features, int width, int height,
+                              const tinsel_hip_denoise_params* p, float* out_dev, void* stream)
+{
+    const char* const who = "denoise_device";
+    if (denoise_args(r, planes_dev, features, width, height, p, out_dev, who))
+        return -1;
+    if ((((uintptr_t)beauty_dev | (uintptr_t)planes_dev | (uintptr_t)out_dev) & 15u) != 0)
+        return fail(std::string(who) + ": the arrays must be 16-byte aligned");
+    if (!beauty_dev && denoise_own_beauty(r, width, height, who))
+        return -1;
     HIP_TRY(hipSetDevice(r->device));
-    hipStream_t st = (hipStream_t)stream;
+    return denoise_enqueue(r, beauty_dev ? (const float4*)beauty_dev : r->accum, (const float4*)planes_dev, features, width, height, p, (float4*)out_dev,
+                           (hipStream_t)stream);
+}
+
+int tinsel_hip_denoise(tinsel_hip* r, const float* beauty_host, const float* planes_host, unsigned features, int width, int height,
+                       const tinsel_hip_denoise_params* p, float* out_host)
+{
+    const char* const who = "denoise";
+    if (denoise_args(r, planes_host, features, width, height, p, out_host, who))
+        return -1;
+    if (!beauty_host && denoise_own_beauty(r, width, height, who))
+        return -1;
+    HIP_TRY(hipSetDevice(r->device));
+    const size_t image = sizeof(float4)*(size_t)width*height;
+    const size_t planes = image*(size_t)__builtin_popcount(features);
+    // [beauty][planes] on the device; the accumulator is read where it is
+    if (query_buffer(r->denoiseIn, image + planes) || query_buffer(r->denoiseOut, image))
+        return -1;
+    unsigned char* const in = r->denoiseIn.get();
+    if (beauty_host)
+        HIP_TRY(hipMemcpy(in, beauty_host, image, hipMemcpyHostToDevice));
+    else
+        HIP_TRY(hipDeviceSynchronize());        // (as tinsel_hip_read_accum: whatever still adds to the accumulator)
+    if (planes)
+        HIP_TRY(hipMemcpy(in + image, planes_host, planes, hipMemcpyHostToDevice));
+    if (denoise_enqueue(r, beauty_host ? (const float4*)in : r->accum, (const float4*)(in + image), features, width, height, p, (float4*)r->denoiseOut.get(),
+                        nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_host, r->denoiseOut.get(), image, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The display stage of the reference's frame loop (main.cpp:258-282) on an accumulator-form image of the init size.
+static int present_enqueue(tinsel_hip* r, const float4* source, const tinsel_options* options, int nlm_width, float nlm_falloff, hipStream_t st)
+{
+    HIP_TRY(hipSetDevice(r->device));
     const size_t n = (size_t)r->width*r->height;
     if (options->mode != TINSEL_MODE_PATHTRACE)
     {
-        r->presented = r->accum;        // main.cpp:258: the other modes present the raw pixels
+        r->presented = source;          // main.cpp:258: the other modes present the raw pixels
         return 0;
     }
     if (r->display[0].count() != n)
@@ -275,7 +324,7 @@ int tinsel_hip_present_async(tinsel_hip* r, const tinsel_options* options, int n
 
     {
         ScopedTimer t(r, KN_PRESENT, st);
-        hipLaunchKernelGGL(k_present, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, r->accum, display[0], (int)n,
+        hipLaunchKernelGGL(k_present, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, source, display[0], (int)n,
                            options->exposure, options->limit);
     }
     r->presented = display[0];
@@ -295,6 +344,25 @@ int tinsel_hip_present_async(tinsel_hip* r, const tinsel_options* options, int n
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int tinsel_hip_present_image_device(tinsel_hip* r, const float* image_dev, const tinsel_options* options, int nlm_width, float nlm_falloff, void* stream)
+{
+    if (!r || !image_dev || !options || nlm_width < 0)
+        return fail("present_image_device: bad arguments");
+    if (((uintptr_t)image_dev & 15u) != 0)
+        return fail("present_image_device: the image must be 16-byte aligned");
+    if (!r->accum)
+        return fail("present_image_device: no tinsel_hip_init (the image has the init size)");
+    return present_enqueue(r, (const float4*)image_dev, options, nlm_width, nlm_falloff, (hipStream_t)stream);
+}
+
+// ... on the device accumulator
+int tinsel_hip_present_async(tinsel_hip* r, const tinsel_options* options, int nlm_width, float nlm_falloff, void* stream)
+{
+    if (!r || !r->accum || !options || nlm_width < 0)
+        return fail("present: bad arguments (Init and Render first)");
+    return tinsel_hip_present_image_device(r, (const float*)r->accum, options, nlm_width, nlm_falloff, stream);
 }
 
 int tinsel_hip_present(tinsel_hip* r, const tinsel_options* options, int nlm_width, float nlm_falloff, float* out_rgba)

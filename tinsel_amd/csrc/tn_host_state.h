@@ -181,6 +181,14 @@ struct tinsel_hip
     Event featFence;
     hipStream_t featFenceStream = nullptr;
     bool featFencePending = false;
+    // denoise stage (tinsel_hip_denoise*, tn_host_denoise.h): [0] the filter's colour input U, [1] its patch means, [2] (albedo, depth),
+    // [3] the mean normal -- sized to the largest frame denoised -- the host entries' inputs (beauty, planes) and output on the device, and
+    // the event behind the last call's last launch, which a call on another stream waits for before it writes them
+    DevBuf<float4> denoise[4];
+    DevBuf<unsigned char> denoiseIn, denoiseOut;
+    Event denoiseFence;
+    hipStream_t denoiseFenceStream = nullptr;
+    bool denoiseFencePending = false;
 
     size_t lastBatchSlots = 0;          // paths of the last batch (tinsel_hip_read_batch_radiance)
     int lastPipeline = TINSEL_PIPELINE_WAVEFRONT;   // of the last batch (queue_counts)

@@ -5,7 +5,7 @@
                                   [-complexity=rays|nodes|tris|prims] [-firsthit=buffers.npz]
                                   [-irradiance=bake.npz] [-irradiance_spp=N]
                                   [-probes=probes.npz -probes_at=positions.npy] [-probes_spp=N] [-probes_order=0|1|2]
-                                  [-features=features.npz] [-features_spp=N]
+                                  [-features=features.npz] [-features_spp=N] [-denoise[=RADIUS]]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -51,6 +51,10 @@ the render's filter exactly as the image is.  The file holds the raw planes `alb
 float32: weighted sum xyz, weight sum w) and tinsel_amd.feature_images of them: `albedo` [H, W, 3], `normal` [H, W, 3] (unit length),
 `depth`, `depth_variance`, `coverage` [H, W], and `passes`.  Refused with batch mode, -resume (its passes are not [0, N)), -complexity,
 -firsthit, -irradiance and -probes, which render no image.
+-denoise[=RADIUS] does a normal render, then takes the features of its passes [0, spp), denoises the accumulator with the library's
+defaults (HipRenderer.denoise: the feature-guided filter on linear radiance; RADIUS 1 .. 8 replaces the default search radius), runs the
+display stage on the denoised image (HipRenderer.present_image) and writes that to -out (a .pfm gets the denoised linear radiance).
+Refused with what -features is refused with.
 
 No CPU fallback: without a GPU and the HIP library this exits with the library's error.
 """
@@ -62,7 +66,7 @@ import numpy as np
 
 from . import abi
 from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
-from .renderer import Scene, create_gpu_renderer, feature_images, gather_points
+from .renderer import Scene, create_gpu_renderer, denoise_params, feature_images, gather_points
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
 
@@ -72,8 +76,11 @@ def parse_args(argv):
         raise SystemExit(__doc__)
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
-           "over": {}}
+           "denoise": None, "over": {}}
     for a in argv[1:-1]:
+        if a == "-denoise":
+            cfg["denoise"] = 0          # the default radius
+            continue
         if not a.startswith("-") or "=" not in a:
             raise SystemExit("unrecognised argument %r\n%s" % (a, __doc__))
         k, v = a[1:].split("=", 1)
@@ -88,6 +95,10 @@ def parse_args(argv):
                 cfg["nlm_falloff"] = float(parts[1])
         elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features"):
             cfg[k] = v
+        elif k == "denoise":
+            cfg[k] = int(v)
+            if not 1 <= cfg[k] <= 8:
+                raise SystemExit("-denoise=%s: want a radius 1 .. 8" % v)
         elif k == "features_spp":
             cfg[k] = int(v)
             if cfg[k] < 1:
@@ -243,6 +254,17 @@ def features(r, cam, opt, cfg):
     print("wrote %s: %dx%d, %d passes in %.3fms, coverage %.4f" % (cfg["features"], opt.width, opt.height, n, ms, float(images["coverage"].mean())))
 
 
+def denoise(r, cam, opt, cfg, samples):
+    """-denoise: the features of the render's own passes, the denoise stage on the accumulator, the display stage on its result;
+    returns (presented image, denoised linear image)"""
+    ts = time.perf_counter()
+    params = denoise_params(radius=cfg["denoise"]) if cfg["denoise"] else denoise_params()
+    linear = r.denoise(r.features(cam, opt, 0, samples), params)
+    image = r.present_image(linear, opt, cfg["nlm"], cfg["nlm_falloff"])
+    print("denoise: radius %d, features of %d passes (%.4fms)" % (params.radius, samples, (time.perf_counter() - ts)*1000.0), flush=True)
+    return image, linear
+
+
 def main(argv=None):
     cfg = parse_args(sys.argv if argv is None else argv)
     if cfg["features_spp"] and not cfg["features"]:
@@ -250,6 +272,10 @@ def main(argv=None):
     if cfg["features"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                             cfg["probes_at"]):
         raise SystemExit("-features writes the guide buffers of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
+                         "-firsthit, -irradiance or -probes")
+    if cfg["denoise"] is not None and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                                       cfg["probes_at"]):
+        raise SystemExit("-denoise filters a normal render with the guide buffers of its passes [0, N): no batch mode, no -resume, -complexity, "
                          "-firsthit, -irradiance or -probes")
     if cfg["complexity"] and ("%" in cfg["file"] or cfg["save"] or cfg["resume"]):
         raise SystemExit("-complexity renders one cost map: no batch mode, -save or -resume")
@@ -308,11 +334,14 @@ def main(argv=None):
 
     if cfg["features"]:
         features(r, cam, opt, cfg)
+    linear = None
+    if cfg["denoise"] is not None:
+        image, linear = denoise(r, cam, opt, cfg, samples)
     if cfg["save"]:
         np.savez(cfg["save"], accum=r.read_accum(), samples=np.int64(samples))
     if cfg["out"]:
         if cfg["out"].endswith(".pfm"):
-            a = r.read_accum()
+            a = r.read_accum() if linear is None else linear
             with np.errstate(all="ignore"):
                 write_pfm(cfg["out"], a[..., :3]/a[..., 3:4])
         else:

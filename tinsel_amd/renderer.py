@@ -102,6 +102,12 @@ def load_library():
     if hasattr(L, "tinsel_hip_render_features"):       # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_render_features.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
         L.tinsel_hip_render_features_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
+    if hasattr(L, "tinsel_hip_denoise"):               # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_denoise_params_init.restype = None
+        L.tinsel_hip_denoise_params_init.argtypes = [C.POINTER(abi.DenoiseParams)]
+        L.tinsel_hip_denoise.argtypes = [vp, vp, vp, C.c_uint, ci, ci, C.POINTER(abi.DenoiseParams), vp]
+        L.tinsel_hip_denoise_device.argtypes = [vp, vp, vp, C.c_uint, ci, ci, C.POINTER(abi.DenoiseParams), vp, vp]
+        L.tinsel_hip_present_image_device.argtypes = [vp, vp, C.POINTER(abi.Options), ci, C.c_float, vp]
     L.tinsel_hip_kernel_times.argtypes = [vp, C.POINTER(abi.KernelTime), ci]
     L.tinsel_hip_enable_kernel_timing.argtypes = [vp, ci]
     L.tinsel_hip_set_batch_paths.argtypes = [vp, C.c_ulonglong]
@@ -184,6 +190,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_gather_radiance", "tinsel_hip_gather_radiance_device",
     "tinsel_hip_gather_sh", "tinsel_hip_gather_sh_device",
     "tinsel_hip_render_features", "tinsel_hip_render_features_device",
+    "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
 
 
@@ -328,6 +335,23 @@ def feature_images(planes):
         out["depth_variance"] = np.where(a[..., 2] != 0.0, ratio(a[..., 1], a[..., 2]) - mean*mean, 0.0)
         out["coverage"] = ratio(a[..., 2], a[..., 3])
     return out
+
+
+def denoise_params(**fields):
+    """tinsel_hip_denoise_params: the library's defaults (tinsel_hip_denoise_params_init) with `fields` over them -- radius, patch_radius,
+    k_color, k_albedo, k_normal, k_depth, demodulate, albedo_floor"""
+    p = abi.DenoiseParams()
+    load_library().tinsel_hip_denoise_params_init(C.byref(p))
+    names = [k for k, _ in abi.DenoiseParams._fields_]
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError("tinsel_hip_denoise_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _is_tensor(a):
+    return a is not None and not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
 
 
 def _check(rc, what):
@@ -674,6 +698,102 @@ class HipRenderer:
             _check(self._L.tinsel_hip_render_features(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), mask,
                                                       out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_features")
         return {n: out[k] for k, n in enumerate(names)}
+
+    def _image_tensor(self, who, t, shape):
+        import torch
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("%s: a contiguous float32 tensor %s on the GPU is expected" % (who, shape))
+        if t.device.index != self.device:
+            raise ValueError("%s: the tensor is on %s, the renderer on device %d" % (who, t.device, self.device))
+        return t
+
+    def denoise(self, planes=None, params=None, beauty=None, out=None):
+        """The feature-guided denoise stage (tinsel_hip_denoise*): a joint non-local-means filter on linear radiance.  `beauty`: an
+        accumulator-form image [H, W, 4] (xyz the sum, w the weight), None = this renderer's own accumulator; `planes`: what features()
+        returns -- a dict name -> [H, W, 4] -- or None for no guides; `params`: denoise_params(...), None = the defaults.  Returns the
+        denoised radiance [H, W, 4] with w = 1, which present_image takes.  numpy arrays go through the host entry and numpy comes back;
+        where beauty, a plane or `out` is a torch tensor on this renderer's device everything given must be one, the device entry runs on
+        torch's current stream, not waited for, and a tensor comes back (`out` when given).  Leaves the accumulator, pass index, statistics
+        and tuning as they were."""
+        params = params if params is not None else denoise_params()
+        planes = dict(planes) if planes else {}
+        mask, names = feature_mask(tuple(planes))
+        given = [beauty, out] + [planes[n] for n in names]
+        on_device = any(_is_tensor(a) for a in given)
+        if beauty is not None:
+            H, W = int(beauty.shape[0]), int(beauty.shape[1])
+        elif names:
+            H, W = int(planes[names[0]].shape[0]), int(planes[names[0]].shape[1])
+        else:
+            H, W = self.height, self.width
+        shape = (H, W, 4)
+        if on_device:
+            import torch
+            if any(a is not None and not _is_tensor(a) for a in given):
+                raise ValueError("denoise: beauty, planes and out are either all numpy arrays or all tensors on the GPU")
+            dev = next(a for a in given if a is not None).device
+            stack = None
+            if names:
+                for n in names:
+                    self._image_tensor("denoise", planes[n], shape)
+                # (the planes of one features() tensor are neighbours already: no copy)
+                first = planes[names[0]]
+                step = H*W*4*4
+                if all(planes[n].data_ptr() == first.data_ptr() + k*step for k, n in enumerate(names)):
+                    stack = first
+                else:
+                    stack = torch.stack([planes[n] for n in names])
+            if beauty is not None:
+                self._image_tensor("denoise", beauty, shape)
+            out = self._image_tensor("denoise", out, shape) if out is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+            _check(self._L.tinsel_hip_denoise_device(self._h, beauty.data_ptr() if beauty is not None else None,
+                                                     stack.data_ptr() if stack is not None else None, mask, W, H, C.byref(params), out.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "tinsel_hip_denoise_device")
+            return out
+        stack = None
+        if names:
+            stack = np.ascontiguousarray(np.stack([np.asarray(planes[n], np.float32) for n in names]))
+            if stack.shape != (len(names),) + shape:
+                raise ValueError("denoise: every plane is an array %s" % (shape,))
+        if beauty is not None:
+            beauty = np.ascontiguousarray(beauty, np.float32)
+            if beauty.shape != shape:
+                raise ValueError("denoise: the beauty is an array [H, W, 4]")
+        if out is None:
+            out = np.empty(shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("denoise: a C-contiguous float32 array %s is expected" % (shape,))
+        _check(self._L.tinsel_hip_denoise(self._h, _host_ptr(beauty) if beauty is not None else None, _host_ptr(stack) if stack is not None else None,
+                                          mask, W, H, C.byref(params), out.ctypes.data_as(C.c_void_p)), "tinsel_hip_denoise")
+        return out
+
+    def present_image(self, image, options, nlm_width=0, nlm_falloff=200.0):
+        """The display stage (present) on `image` in place of the accumulator (tinsel_hip_present_image_device): any accumulator-form
+        image [H, W, 4] of the init size -- what denoise() returns, a reduced frame.  A torch tensor on this renderer's device is read
+        where it is, on torch's current stream, and the presented image comes back as a tensor; a numpy array is uploaded first and
+        numpy comes back."""
+        shape = (self.height, self.width, 4)
+        import torch
+        host = not _is_tensor(image)
+        if host:
+            a = np.ascontiguousarray(image, np.float32)
+            if a.shape != shape:
+                raise ValueError("present_image: an array %s is expected" % (shape,))
+            image = torch.from_numpy(a).to("cuda:%d" % self.device)
+        self._image_tensor("present_image", image, shape)
+        stream = torch.cuda.current_stream(image.device)
+        _check(self._L.tinsel_hip_present_image_device(self._h, image.data_ptr(), C.byref(options), int(nlm_width), float(nlm_falloff), stream.cuda_stream),
+               "tinsel_hip_present_image_device")
+        ptr = self._L.tinsel_hip_present_device_ptr(self._h)
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+        # (the HIP runtime the library is linked against, found through the library's own handle: device to device, on the same stream)
+        copy = self._L.hipMemcpyAsync
+        copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        if copy(out.data_ptr(), ptr, out.numel()*4, 3, stream.cuda_stream) != 0:
+            raise TinselHipError("present_image: the copy of the presented image failed")
+        if host:
+            return out.cpu().numpy()
+        return out
 
     def _records(self, who, arg, width, record=None):
         """The record array of trace_rays / radiance / gather: (n, its address, torch device, stream).  A contiguous (n, width) torch tensor
