@@ -47,7 +47,9 @@ def test_fast_arm_is_inside_the_bar_at_256_spp(name, W, H, depth):
 
 
 def test_fast_arm_follows_the_exact_paths_until_a_branch_flips():
-    """Same seeds, same RNG streams: most paths agree to rounding; the rest took another branch.  Reports both."""
+    """Same seeds, same RNG streams: most paths agree to rounding; the rest took another branch.  Reports both.  (A coarse net on one
+    scene and the fused kernel: tests/test_gpu_fast_accuracy.py holds the off-track share per scene, depth and pipeline to the reference's
+    own two builds, and the off-track paths to an unbiased sum.)"""
     scene, cam, opt, g = _load("cornell")
     opt.width = opt.height = 256
     _, rad_e = _render(scene, cam, opt, 1, abi.ARITH_EXACT, want_radiance=True)

@@ -439,6 +439,8 @@ def test_kernel_times_list_the_calls_kernels(which):
 
 @pytest.mark.parametrize("name", ["cornell", "ajax_standin_96"])
 def test_the_fast_arm_answers_with_the_same_shapes(name):
+    """shapes, finiteness and weights only; the planes' values against the exact arm's, pixel by pixel off the edges:
+    tests/test_gpu_fast_accuracy.py::test_feature_planes_follow_the_exact_arm_off_the_edges"""
     scene, r, cam, opt = _open(name)
     try:
         exact = r.features(cam, opt, 0, PASSES)

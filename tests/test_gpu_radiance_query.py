@@ -386,6 +386,8 @@ def test_the_query_follows_the_roulette_setting(ref):
 
 
 def test_the_fast_arithmetic_arm_answers():
+    """that the entry answers under the tolerance arm at all; WHAT it answers -- per path, by depth, under every pipeline -- is held in
+    tests/test_gpu_fast_accuracy.py (test_paths_stay_on_track_and_the_rest_is_unbiased, test_paths_under_every_pipeline)"""
     starts, want, depth = _case("cornell")
     scene, r = _renderer("cornell")
     try:
