@@ -459,6 +459,62 @@ int tinsel_hip_render_features(tinsel_hip* r, const tinsel_camera* camera, const
 int tinsel_hip_render_features_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
                                       uint32_t pass_begin, int passes, unsigned features, float* out_dev, void* stream);
 
+/* ID mattes: which primitive is under each pixel, and by how much -- per pixel a ranked list of (id, filter-weight sum) pairs (Cryptomatte's
+ * data model) on the beauty's own samples, so that a matte is anti-aliased, motion-blurred and filtered EXACTLY as the image is.  An id does
+ * not average, so the feature planes above cannot carry it.
+ * Samples and ids: every path of the passes [pass_begin, pass_begin + passes), with the camera sample and the shutter time of
+ * tinsel_hip_render_features (generator Random(i + j*W + pass_seed(pass_begin + s)), draws x, y, t).  The id of a path is the primitive
+ * index of its one closest-hit Trace() at that time -- what tinsel_ray_hit carries for that ray --, or TINSEL_ID_MISS where the path left
+ * the scene.
+ * Visiting order: a pixel visits its candidates in AddSample's order (render.cpp:401-445): passes ascending, within a pass the generating
+ * pixels in raster order (rows ascending, columns ascending inside a row) -- the order in which the accumulator adds.
+ * Which candidates count: the path generated at a pixel has the raster position (x + i, y + j) = (rx, ry) and the footprint
+ * [max(0, int(rx - fw)), min(int(rx + fw), W - 1)] x [max(0, int(ry - fw)), min(int(ry + fw), H - 1)], fw = options->filter.width, as
+ * AddSample's.  It is a candidate of every pixel (px, py) of its footprint, with the weight w = 1 for the box filter and, for the Gaussian,
+ * w = G(px - rx)*G(py - ry) (one fp32 multiply), G(x) = max(0, expf(-falloff*x*x) - offset) as Filter::Gaussian.  A candidate with w == +0
+ * is skipped entirely: it claims no slot and adds nothing (adding +0 to a non-negative sum changes no bit).
+ * What a counting candidate (w > 0) does to its pixel, in this order:
+ *   1. total += w;
+ *   2. if one of the pixel's `slots` slots holds the id already: that slot's weight += w;
+ *   3. otherwise, if a slot is empty: the FIRST empty slot takes (id, w);
+ *   4. otherwise residual += w.
+ * Every pixel starts from empty slots, residual = total = 0; all sums are fp32, one rounding per add.  Slots keep first-seen order from
+ * batch to batch within a call, so the result does not depend on the batch cut.
+ * Ranking: at the end of the call each pixel's slots are sorted: weight descending, ties by ascending id as int32, empty slots last.  An
+ * occupied slot always has weight > 0; an empty one has id TINSEL_ID_EMPTY and weight 0.
+ * Output, planar (pixel (i, j) of plane p at [(p*H + j)*W + i]): out_ids[slots][H][W] int32, the ranked ids; out_weights[slots + 2][H][W]
+ * float, planes 0 .. slots - 1 the ranked slots' weights, plane `slots` the residual, plane `slots + 1` the total.  Both are overwritten.
+ * The total plane is bit for bit the w of the accumulator, and of any tinsel_hip_render_features plane, for the same passes and filter.
+ * A matte of a set of ids is (the sum of the weights of the slots that hold one of them)/total.
+ * Everything else as tinsel_hip_render_features: the seeds are a table of the call's own and the renderer's generator is only read; the
+ * accumulator, the pass index, the pass seeds, the statistics, the tuning, look-ahead and the path buffers are left as they were, and
+ * tinsel_hip_stats does not count the call; tinsel_hip_set_arithmetic's arm traces the rays (the lists are built the same way in both);
+ * options->clamp, max_depth, exposure and limit are ignored.  Under a shard a rank processes the samples of the pixels it owns wherever
+ * their footprints reach: the result is that rank's PARTIAL list, and merging the ranks' lists (sum the weights of equal ids, re-rank, add
+ * what no longer fits to the residual, sum residuals and totals: tinsel_amd.merge_id_mattes) is the caller's job.
+ * Kernels: "k_ids" (once per batch) is timed under the name "k_features" in tinsel_hip_kernel_times -- the name table does not grow --,
+ * and the gather ("k_ids_accumulate", once per batch) and the ranking ("k_ids_rank", once per call) have no class there, like the denoise
+ * stage's kernels: time the device entry with events on the stream it is given (profiles/id_mattes_measure.py).
+ * Needs options->mode == TINSEL_MODE_PATHTRACE and the frame size of the last tinsel_hip_init.  Returns -1 and writes nothing for: a null
+ * argument, passes < 1, slots outside 1 .. TINSEL_ID_MAX_SLOTS, another mode, a frame size that does not match (or no tinsel_hip_init), a
+ * moved primitive without tinsel_hip_rebuild_scene, and for the device entry a pointer that is not 16-byte aligned (or buffers that overlap).
+ * Memory, kept until tinsel_hip_destroy: 4 bytes per path slot of a batch -- a batch holds whole passes, max(1, floor(batch_paths / slots
+ * per pass)) of them and no more than `passes`, a pass W*H slots (a shard: its own tiles); 1024 x 1024, 16 passes: 64 MB --, 72 bytes per
+ * pixel for the lists between batches (eight ids, eight weights, residual, total, whatever `slots` is), 4 bytes per pass for the seeds,
+ * and for the host entry (8*slots + 8)*W*H bytes of ranked planes. */
+#define TINSEL_ID_MISS   (-1)   /* the path left the scene */
+#define TINSEL_ID_EMPTY  (-2)   /* an unused slot */
+#define TINSEL_ID_MAX_SLOTS 8
+
+/* host arrays of slots*W*H int32 and (slots + 2)*W*H floats; returns when they are written */
+int tinsel_hip_render_id_mattes(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                uint32_t pass_begin, int passes, int slots, int32_t* out_ids_host, float* out_weights_host);
+/* device arrays, each 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for, under the stream and fence rules
+ * of tinsel_hip_render_features_device: the call waits for nothing the renderer has in flight and nothing of the renderer's waits for it;
+ * a later ID-matte call on another stream waits, on the device, for this one. */
+int tinsel_hip_render_id_mattes_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                       uint32_t pass_begin, int passes, int slots, int32_t* out_ids_dev, float* out_weights_dev, void* stream);
+
 /* Feature-guided denoise: a joint non-local-means filter on LINEAR radiance, in front of the display stage, guided by the planes above.
  * With features == 0 and demodulate == 0 it is NonLocalMeansFilter (nlm.cpp:35-77) on the normalised colour, bit for bit, falloff =
  * k_color and AverageFilter's radius = patch_radius; the guide terms add to the exponent.  Everything is fp32, one rounding per

@@ -167,6 +167,8 @@ GATHER_SH_MAX_ORDER = 2       # tinsel_hip_gather_sh*: bands 0 .. order, (order 
 # tinsel_hip_render_features*: the planes a call asks for, by bit; the output holds them in ascending bit order (FEATURE_NAMES' order)
 FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 1, 2, 4
 FEATURE_NAMES = ("albedo", "normal", "depth")
+# tinsel_hip_render_id_mattes*: the id of a path that left the scene, the id of an unused slot, the most slots a call takes
+ID_MISS, ID_EMPTY, ID_MAX_SLOTS = -1, -2, 8
 
 
 class DenoiseParams(C.Structure):

@@ -72,6 +72,7 @@ int fail(const std::string& msg)
 #include "tn_host_radiance.h"     // radiance queries: the split / paired pipeline on paths the caller starts
 #include "tn_host_gather.h"       // gather queries: many paths per surface point, drawn and reduced on the device
 #include "tn_host_features.h"     // feature buffers: albedo, normal and depth of the camera's own paths through the accumulate stage
+#include "tn_host_ids.h"          // ID mattes: the hit primitive of the camera's own paths, gathered into ranked per-pixel (id, weight) lists
 #include "tn_host_denoise.h"      // the feature-guided denoise stage on linear radiance
 #include "tn_host_lookahead.h"    // the one-pass-per-call pattern
 #include "tn_host_bvh_build.h"    // device BVH build

@@ -236,6 +236,41 @@ int tinsel_hip_render_features(tinsel_hip* r, const tinsel_camera* camera, const
     return 0;
 }
 
+// ID mattes (tn_ids.h, tn_host_ids.h): per pixel a ranked list of (primitive id, filter-weight sum) pairs over the camera's own paths.  Own
+// seeds, own buffers, as the feature buffers; the gather and the ranking have no class in tinsel_hip_kernel_times.
+int tinsel_hip_render_id_mattes_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                       int slots, int32_t* out_ids_dev, float* out_weights_dev, void* stream)
+{
+    const char* const who = "render_id_mattes_device";
+    if (ids_args(r, camera, options, passes, slots, out_ids_dev, out_weights_dev, who))
+        return -1;
+    const size_t npix = (size_t)r->width*r->height;
+    if (query_arrays({ { out_ids_dev, npix*sizeof(int32_t)*(size_t)slots }, { out_weights_dev, npix*sizeof(float)*(size_t)(slots + 2) } }, who) ||
+        query_ready(r, who))
+        return -1;
+    return ids_enqueue(r, camera, options, pass_begin, passes, slots, out_ids_dev, out_weights_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_id_mattes(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                int slots, int32_t* out_ids_host, float* out_weights_host)
+{
+    const char* const who = "render_id_mattes";
+    if (ids_args(r, camera, options, passes, slots, out_ids_host, out_weights_host, who) || query_ready(r, who))
+        return -1;
+    const size_t npix = (size_t)r->width*r->height;
+    const size_t idBytes = npix*sizeof(int32_t)*(size_t)slots, weightBytes = npix*sizeof(float)*(size_t)(slots + 2);
+    if (query_buffer(r->idsOut, idBytes + weightBytes))
+        return -1;
+    int* const ids = (int*)r->idsOut.get();
+    float* const weights = (float*)(r->idsOut.get() + idBytes);
+    if (ids_enqueue(r, camera, options, pass_begin, passes, slots, ids, weights, nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_ids_host, ids, idBytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_weights_host, weights, weightBytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -181,6 +181,15 @@ struct tinsel_hip
     Event featFence;
     hipStream_t featFenceStream = nullptr;
     bool featFencePending = false;
+    // ID mattes (tinsel_hip_render_id_mattes*, tn_host_ids.h): k_ids' records of a batch (4 bytes per path slot), the per-pixel lists the
+    // batches of a call carry (72 bytes per pixel: eight ids, eight weights, residual, total -- planar), the call's own seed table, the host
+    // entry's ranked planes -- grown on demand, freed with the renderer -- and the event behind the last call's last launch, which a call on
+    // another stream waits for before it writes them
+    DevBuf<unsigned char> idsRec, idsState, idsOut;
+    DevBuf<uint32_t> idsSeeds;
+    Event idsFence;
+    hipStream_t idsFenceStream = nullptr;
+    bool idsFencePending = false;
     // denoise stage (tinsel_hip_denoise*, tn_host_denoise.h): [0] the filter's colour input U, [1] its patch means, [2] (albedo, depth),
     // [3] the mean normal -- sized to the largest frame denoised -- the host entries' inputs (beauty, planes) and output on the device, and
     // the event behind the last call's last launch, which a call on another stream waits for before it writes them

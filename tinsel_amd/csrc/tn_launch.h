@@ -92,7 +92,9 @@ namespace tn {
     X(PK_GATHER_REDUCE,         kBlock, 0, GATHER_REDUCE, k_gather_reduce)                                          \
     X(PK_GATHER_SH_REDUCE,      kShWave, 0, GATHER_SH_REDUCE, k_gather_sh_reduce)                                   \
     X(PK_FEATURES_LDS,          kBlock, 0, FEATURES, k_features<true>)                                              \
-    X(PK_FEATURES,              kBlock, 0, FEATURES, k_features<false>)
+    X(PK_FEATURES,              kBlock, 0, FEATURES, k_features<false>)                                             \
+    X(PK_IDS_LDS,               kBlock, 0, FEATURES, k_ids<true>)                                                   \
+    X(PK_IDS,                   kBlock, 0, FEATURES, k_ids<false>)
 
 enum PathKernel : int
 {
@@ -128,7 +130,7 @@ struct LaunchArgs
     RadianceJob radiance;           // k_generate_rays
     GatherJob gather;               // k_generate_gather, k_gather_reduce, k_gather_sh_reduce
     int shOrder;                    // k_gather_sh_reduce: the highest band
-    FeatureJob features;            // k_features
+    FeatureJob features;            // k_features, k_ids
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins

@@ -6,6 +6,7 @@
                                   [-irradiance=bake.npz] [-irradiance_spp=N]
                                   [-probes=probes.npz -probes_at=positions.npy] [-probes_spp=N] [-probes_order=0|1|2]
                                   [-features=features.npz] [-features_spp=N] [-denoise[=RADIUS]]
+                                  [-mattes=FILE.npz] [-mattes_spp=N] [-mattes_slots=K]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -51,6 +52,11 @@ the render's filter exactly as the image is.  The file holds the raw planes `alb
 float32: weighted sum xyz, weight sum w) and tinsel_amd.feature_images of them: `albedo` [H, W, 3], `normal` [H, W, 3] (unit length),
 `depth`, `depth_variance`, `coverage` [H, W], and `passes`.  Refused with batch mode, -resume (its passes are not [0, N)), -complexity,
 -firsthit, -irradiance and -probes, which render no image.
+-mattes=FILE.npz writes, beside a normal render, the ID mattes a compositor takes (HipRenderer.id_mattes): per pixel the ranked list of
+(primitive id, filter-weight sum) pairs of the render's own camera samples of passes [0, -mattes_spp) (default min(spp, 16), as
+-features_spp), -mattes_slots pairs per pixel (default 6, 1 .. 8), filtered with the render's filter exactly as the image is.  The file
+holds `ids` [K, H, W] int32 (-1: the sample left the scene, -2: an unused slot), `weights` [K, H, W], `residual` [H, W], `total` [H, W]
+and `passes`; tinsel_amd.matte turns them into the coverage of a set of primitives.  Refused with what -features is refused with.
 -denoise[=RADIUS] does a normal render, then takes the features of its passes [0, spp), denoises the accumulator with the library's
 defaults (HipRenderer.denoise: the feature-guided filter on linear radiance; RADIUS 1 .. 8 replaces the default search radius), runs the
 display stage on the denoised image (HipRenderer.present_image) and writes that to -out (a .pfm gets the denoised linear radiance).
@@ -76,6 +82,7 @@ def parse_args(argv):
         raise SystemExit(__doc__)
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
+           "mattes": None, "mattes_spp": None, "mattes_slots": None,
            "denoise": None, "over": {}}
     for a in argv[1:-1]:
         if a == "-denoise":
@@ -93,7 +100,7 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes"):
             cfg[k] = v
         elif k == "denoise":
             cfg[k] = int(v)
@@ -103,6 +110,14 @@ def parse_args(argv):
             cfg[k] = int(v)
             if cfg[k] < 1:
                 raise SystemExit("-features_spp=%s: want 1 or more" % v)
+        elif k == "mattes_spp":
+            cfg[k] = int(v)
+            if cfg[k] < 1:
+                raise SystemExit("-mattes_spp=%s: want 1 or more" % v)
+        elif k == "mattes_slots":
+            cfg[k] = int(v)
+            if not 1 <= cfg[k] <= abi.ID_MAX_SLOTS:
+                raise SystemExit("-mattes_slots=%s: want 1 .. %d" % (v, abi.ID_MAX_SLOTS))
         elif k == "probes_spp":
             cfg[k] = int(v)
             if not 1 <= cfg[k] <= 65536:
@@ -254,6 +269,18 @@ def features(r, cam, opt, cfg):
     print("wrote %s: %dx%d, %d passes in %.3fms, coverage %.4f" % (cfg["features"], opt.width, opt.height, n, ms, float(images["coverage"].mean())))
 
 
+def mattes(r, cam, opt, cfg):
+    """-mattes: the ranked id lists of the render's own samples of passes [0, N) (tinsel_hip_render_id_mattes)"""
+    n = cfg["mattes_spp"] if cfg["mattes_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
+    slots = cfg["mattes_slots"] if cfg["mattes_slots"] else 6
+    ts = time.perf_counter()
+    m = r.id_mattes(cam, opt, 0, n, slots)
+    ms = (time.perf_counter() - ts)*1000.0
+    np.savez(cfg["mattes"], passes=np.int64(n), **m)
+    print("wrote %s: %dx%d, %d passes, %d slots in %.3fms, %d pixels with a residual" % (cfg["mattes"], opt.width, opt.height, n, slots, ms,
+                                                                                       int((m["residual"] > 0).sum())))
+
+
 def denoise(r, cam, opt, cfg, samples):
     """-denoise: the features of the render's own passes, the denoise stage on the accumulator, the display stage on its result;
     returns (presented image, denoised linear image)"""
@@ -272,6 +299,12 @@ def main(argv=None):
     if cfg["features"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                             cfg["probes_at"]):
         raise SystemExit("-features writes the guide buffers of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
+                         "-firsthit, -irradiance or -probes")
+    if (cfg["mattes_spp"] or cfg["mattes_slots"]) and not cfg["mattes"]:
+        raise SystemExit("-mattes_spp and -mattes_slots go with -mattes=OUT.npz")
+    if cfg["mattes"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                          cfg["probes_at"]):
+        raise SystemExit("-mattes writes the ID mattes of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
                          "-firsthit, -irradiance or -probes")
     if cfg["denoise"] is not None and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                                        cfg["probes_at"]):
@@ -334,6 +367,8 @@ def main(argv=None):
 
     if cfg["features"]:
         features(r, cam, opt, cfg)
+    if cfg["mattes"]:
+        mattes(r, cam, opt, cfg)
     linear = None
     if cfg["denoise"] is not None:
         image, linear = denoise(r, cam, opt, cfg, samples)

@@ -102,6 +102,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_render_features"):       # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_render_features.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
         L.tinsel_hip_render_features_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
+    if hasattr(L, "tinsel_hip_render_id_mattes"):      # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_id_mattes.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, vp]
+        L.tinsel_hip_render_id_mattes_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, vp, vp]
     if hasattr(L, "tinsel_hip_denoise"):               # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_denoise_params_init.restype = None
         L.tinsel_hip_denoise_params_init.argtypes = [C.POINTER(abi.DenoiseParams)]
@@ -190,8 +193,68 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_gather_radiance", "tinsel_hip_gather_radiance_device",
     "tinsel_hip_gather_sh", "tinsel_hip_gather_sh_device",
     "tinsel_hip_render_features", "tinsel_hip_render_features_device",
+    "tinsel_hip_render_id_mattes", "tinsel_hip_render_id_mattes_device",
     "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
+
+
+def rank_id_lists(ids, weights):
+    """The ranking of tinsel_hip_render_id_mattes on ids / weights [K, H, W]: per pixel weight descending, ties by ascending id as int32,
+    empty slots (abi.ID_EMPTY, weight 0) last.  Returns new arrays."""
+    ids, weights = np.asarray(ids, np.int32), np.asarray(weights, np.float32)
+    empty = ids == abi.ID_EMPTY
+    # np.lexsort: the last key is the primary one
+    order = np.lexsort((ids, -weights.astype(np.float64), empty), axis=0)
+    return np.take_along_axis(ids, order, 0), np.take_along_axis(weights, order, 0)
+
+
+def matte(result, ids):
+    """The coverage of the primitives `ids` (an id or several; abi.ID_MISS is the background) from what HipRenderer.id_mattes returned:
+    float32 [H, W], the sum of the weights of the slots that hold one of the ids divided by the total, 0 where the total is 0 -- the plane a
+    compositor multiplies by, anti-aliased, motion-blurred and filtered as the beauty is."""
+    wanted = np.isin(np.asarray(result["ids"]), np.atleast_1d(np.asarray(ids, np.int64)))
+    wanted &= np.asarray(result["ids"]) != abi.ID_EMPTY
+    total = np.asarray(result["total"], np.float32)
+    s = np.where(wanted, np.asarray(result["weights"], np.float32), np.float32(0)).sum(axis=0, dtype=np.float32)
+    out = np.zeros(total.shape, np.float32)
+    np.divide(s, total, out=out, where=total != 0)
+    return out
+
+
+def merge_id_mattes(results, slots):
+    """The ranks' partial lists (HipRenderer.id_mattes under set_shard, in rank order) as one list of `slots` slots per pixel: the weights
+    of equal ids are summed in rank order (float32), the combined list is ranked by the library's rule, what does not fit in `slots` is
+    added to the residual, and the ranks' residuals and totals are summed.  Returns the dict id_mattes returns."""
+    results = list(results)
+    slots = int(slots)
+    if not results or not 1 <= slots:
+        raise ValueError("merge_id_mattes: at least one result and one slot")
+    H, W = np.asarray(results[0]["total"]).shape
+    cap = sum(np.asarray(r["ids"]).shape[0] for r in results)
+    ids = np.full((cap, H, W), abi.ID_EMPTY, np.int32)
+    weights = np.zeros((cap, H, W), np.float32)
+    residual, total = np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)
+    for r in results:
+        rid, rw = np.asarray(r["ids"], np.int32), np.asarray(r["weights"], np.float32)
+        for k in range(rid.shape[0]):
+            c, w = rid[k], rw[k]
+            todo = c != abi.ID_EMPTY
+            held = (ids == c[None]) & todo[None]
+            weights = np.where(held, weights + w[None], weights)
+            todo &= ~held.any(axis=0)
+            first = np.argmax(ids == abi.ID_EMPTY, axis=0)              # (cap slots: an empty one is always left for a new id)
+            jj, ii = np.nonzero(todo)
+            ids[first[jj, ii], jj, ii] = c[jj, ii]
+            weights[first[jj, ii], jj, ii] = w[jj, ii]
+        residual = residual + np.asarray(r["residual"], np.float32)
+        total = total + np.asarray(r["total"], np.float32)
+    ids, weights = rank_id_lists(ids, weights)
+    for k in range(slots, cap):
+        residual = residual + weights[k]
+    if cap < slots:
+        ids = np.concatenate([ids, np.full((slots - cap, H, W), abi.ID_EMPTY, np.int32)])
+        weights = np.concatenate([weights, np.zeros((slots - cap, H, W), np.float32)])
+    return {"ids": np.ascontiguousarray(ids[:slots]), "weights": np.ascontiguousarray(weights[:slots]), "residual": residual, "total": total}
 
 
 def rng_state(seed, skip=0):
@@ -698,6 +761,43 @@ class HipRenderer:
             _check(self._L.tinsel_hip_render_features(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), mask,
                                                       out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_features")
         return {n: out[k] for k, n in enumerate(names)}
+
+    def id_mattes(self, camera, options, pass_begin=0, passes=1, slots=6, out=None):
+        """ID mattes (tinsel_hip_render_id_mattes*): per pixel the ranked list of (primitive id, filter-weight sum) pairs of the beauty's own
+        camera samples of passes [pass_begin, pass_begin + passes), filtered with options.filter exactly as the beauty is -- a dict
+        {"ids": int32 [slots, H, W] (abi.ID_MISS: the path left the scene, abi.ID_EMPTY: an unused slot), "weights": float32 [slots, H, W],
+        "residual": [H, W] (what found no slot), "total": [H, W] (the accumulator's w)}, weight descending.  tinsel_amd.matte turns it into
+        the coverage of a set of ids.  `out`: a pair of contiguous torch tensors on this renderer's device, int32 [slots, H, W] and float32
+        [slots + 2, H, W], takes the device entry on torch's current stream, not waited for, and the dict holds views of them; a pair of
+        numpy arrays of those shapes is filled by the host entry.  Needs init() at the options' frame size; leaves the accumulator, pass
+        index, pass seeds, statistics and tuning as they were.  Under a shard the result is this rank's partial list (merge_id_mattes)."""
+        slots = int(slots)
+        H, W = int(options.height), int(options.width)
+        ishape, wshape = (max(slots, 0), H, W), (max(slots, 0) + 2, H, W)
+        if out is not None and len(out) != 2:
+            raise ValueError("id_mattes: out is a pair (ids, weights)")
+        if out is not None and hasattr(out[0], "data_ptr") and not isinstance(out[0], np.ndarray):
+            import torch
+            ids, weights = out
+            for t, dtype, shape in ((ids, torch.int32, ishape), (weights, torch.float32, wshape)):
+                if not hasattr(t, "data_ptr") or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                    raise ValueError("id_mattes: contiguous tensors int32 %s and float32 %s on the GPU are expected" % (ishape, wshape))
+                if t.device.index != self.device:
+                    raise ValueError("id_mattes: the tensor is on %s, the renderer on device %d" % (t.device, self.device))
+            _check(self._L.tinsel_hip_render_id_mattes_device(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), slots,
+                                                              ids.data_ptr(), weights.data_ptr(), torch.cuda.current_stream(ids.device).cuda_stream),
+                   "tinsel_hip_render_id_mattes_device")
+        else:
+            if out is None:
+                ids, weights = np.zeros(ishape, np.int32), np.zeros(wshape, np.float32)
+            else:
+                ids, weights = out
+                for a, dtype, shape in ((ids, np.int32, ishape), (weights, np.float32, wshape)):
+                    if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape or not a.flags.c_contiguous:
+                        raise ValueError("id_mattes: C-contiguous arrays int32 %s and float32 %s are expected" % (ishape, wshape))
+            _check(self._L.tinsel_hip_render_id_mattes(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), slots,
+                                                       ids.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_id_mattes")
+        return {"ids": ids, "weights": weights[:slots], "residual": weights[slots], "total": weights[slots + 1]}
 
     def _image_tensor(self, who, t, shape):
         import torch
