@@ -752,6 +752,10 @@ int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2);
 /* The SCENE's share of those bits (media, probe, motion, mesh walk, sphere, transmission) from a scene description alone: no device, no
  * renderer.  What a renderer created from `scene` with the default tuning reports until a primitive is moved or a mesh tree rebuilt. */
 unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene);
+/* 1 where a path of `scene` carries the SLIM state in the fused kernel's compiled instances (kinds 2 and 3), else 0: no media, probe, motion,
+ * mesh walk or transmission among the bits above, and every material's `subsurface` is +0.0f BY ITS BITS (-0.0f is not).  A scene that is
+ * not slim runs the general kernel (kind 0) whatever its bits; the bits themselves do not know about subsurface.  No device, no renderer. */
+int tinsel_hip_scene_slim(const tinsel_scene_desc* scene);
 enum { TINSEL_BOUNCE_MEDIA = 1, TINSEL_BOUNCE_PROBE = 2, TINSEL_BOUNCE_MOTION = 4, TINSEL_BOUNCE_MESH_WALK = 8, TINSEL_BOUNCE_SPHERE = 16,
        TINSEL_BOUNCE_TRANSMISSION = 32, TINSEL_BOUNCE_POOLS = 64, TINSEL_BOUNCE_SHARE = 128, TINSEL_BOUNCE_SORT = 256, TINSEL_BOUNCE_ROULETTE = 512 };
 

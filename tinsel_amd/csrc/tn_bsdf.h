@@ -138,13 +138,18 @@ TN_D V3 sample_ggx_reflection(const Mat& mat, V3 U, V3 Vt, V3 N, V3 view, float 
 // arithmetic; the three lobe samplers are each written ONCE after the lobe choice so that lanes
 // which picked the same lobe through different branches (GGX via the Fresnel branch or via the
 // 50/50 BRDF branch) execute it together.
+// SLIM (k_bounce's FIT instances, tn_fused.h): mat.transmission and mat.subsurface are +0.0f, so neither `randf() < transmission` nor
+// `randf() < subsurface` holds for any draw -- the draws stay (the stream's order), the refraction and the inside lobe go, and `type`
+// is kReflected whatever the lobe.
+template <bool SLIM = false>
 TN_D void bsdf_sample(const Mat& mat, float etaI, float etaO, V3 U, V3 Vt, V3 N, V3 view, V3& light, float& pdf, int& type, Rng& rng)
 {
     enum { kLobeGgx, kLobeCosine, kLobeInside };
     int lobe = kLobeGgx;
     float r1, r2;
 
-    if (rng.randf() < mat.transmission)
+    const float uTransmission = rng.randf();
+    if (!SLIM && uTransmission < mat.transmission)
     {
         float F = fresnel_dielectric(dot(N, view), etaI, etaO);
         if (rng.randf() < F)
@@ -173,7 +178,10 @@ TN_D void bsdf_sample(const Mat& mat, float etaI, float etaO, V3 U, V3 Vt, V3 N,
         r1 = rng.randf();
         r2 = rng.randf();
         if (rng.randf() < 0.5f)
-            lobe = (rng.randf() < mat.subsurface) ? kLobeInside : kLobeCosine;      // disney.h:243-261
+        {
+            const float uSubsurface = rng.randf();
+            lobe = (!SLIM && uSubsurface < mat.subsurface) ? kLobeInside : kLobeCosine;     // disney.h:243-261
+        }
         else
             lobe = kLobeGgx;                                                         // disney.h:264-287
     }
@@ -182,7 +190,7 @@ TN_D void bsdf_sample(const Mat& mat, float etaI, float etaO, V3 U, V3 Vt, V3 N,
     // theta = k2Pi*u2 (maths.h:1307), inside-hemisphere phi = k2Pi*Randf (maths.h:1297, after its z draw)
     float zIn = 0.0f;
     float angle;
-    if (lobe == kLobeInside)
+    if (!SLIM && lobe == kLobeInside)
     {
         zIn = rng.randf();
         angle = k2Pi*rng.randf();
@@ -199,7 +207,7 @@ TN_D void bsdf_sample(const Mat& mat, float etaI, float etaO, V3 U, V3 Vt, V3 N,
         light = sample_ggx_reflection(mat, U, Vt, N, view, sn, cs, r2);
         type = kReflected;
     }
-    else if (lobe == kLobeCosine)
+    else if (SLIM || lobe == kLobeCosine)
     {
         // CosineSampleHemisphere (maths.h:1304-1310, 1319-1325)
         const float r = sqrtf_cr(r1);

@@ -20,11 +20,30 @@ constexpr int kPoolFields = 25;         // (28 until round 5: the medium's absor
 constexpr int kPoolWordsPerWave = kPoolFields*kWave;
 constexpr int kPoolWords = kPoolWordsPerWave*(kBlock/kWave);     // per workgroup: 25 KB
 
+// The FIT instances' entries are SLIM like their path state (load_state_slim, tn_path_state.h): 21 fields, without the time, rayEta, rayType
+// and the medium, which are constants there.  The host sizes a workgroup's pools by kPoolWords for every instance (plan_bounce, trace_fused:
+// what is resident on a CU does not depend on the instance), so a slim pool is the front of its wave's 25 rows.
+constexpr int kPoolFieldsSlim = 21;
+
+template <int FIELDS>
 TN_D void pool_store(uint32_t* pool, uint32_t e, const PathRegs& p, uint32_t slot, int prim, float t, V3 n)
 {
+    static_assert(FIELDS == kPoolFields || FIELDS == kPoolFieldsSlim, "a pool entry is whole or slim");
     uint32_t* q = pool + e;
     q[0*kWave] = __float_as_uint(p.o.x); q[1*kWave] = __float_as_uint(p.o.y); q[2*kWave] = __float_as_uint(p.o.z);
     q[3*kWave] = __float_as_uint(p.d.x); q[4*kWave] = __float_as_uint(p.d.y); q[5*kWave] = __float_as_uint(p.d.z);
+    if constexpr (FIELDS == kPoolFieldsSlim)
+    {
+        q[6*kWave] = __float_as_uint(p.thr.x); q[7*kWave] = __float_as_uint(p.thr.y); q[8*kWave] = __float_as_uint(p.thr.z);
+        q[9*kWave] = __float_as_uint(p.rad.x); q[10*kWave] = __float_as_uint(p.rad.y); q[11*kWave] = __float_as_uint(p.rad.z);
+        q[12*kWave] = p.rng.s1; q[13*kWave] = p.rng.s2;
+        q[14*kWave] = __float_as_uint(p.bsdfPdf);
+        q[15*kWave] = slot;
+        q[16*kWave] = (uint32_t)prim;
+        q[17*kWave] = __float_as_uint(t);
+        q[18*kWave] = __float_as_uint(n.x); q[19*kWave] = __float_as_uint(n.y); q[20*kWave] = __float_as_uint(n.z);
+        return;
+    }
     q[6*kWave] = __float_as_uint(p.time);
     q[7*kWave] = __float_as_uint(p.thr.x); q[8*kWave] = __float_as_uint(p.thr.y); q[9*kWave] = __float_as_uint(p.thr.z);
     q[10*kWave] = __float_as_uint(p.rad.x); q[11*kWave] = __float_as_uint(p.rad.y); q[12*kWave] = __float_as_uint(p.rad.z);
@@ -39,11 +58,27 @@ TN_D void pool_store(uint32_t* pool, uint32_t e, const PathRegs& p, uint32_t slo
     q[24*kWave] = (uint32_t)p.medium;
 }
 
+// (a slim entry: the four constants are set like load_state_slim sets them; a whole one: the caller looks the medium's absorption up)
+template <int FIELDS>
 TN_D void pool_load(const uint32_t* pool, uint32_t e, PathRegs& p, uint32_t& slot, int& prim, float& t, V3& n)
 {
+    static_assert(FIELDS == kPoolFields || FIELDS == kPoolFieldsSlim, "a pool entry is whole or slim");
     const uint32_t* q = pool + e;
     p.o = V3(__uint_as_float(q[0*kWave]), __uint_as_float(q[1*kWave]), __uint_as_float(q[2*kWave]));
     p.d = V3(__uint_as_float(q[3*kWave]), __uint_as_float(q[4*kWave]), __uint_as_float(q[5*kWave]));
+    if constexpr (FIELDS == kPoolFieldsSlim)
+    {
+        p.thr = V3(__uint_as_float(q[6*kWave]), __uint_as_float(q[7*kWave]), __uint_as_float(q[8*kWave]));
+        p.rad = V3(__uint_as_float(q[9*kWave]), __uint_as_float(q[10*kWave]), __uint_as_float(q[11*kWave]));
+        p.rng.s1 = q[12*kWave]; p.rng.s2 = q[13*kWave];
+        p.bsdfPdf = __uint_as_float(q[14*kWave]);
+        slot = q[15*kWave];
+        prim = (int)q[16*kWave];
+        t = __uint_as_float(q[17*kWave]);
+        n = V3(__uint_as_float(q[18*kWave]), __uint_as_float(q[19*kWave]), __uint_as_float(q[20*kWave]));
+        path_slim_constants(p);
+        return;
+    }
     p.time = __uint_as_float(q[6*kWave]);
     p.thr = V3(__uint_as_float(q[7*kWave]), __uint_as_float(q[8*kWave]), __uint_as_float(q[9*kWave]));
     p.rad = V3(__uint_as_float(q[10*kWave]), __uint_as_float(q[11*kWave]), __uint_as_float(q[12*kWave]));
@@ -99,7 +134,9 @@ struct BounceKernargs { DevScene scIn; SplitState ss; QueueCtl q; int bounceBegi
 // k_bounce's instances by KIND.  0: the general kernel, every BounceFeature (tn_scene.h) tested at run time; 1: the same with the detail
 // counters.  2 and up: FIT instances, compiled for the feature set below -- a test of a feature outside the set is decided at compile time,
 // so its code and the scalars it keeps live through the round loop are not in the instance.  The host launches a FIT instance only for a
-// scene and a plan whose features lie inside its set (plan_batch, tn_host_batch.h); everything else runs the general kernel.  Which sets:
+// scene and a plan whose features lie inside its set (plan_batch, tn_host_batch.h) AND whose materials have no subsurface (scene_slim): a FIT
+// instance carries the slim path state (tn_path_state.h) and has neither the inside lobe nor a medium to hand over.  Everything else runs
+// the general kernel.  Which sets:
 // what the fused scenes of BASELINE.md ask for -- the closed static box (cornell) and the open scene with deferred mesh walks, pools,
 // sharing and sorted queues (veach).  (A third one, the closed box with shared regions for small batches of cornell, did not clearly beat
 // the general kernel at 256^2 and is not compiled: profiles/r09_bounce_fit_icache.md.)
@@ -115,6 +152,11 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
 {
     constexpr bool COUNT = KIND == kBounceCount;
     constexpr uint32_t FEAT = bounce_kind_features(KIND);
+    // every FIT instance is SLIM: its scenes have no subsurface either (plan_batch: scene_slim), so a path carries the slim state and
+    // pool entries, and what hangs off rayEta, the medium and rayType is decided here
+    constexpr bool SLIM = KIND >= kBounceFitClosed;
+    constexpr int POOL = SLIM ? kPoolFieldsSlim : kPoolFields;
+    static_assert(!SLIM || !(FEAT & (kFeatMedia | kFeatMotion | kFeatTransmission | kFeatProbe)), "the slim state has no word for these");
     typedef SceneT<LDS, false, DEFER ? 1 : 0, false, FEAT> SC;
     const DevScene& scIn = ka.scIn;
     const SplitState& ss = ka.ss;
@@ -141,6 +183,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
     auto mat_at = [&](int prim) {
         Mat m = load_mat(sc.mats, prim);
         if constexpr (!(FEAT & kFeatTransmission)) m.transmission = 0.0f;       // (the value every material of its scenes holds)
+        if constexpr (SLIM) m.subsurface = 0.0f;                                // (the same: +0.0f by its bits, scene_slim)
         return m;
     };
     // the path state's pointers (ten of them and the radiance array: 22 SGPRs that a round needs for a dozen instructions at its start
@@ -154,6 +197,16 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
     };
     auto ssBuf = [&](int buf) {
         StatePtr sp = state_args();
+        if constexpr (SLIM)
+        {
+            // the slim state's eight pointers are SplitState's first 64 bytes: one scalar load of both buffers' and a select each, where the
+            // indexed form is four loads at a computed offset (and a spilled SGPR more in the deferred instance: profiles/r18_slim_state.md)
+            static_assert(offsetof(SplitState, rad) + sizeof(float4*[2]) - offsetof(SplitState, rayO) == 64, "rayO, rayD, thr, rad: contiguous");
+            float4* const o0 = sp->rayO[0]; float4* const o1 = sp->rayO[1]; float4* const d0 = sp->rayD[0]; float4* const d1 = sp->rayD[1];
+            float4* const t0 = sp->thr[0]; float4* const t1 = sp->thr[1]; float4* const r0 = sp->rad[0]; float4* const r1 = sp->rad[1];
+            StateBuf b = { buf ? o1 : o0, buf ? d1 : d0, buf ? t1 : t0, buf ? r1 : r0, nullptr };
+            return b;
+        }
         StateBuf b = { sp->rayO[buf], sp->rayD[buf], sp->thr[buf], sp->rad[buf], sp->rngId[buf] };
         return b;
     };
@@ -287,7 +340,10 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     }
                     else
                         pos = region_pos(base, rLen, nFront, j);
-                    load_state(sc, TN_SS_BUF(cur), pos, p, slot, hasMedia);
+                    if constexpr (SLIM)
+                        load_state_slim(TN_SS_BUF(cur), pos, p, slot);
+                    else
+                        load_state(sc, TN_SS_BUF(cur), pos, p, slot, hasMedia);
                     have = true;
                 }
             }
@@ -318,8 +374,9 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     const uint32_t rank = bits_below(~live);
                     if (!have && rank < take)
                     {
-                        pool_load(pool, poolCount - 1u - rank, p, slot, prim, t, n3);
-                        p.absorption = medium_absorption(sc, p.medium, hasMedia);
+                        pool_load<POOL>(pool, poolCount - 1u - rank, p, slot, prim, t, n3);
+                        if constexpr (!SLIM)
+                            p.absorption = medium_absorption(sc, p.medium, hasMedia);
                         have = true;
                     }
                     poolCount -= take;
@@ -327,7 +384,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                 else
                 {
                     if (have)
-                        pool_store(pool, poolCount + bits_below(live), p, slot, prim, t, n3);
+                        pool_store<POOL>(pool, poolCount + bits_below(live), p, slot, prim, t, n3);
                     poolCount += nLive;
                     have = false;           // waits in the pool
                 }
@@ -340,7 +397,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     const V3 n = n3;
                     const Mat mat = mat_at(prim);
                     HitCtx h;
-                    on_hit_begin(p, mat, t, n, bounce, h, prim);
+                    on_hit_begin<SLIM>(p, mat, t, n, bounce, h, prim);
 
                     if (sc.totalLightSamples > 0)
                     {
@@ -368,10 +425,10 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                             // the BSDF terms only for the samples that arrive; the 28-register material record is re-read here
                             // instead of living across the shadow trace
                             if (light < 0)
-                                return (hp < 0) ? nee_contrib_probe(mat_at(prim), h, g.wi, skyColor, skyPdf) : V3(0.0f);
+                                return (hp < 0) ? nee_contrib_probe<SLIM>(mat_at(prim), h, g.wi, skyColor, skyPdf) : V3(0.0f);
                             if (!nee_light_reached(g, hp, ts))
                                 return V3(0.0f);
-                            return nee_contrib_light(sc, mat_at(prim), h, g.wi, g.nl, light, hp, ts);
+                            return nee_contrib_light<SLIM>(sc, mat_at(prim), h, g.wi, g.nl, light, hp, ts);
                         });
                         p.rad = p.rad + thrAtNee*sum;
                     }
@@ -382,7 +439,7 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     {
                         // the material is read again rather than kept in 28 registers across the shadow traces
                         const Mat matAgain = mat_at(prim);
-                        alive = (bsdf_step(p, matAgain, h) == kContinue);
+                        alive = (bsdf_step<SLIM>(p, matAgain, h) == kContinue);
                         if ((FEAT & kFeatRoulette) && alive && fp.rrStart > 0 && bounce + 1 >= fp.rrStart)
                             alive = roulette_survives(p);
                     }
@@ -397,7 +454,12 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
             }
             const uint32_t np = out.push(alive, front);
             if (alive)
-                store_state(TN_SS_BUF(nxt), np, p, slot);
+            {
+                if constexpr (SLIM)
+                    store_state_slim(TN_SS_BUF(nxt), np, p, slot);
+                else
+                    store_state(TN_SS_BUF(nxt), np, p, slot);
+            }
             if (flush)
                 break;
         }

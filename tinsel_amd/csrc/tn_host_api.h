@@ -863,6 +863,16 @@ unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene)
     return f;
 }
 
+int tinsel_hip_scene_slim(const tinsel_scene_desc* scene)
+{
+    if (!scene || !scene->primitives)
+        return 0;
+    bool anySubsurface = false;
+    for (int i = 0; i < scene->num_primitives; ++i)
+        anySubsurface = anySubsurface || !is_plus_zero(scene->primitives[i].material.subsurface);
+    return scene_slim(tinsel_hip_scene_features(scene), anySubsurface) ? 1 : 0;
+}
+
 int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2)
 {
     if (!r || !out2)

@@ -480,6 +480,16 @@ uint32_t bounce_features(const tinsel_hip* r, bool pools)
     return f;
 }
 
+// Do the scene's paths carry the SLIM state (load_state_slim, tn_path_state.h)?  What the slim state has no word for -- a medium, a ray
+// time, a transmitted or specular ray type, a probe's MIS -- and what the FIT sets leave out anyway (a walked mesh), among the scene's own
+// bits of `features`; and no subsurface: every material's is +0.0f by its bits (`anySubsurface`).  Every FIT instance is compiled slim, so
+// this is one more condition of theirs (plan_batch); the feature bits themselves do not know about subsurface.  Derived for every
+// render call like they are; tinsel_hip_scene_slim states it from a scene description.
+bool scene_slim(uint32_t features, bool anySubsurface)
+{
+    return !(features & (kFeatMedia | kFeatProbe | kFeatMotion | kFeatMeshWalk | kFeatTransmission)) && !anySubsurface;
+}
+
 // the FIT instance of k_bounce (tn_launch.h) for a scene whose features are `need`, PK_NONE where none is compiled for them
 int fit_bounce(uint32_t need, bool deferMeshes)
 {
@@ -721,9 +731,10 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     if (fused)
     {
         // a FIT instance where one is compiled for what the scene and the plan ask for (the whole scene in LDS, the flat scan, no detail
-        // counters: what every fused BASELINE scene is); tinsel_hip_tuning::bounce_fit = 0: the general kernel (parity tests, A/B)
+        // counters: what every fused BASELINE scene is) and the scene is slim (no subsurface on top of the sets' own conditions: the
+        // instances carry the slim path state); tinsel_hip_tuning::bounce_fit = 0: the general kernel (parity tests, A/B)
         p.bounceFeatures = bounce_features(r, p.pools);
-        if (lds && !count && r->scene.flatScan && r->tune.bounce_fit != 0)
+        if (lds && !count && r->scene.flatScan && r->tune.bounce_fit != 0 && scene_slim(p.bounceFeatures, r->anySubsurface))
         {
             const int alone = fit_bounce(p.bounceFeatures, r->scene.deferMeshes != 0), shared = fit_bounce(p.bounceFeatures | kFeatShare, r->scene.deferMeshes != 0);
             p.bounce = alone != PK_NONE ? alone : p.bounce;

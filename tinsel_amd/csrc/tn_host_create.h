@@ -379,6 +379,7 @@ void SceneBuild::set_scene_flags()
         if (mm.absorption[0] != 0.0f || mm.absorption[1] != 0.0f || mm.absorption[2] != 0.0f)
             sc.hasMedia = 1;
     r->anyTransmission = std::any_of(mats.begin(), mats.end(), [](const Mat128& mm) { return mm.transmission != 0.0f; });
+    r->anySubsurface = std::any_of(mats.begin(), mats.end(), [](const Mat128& mm) { return !is_plus_zero(mm.subsurface); });
     sc.flatScan = flatScan ? 1 : 0;
     {
         int meshPrimCount = 0;

@@ -137,6 +137,15 @@ void set_light_constants(Mat128& m)
     m.clight = (float)m.lightSamples/(float)N;
 }
 
+// +0.0f by its BITS: what k_bounce's FIT instances pin Mat::subsurface to (tn_fused.h mat_at).  -0.0f compares equal but is another operand
+// to kInv2Pi*subsurface*0.5f and 1.0f - subsurface's neighbours, and stays with the general kernel (scene_slim, tn_host_batch.h).
+bool is_plus_zero(float v)
+{
+    uint32_t bits;
+    memcpy(&bits, &v, sizeof(bits));
+    return bits == 0u;
+}
+
 void make_material(const tinsel_primitive& p, Mat128& m)
 {
     const tinsel_material& a = p.material;

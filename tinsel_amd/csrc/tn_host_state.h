@@ -73,6 +73,7 @@ struct tinsel_hip
     int bvhMode = TINSEL_BVH_REFERENCE;
     int rrStart = 0;                    // > 0: Russian roulette from this bounce on (opt-in)
     bool anyTransmission = false;       // a material has a transmission lobe (materials never change after create)
+    bool anySubsurface = false;         // a material's subsurface is not +0.0f by its bits (the same; scene_slim, tn_host_batch.h)
     int lastBounceKind = -1;            // k_bounce's last launch: its kind (tn_fused.h BounceKind) and the features asked of it (tinsel_hip_bounce_plan)
     uint32_t lastBounceFeatures = 0;
     DevPool lbvhTrees;                  // the device-built mesh trees in force (set_mesh_bvh: one generation)

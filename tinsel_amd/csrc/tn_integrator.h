@@ -62,10 +62,18 @@ struct HitCtx
     int outMedium;      // the primitive outAbsorption belongs to (entering: the hit one), or -1 (leaving: 0)
 };
 
+// SLIM paths (k_bounce's FIT instances: load_state_slim, tn_path_state.h) travel with rayEta == 1, rayAbsorption == 0, no medium and a
+// reflected rayType for good: the functions below take SLIM to drop what hangs off those four -- the eta / absorption / medium selects and
+// their six registers of HitCtx across the shadow traces, the Beer-Lambert test, the specular select, bsdf_step's hand-over.  Where a
+// BSDF term still asks for the two etas (the Fresnel corner of bsdf_pdf), they are 1.0f and the material's own ior, read again with it.
+template <bool SLIM> TN_D float hit_eta_i(const HitCtx& h) { return SLIM ? 1.0f : h.etaI; }
+template <bool SLIM> TN_D float hit_eta_o(const HitCtx& h, const Mat& mat) { return SLIM ? mat.ior : h.etaO; }
+
 // render.cpp:255-310.  `bounce` is the loop index i.
+template <bool SLIM = false>
 TN_D void on_hit_begin(PathRegs& p, const Mat& mat, float t, V3 n, int bounce, HitCtx& h, int prim = -1)
 {
-    if (p.eta == 1.0f)
+    if (SLIM || p.eta == 1.0f)
     {
         h.etaO = mat.ior;
         h.outAbsorption = mat.absorption;
@@ -77,11 +85,11 @@ TN_D void on_hit_begin(PathRegs& p, const Mat& mat, float t, V3 n, int bounce, H
         h.outAbsorption = V3(0.0f);
         h.outMedium = -1;
     }
-    h.etaI = p.eta;
+    h.etaI = SLIM ? 1.0f : p.eta;
 
     // pathThroughput *= Exp(-rayAbsorption*t)   (render.cpp:272, maths.h:253)
     // exp(-0*t) == 1 exactly and thr*1 == thr, so the (common) non-absorbing medium skips the three exps
-    if (p.absorption.x != 0.0f || p.absorption.y != 0.0f || p.absorption.z != 0.0f)
+    if (!SLIM && (p.absorption.x != 0.0f || p.absorption.y != 0.0f || p.absorption.z != 0.0f))
     {
         V3 a = (-p.absorption)*t;
         p.thr = p.thr*V3(m_expf(a.x), m_expf(a.y), m_expf(a.z));
@@ -107,7 +115,7 @@ TN_D void on_hit_begin(PathRegs& p, const Mat& mat, float t, V3 n, int bounce, H
             float clight = mat.clight;
             float weight = cbsdf*p.bsdfPdf/(cbsdf*p.bsdfPdf + clight*lightPdf);
 
-            if (p.rayType == kSpecular)
+            if (!SLIM && p.rayType == kSpecular)
                 weight = 1.0f;
 
             p.rad = p.rad + weight*p.thr*mat.emission;
@@ -239,15 +247,17 @@ struct NeeTerms
     float absDot;       // |dot(wi, n)|
 };
 
+template <bool SLIM = false>
 TN_D NeeTerms nee_bsdf_terms(const Mat& surf, const HitCtx& h, V3 wi)
 {
     NeeTerms e;
     e.f = V3(0.0f);
     e.absDot = 0.0f;
-    e.bsdfPdf = bsdf_pdf(surf, h.etaI, h.etaO, h.n, h.wo, wi);
+    const float etaI = hit_eta_i<SLIM>(h), etaO = hit_eta_o<SLIM>(h, surf);
+    e.bsdfPdf = bsdf_pdf(surf, etaI, etaO, h.n, h.wo, wi);
     if (e.bsdfPdf > 0.0f)
     {
-        e.f = bsdf_eval(surf, h.etaI, h.etaO, h.n, h.wo, wi);
+        e.f = bsdf_eval(surf, etaI, etaO, h.n, h.wo, wi);
         e.absDot = absf(dot(wi, h.n));
     }
     return e;
@@ -271,9 +281,10 @@ TN_D V3 nee_combine_light(const DevScene& sc, const NeeTerms& e, float nl, int l
     return L;
 }
 
+template <bool SLIM = false>
 TN_D V3 nee_contrib_light(const DevScene& sc, const Mat& surf, const HitCtx& h, V3 wi, float nl, int light, int hitPrim, float t)
 {
-    return nee_combine_light(sc, nee_bsdf_terms(surf, h, wi), nl, light, hitPrim, t);
+    return nee_combine_light(sc, nee_bsdf_terms<SLIM>(surf, h, wi), nl, light, hitPrim, t);
 }
 
 // render.cpp:107-116: the probe sample and its shadow ray
@@ -289,13 +300,15 @@ TN_D void nee_sample_probe(const DevScene& sc, V3 hitP, V3 hitN, Rng& rng, NeeGe
 }
 
 // render.cpp:118-139 for an unoccluded probe sample
+template <bool SLIM = false>
 TN_D V3 nee_contrib_probe(const Mat& surf, const HitCtx& h, V3 wi, V3 skyColor, float skyPdf)
 {
     V3 L(0.0f);
-    float bsdfPdf = bsdf_pdf(surf, h.etaI, h.etaO, h.n, h.wo, wi);
+    const float etaI = hit_eta_i<SLIM>(h), etaO = hit_eta_o<SLIM>(h, surf);
+    float bsdfPdf = bsdf_pdf(surf, etaI, etaO, h.n, h.wo, wi);
     if (bsdfPdf > 0.0f)
     {
-        V3 f = bsdf_eval(surf, h.etaI, h.etaO, h.n, h.wo, wi);
+        V3 f = bsdf_eval(surf, etaI, etaO, h.n, h.wo, wi);
         int N = int(kProbeSamples + kBsdfSamples);
         float cbsdf = kBsdfSamples/N;
         float csky = float(kProbeSamples)/N;
@@ -347,6 +360,7 @@ TN_D V3 nee_sum(const DevScene& sc, Contrib contrib)
 enum StepResult : int { kContinue = 0, kTerminate = 1 };
 
 // render.cpp:322-363
+template <bool SLIM = false>
 TN_D int bsdf_step(PathRegs& p, const Mat& mat, const HitCtx& h)
 {
     if (mat.lightSamples)
@@ -358,15 +372,17 @@ TN_D int bsdf_step(PathRegs& p, const Mat& mat, const HitCtx& h)
     V3 bsdfDir;
     int bsdfType = kReflected;
     float pdf = 0.0f;
-    bsdf_sample(mat, h.etaI, h.etaO, u, v, h.n, h.wo, bsdfDir, pdf, bsdfType, p.rng);
+    const float etaI = hit_eta_i<SLIM>(h), etaO = hit_eta_o<SLIM>(h, mat);
+    bsdf_sample<SLIM>(mat, etaI, etaO, u, v, h.n, h.wo, bsdfDir, pdf, bsdfType, p.rng);
     p.bsdfPdf = pdf;
 
     if (pdf <= 0.0f)
         return kTerminate;
 
-    V3 f = bsdf_eval(mat, h.etaI, h.etaO, h.n, h.wo, bsdfDir);
+    V3 f = bsdf_eval(mat, etaI, etaO, h.n, h.wo, bsdfDir);
 
-    if (dot(bsdfDir, h.n) <= 0.0f)
+    // (SLIM: a direction below the surface has pdf == 0 -- bsdf_pdf's lerp of +0 subsurface and +0 transmission -- and ended the path above)
+    if (!SLIM && dot(bsdfDir, h.n) <= 0.0f)
     {
         p.eta = h.etaO;
         p.absorption = h.outAbsorption;

@@ -408,4 +408,37 @@ TN_D void store_state(const SplitState& ss, int buf, uint32_t pos, const PathReg
     store_state(state_buf(ss, buf), pos, p, slot);
 }
 
+// The SLIM state of k_bounce's FIT instances (tn_fused.h): their scenes have no media, no motion, no transmission, no probe and no subsurface
+// (plan_batch), so a path's time is never read, and rayEta, rayType and the medium never leave what path_begin gave them -- bsdf_step hands a
+// medium over only for a direction below the surface with pdf > 0, which only the refraction and the inside lobe produce.  Four of the twenty
+// words are constants then: rng and slot move into the freed .w words, and the fifth array (rngId) is neither read nor written.
+//   rayO {o, bsdfPdf}   rayD {d, slot}   thr {thr, rng.s1}   rad {rad, rng.s2}
+// (A batch is one launch of one instance, and nothing but k_bounce reads these arrays: the two layouts never meet.)
+TN_D void path_slim_constants(PathRegs& p)
+{
+    p.time = 0.0f;
+    p.eta = 1.0f;
+    p.absorption = V3(0.0f);
+    p.rayType = kReflected;
+    p.medium = -1;
+}
+
+TN_D void load_state_slim(const StateBuf& sb, uint32_t pos, PathRegs& p, uint32_t& slot)
+{
+    const float4 ro = sb.rayO[pos], rd = sb.rayD[pos], th = sb.thr[pos], ra = sb.rad[pos];
+    p.o = V3(ro.x, ro.y, ro.z); p.bsdfPdf = ro.w;
+    p.d = V3(rd.x, rd.y, rd.z); slot = __float_as_uint(rd.w);
+    p.thr = V3(th.x, th.y, th.z); p.rng.s1 = __float_as_uint(th.w);
+    p.rad = V3(ra.x, ra.y, ra.z); p.rng.s2 = __float_as_uint(ra.w);
+    path_slim_constants(p);
+}
+
+TN_D void store_state_slim(const StateBuf& sb, uint32_t pos, const PathRegs& p, uint32_t slot)
+{
+    sb.rayO[pos] = make_float4(p.o.x, p.o.y, p.o.z, p.bsdfPdf);
+    sb.rayD[pos] = make_float4(p.d.x, p.d.y, p.d.z, __uint_as_float(slot));
+    sb.thr[pos] = make_float4(p.thr.x, p.thr.y, p.thr.z, __uint_as_float(p.rng.s1));
+    sb.rad[pos] = make_float4(p.rad.x, p.rad.y, p.rad.z, __uint_as_float(p.rng.s2));
+}
+
 } // namespace tn

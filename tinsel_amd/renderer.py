@@ -137,6 +137,8 @@ def load_library():
         L.tinsel_hip_bounce_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.tinsel_hip_scene_features.restype = C.c_uint
         L.tinsel_hip_scene_features.argtypes = [C.POINTER(abi.SceneDesc)]
+    if hasattr(L, "tinsel_hip_scene_slim"):           # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_scene_slim.argtypes = [C.POINTER(abi.SceneDesc)]
     if hasattr(L, "tinsel_hip_queue_counts"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_queue_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.tinsel_hip_set_lookahead.argtypes = [vp, ci]
@@ -174,7 +176,7 @@ def load_library():
 
 
 EXPORTED_SYMBOLS = [
-    "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
+    "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_scene_slim", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
     "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_render_cost", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
@@ -457,6 +459,10 @@ class Scene:
     def bounce_features(self):
         """tinsel_hip_scene_features: the abi.BOUNCE_* bits this scene asks of the fused kernel (no device needed)"""
         return int(load_library().tinsel_hip_scene_features(C.byref(self.desc)))
+
+    def bounce_slim(self):
+        """tinsel_hip_scene_slim: do this scene's paths carry the slim state in the fused kernel's compiled instances (no device needed)"""
+        return bool(load_library().tinsel_hip_scene_slim(C.byref(self.desc)))
 
 
 def _bytes_at(ptr, n):
