@@ -515,6 +515,50 @@ int tinsel_hip_render_id_mattes(tinsel_hip* r, const tinsel_camera* camera, cons
 int tinsel_hip_render_id_mattes_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
                                        uint32_t pass_begin, int passes, int slots, int32_t* out_ids_dev, float* out_weights_dev, void* stream);
 
+/* Light groups: the beauty split by which emitter produced it, in ONE trace of the paths -- lights can be re-balanced, tinted or switched
+ * off in comp without another render.  The integrator is linear in emission: every term it adds to a path's radiance is a product with
+ * exactly one emitter's colour -- the primitive whose `emission` is read (a camera ray or a BSDF ray that hits it; the primitive a light
+ * sample's shadow ray ENDS on, which need not be the light that was sampled), or the sky / probe (a ray that leaves the scene, the probe's
+ * light sample) -- and emission never steers a path.  So each term is deposited into the plane of its emitter's group.
+ * Plane g is DEFINED as the accumulator tinsel_hip_render would produce for the passes [pass_begin, pass_begin + passes) on the same scene
+ * with emission = 0 on every primitive i whose group_of_primitive[i] != g and sky horizon = zenith = 0 unless env_group == g: bit for bit
+ * in all four channels wherever that render is finite.  It follows that
+ *   - options->clamp applies to EACH PLANE SEPARATELY (ClampLength is not linear): the planes add up to the beauty, within fp32 rounding,
+ *     only with clamp = FLT_MAX;
+ *   - the weight channel of every plane is the beauty's;
+ *   - a primitive with emission but light_samples == 0 (found by BSDF rays only) has its group like any light.
+ * A PROBE is not masked by the definition (it shapes light sampling and MIS in every plane): its radiance lands in env_group only, the
+ * env_group plane is the render with every emission zeroed, and a light's plane is (the render masked to that group) - (the env_group
+ * plane) up to fp32 rounding.
+ * group_of_primitive: num_primitives int32, the group of each primitive of the scene in force, -1: in no group (its emission reaches no
+ * plane); env_group likewise for the sky / probe.  `out` holds num_groups planes of W*H float4, out[(g*H*W + j*W + i)*4 + c], every plane
+ * from zero: the call overwrites.
+ * The call traces the camera's paths through the split pipeline whatever tinsel_hip_set_pipeline says (k_generate, k_extend, k_lights,
+ * k_shadow and the walk and segment kernels as a render plans them; the shading kernel is k_shade_groups, timed under the name "k_shade" in
+ * tinsel_hip_kernel_times -- the name table does not grow), then one "k_accumulate" per plane and batch.  The seeds, the planes' records
+ * and the statistics the kernels count into are the call's own: the accumulator, the pass index, the renderer's seed table and
+ * tinsel_hip_stats are left as they were, and a render, a light-groups call and the render that follows give the images of the two renders
+ * alone.  The paths themselves live in the renderer's path buffers, used under the fences of the radiance queries.
+ * options->max_depth < 1 gives all-zero planes.  Returns -1 before anything is launched or written for: a null argument, passes < 1,
+ * num_groups outside 1 .. TINSEL_MAX_LIGHT_GROUPS, env_group or a table entry outside -1 .. num_groups - 1, another mode than
+ * TINSEL_MODE_PATHTRACE, a frame size that does not match the last tinsel_hip_init, a moved primitive without tinsel_hip_rebuild_scene, a
+ * sharded renderer (world > 1), TINSEL_ARITH_FAST, and for the device entry an out_dev that is not 16-byte aligned.
+ * Memory, kept until tinsel_hip_destroy: 16 bytes x num_groups per path slot of a batch -- a batch holds whole passes, and those bytes count
+ * against batch_paths beside the 176 bytes of a path's own state: max(1, floor(batch_paths*176/(176 + 16*num_groups) / (W*H))) passes --
+ * plus 4 bytes per pass for the seeds, one byte per primitive for the table, and for the host entry num_groups*W*H*16 bytes of planes. */
+#define TINSEL_MAX_LIGHT_GROUPS 8
+
+/* host array of num_groups*W*H*4 floats; returns when it is written */
+int tinsel_hip_render_light_groups(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                   uint32_t pass_begin, int passes, int num_groups, const int32_t* group_of_primitive, int env_group,
+                                   float* out_host);
+/* device array, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for; the table is a HOST array, read before
+ * the call returns.  The stream waits, on the device, for what the renderer's path buffers still serve and for an earlier light-groups call
+ * on another stream. */
+int tinsel_hip_render_light_groups_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                          uint32_t pass_begin, int passes, int num_groups, const int32_t* group_of_primitive, int env_group,
+                                          float* out_dev, void* stream);
+
 /* Feature-guided denoise: a joint non-local-means filter on LINEAR radiance, in front of the display stage, guided by the planes above.
  * With features == 0 and demodulate == 0 it is NonLocalMeansFilter (nlm.cpp:35-77) on the normalised colour, bit for bit, falloff =
  * k_color and AverageFilter's radius = patch_radius; the guide terms add to the exponent.  Everything is fp32, one rounding per

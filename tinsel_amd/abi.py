@@ -169,6 +169,8 @@ FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_DEPTH = 1, 2, 4
 FEATURE_NAMES = ("albedo", "normal", "depth")
 # tinsel_hip_render_id_mattes*: the id of a path that left the scene, the id of an unused slot, the most slots a call takes
 ID_MISS, ID_EMPTY, ID_MAX_SLOTS = -1, -2, 8
+# tinsel_hip_render_light_groups*: the most planes a call takes
+MAX_LIGHT_GROUPS = 8
 
 
 class DenoiseParams(C.Structure):

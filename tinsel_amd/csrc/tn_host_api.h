@@ -271,6 +271,35 @@ int tinsel_hip_render_id_mattes(tinsel_hip* r, const tinsel_camera* camera, cons
     return 0;
 }
 
+// Light groups (tn_split.h k_shade_groups, tn_host_light_groups.h): the beauty split per emitter group in one trace of the camera's paths
+// through the split pipeline.  Own seeds, own planes, own statistics block: nothing of the renderer's frame state is written; the path
+// buffers are used under the radiance queries' fences, look-ahead work in flight is waited for on the device and kept.
+int tinsel_hip_render_light_groups_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                          int num_groups, const int32_t* group_of_primitive, int env_group, float* out_dev, void* stream)
+{
+    const char* const who = "render_light_groups_device";
+    if (light_groups_args(r, camera, options, passes, num_groups, group_of_primitive, env_group, out_dev, who))
+        return -1;
+    if (query_arrays({ { out_dev, (size_t)r->width*r->height*sizeof(float4)*(size_t)num_groups } }, who) || query_ready(r, who))
+        return -1;
+    return light_groups_enqueue(r, camera, options, pass_begin, passes, num_groups, group_of_primitive, env_group, (float4*)out_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_light_groups(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                   int num_groups, const int32_t* group_of_primitive, int env_group, float* out_host)
+{
+    const char* const who = "render_light_groups";
+    if (light_groups_args(r, camera, options, passes, num_groups, group_of_primitive, env_group, out_host, who) || query_ready(r, who))
+        return -1;
+    const size_t bytes = (size_t)r->width*r->height*sizeof(float4)*(size_t)num_groups;
+    if (query_buffer(r->groupsOut, bytes) ||
+        light_groups_enqueue(r, camera, options, pass_begin, passes, num_groups, group_of_primitive, env_group, (float4*)r->groupsOut.get(), nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_host, r->groupsOut.get(), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -627,12 +627,14 @@ struct BatchPlan
 };
 
 // perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve);
-// generate: the kernel that makes the batch's paths -- the camera's, or a query's (PK_GENERATE_RAYS / _GATHER), which run radiance_pipeline's choice
-BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE)
+// generate: the kernel that makes the batch's paths -- the camera's, or a query's (PK_GENERATE_RAYS / _GATHER), which run radiance_pipeline's choice;
+// groups: a light-groups call's batch (tn_host_light_groups.h) -- the split pipeline whatever the setting, planned as a render's, with
+// k_shade's GROUPS twin as its shading kernel (k_shade_sorted has none)
+BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE, bool groups = false)
 {
     BatchPlan p;
     p.generate = generate;
-    p.pipeline = generate == PK_GENERATE ? resolve_pipeline(r) : radiance_pipeline(r);
+    p.pipeline = groups ? (int)TINSEL_PIPELINE_WAVEFRONT_SPLIT : generate == PK_GENERATE ? resolve_pipeline(r) : radiance_pipeline(r);
     const bool fused = p.pipeline == TINSEL_PIPELINE_WAVEFRONT, split = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_SPLIT,
                paired = p.pipeline == TINSEL_PIPELINE_WAVEFRONT_PAIRED;
 
@@ -705,7 +707,7 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     // pipeline veach 1902 -> 2003, features 1047 -> 1093; it loses in an enclosed scene (glass: no ray leaves, 17.5 -> 19.3 ms) and
     // where k_walk runs (the 524k-triangle config 6.47 -> 6.86 ms) (profiles/r03_g_ab_shade_sorted.txt, r04_e_rates.md).
     // tinsel_hip_tuning::shade_sorted = 0 / 1 forces either arm (A/B, tests).
-    const bool sorted = (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !p.walk)) &&
+    const bool sorted = !groups && (r->tune.shade_sorted >= 0 ? r->tune.shade_sorted != 0 : (!r->sceneEnclosed && !p.walk)) &&
                         (size_t)p.ldsShade + kShadeListWords*sizeof(uint32_t) <= (size_t)r->sharedMemLimit;
     if (sorted)
         p.ldsShade += (uint32_t)(kShadeListWords*sizeof(uint32_t));
@@ -725,6 +727,8 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     p.step = wl == 2 ? PK_STEP_W2_MIXED : wl && mixed ? PK_STEP_W1_MIXED : wl ? PK_STEP_W1 : mixed ? PK_STEP_MIXED : lds ? PK_STEP_LDS : PK_STEP;
     p.lights = lightsDrawn ? PK_NONE : mixed ? PK_LIGHTS_MIXED : lds ? PK_LIGHTS_LDS : PK_LIGHTS;
     p.shade = sorted ? (mixedShade ? PK_SHADE_SORTED_MIXED : lds ? PK_SHADE_SORTED_LDS : PK_SHADE_SORTED) : (mixedShade ? PK_SHADE_MIXED : lds ? PK_SHADE_LDS : PK_SHADE);
+    if (groups)
+        p.shade = p.shade == PK_SHADE_MIXED ? PK_SHADE_GROUPS_MIXED : p.shade == PK_SHADE_LDS ? PK_SHADE_GROUPS_LDS : PK_SHADE_GROUPS;
     // (the detail-counting variants walk the scene BVH: nothing to defer)
     p.bounce = count ? (lds ? PK_BOUNCE_COUNT_LDS : PK_BOUNCE_COUNT) : r->scene.deferMeshes ? (lds ? PK_BOUNCE_LDS_DEFER : PK_BOUNCE_DEFER) : lds ? PK_BOUNCE_LDS : PK_BOUNCE;
     p.bounceShared = p.bounce;
@@ -1380,11 +1384,20 @@ struct CallerPaths
     int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : PK_NONE; }
 };
 
+// What a side call over the camera's own paths replaces of a render's batch (light groups): the seed table k_generate reads, the statistics
+// the kernels count into, the planes k_shade_groups deposits into.  Null / zero: the renderer's own.
+struct TraceOverrides
+{
+    const uint32_t* passSeeds = nullptr;
+    unsigned long long* stats = nullptr;
+    GroupState groups = { nullptr, nullptr, -1, 0u };
+};
+
 // The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
 // are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query -- the split or the paired pipeline
 // behind k_generate_rays / k_generate_gather, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
 int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
-                size_t slots, const CallerPaths* starts = nullptr)
+                size_t slots, const CallerPaths* starts = nullptr, const TraceOverrides* over = nullptr)
 {
     if (starts && (p.generate != starts->generate() || (p.pipeline != TINSEL_PIPELINE_WAVEFRONT_SPLIT && p.pipeline != TINSEL_PIPELINE_WAVEFRONT_PAIRED)))
         return fail("trace_batch: caller-started paths run the split or the paired pipeline");
@@ -1402,6 +1415,12 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
         a.gather = *starts->gather;
     a.fp = fp;
     a.passSeeds = r->passSeeds;
+    if (over)
+    {
+        a.passSeeds = over->passSeeds ? over->passSeeds : a.passSeeds;
+        a.ctl.stats = over->stats ? over->stats : a.ctl.stats;
+        a.groups = over->groups;
+    }
     a.walkRec = p.walk ? L.walkRec : nullptr;
     a.walkPrims = (uint32_t)r->walkPrims.count;
     a.bins = r->binPrims;
@@ -1461,17 +1480,9 @@ int batch_fence_signal(tinsel_hip* r, hipStream_t st)
     return 0;
 }
 
-// The batches of a query: `n` items (a radiance query's paths, a gather query's points) of `pathsEach` paths each, perBatch items at a time in
-// the renderer's path buffers, one batch after the other on st; batch(plan, fp, done, m) enqueues the items [done, done + m) with trace_batch
-// and what follows it.  Ordered against the buffers' other users by events, both ways and without a host wait: st waits for what the renderer
-// has in flight (the default stream's, the look-ahead's, a render or a query on a caller's stream: batch_fence_wait and the fork below),
-// nothing of it is discarded, and the fence recorded behind the last launch is what the next user waits for.
-template <class Batch>
-int trace_caller_batches(tinsel_hip* r, size_t n, size_t perBatch, size_t pathsEach, int generate, int maxDepth, hipStream_t st, Batch batch)
+// st waits, on the device, for what the renderer's own streams hold -- the default one and the look-ahead's (the queryFork events)
+int own_streams_wait(tinsel_hip* r, hipStream_t st)
 {
-    const BatchPlan plan = plan_batch(r, perBatch*pathsEach, 1, /*mayOverlap*/ false, generate);
-    if (ensure_batch(r, plan, maxDepth) || batch_fence_wait(r, st))
-        return -1;
     const hipStream_t own[2] = { nullptr, (hipStream_t)r->workStream };
     for (int k = 0; k < 2; ++k)
     {
@@ -1482,6 +1493,20 @@ int trace_caller_batches(tinsel_hip* r, size_t n, size_t perBatch, size_t pathsE
         HIP_TRY(hipEventRecord(r->queryFork[k], own[k]));
         HIP_TRY(hipStreamWaitEvent(st, r->queryFork[k], 0));
     }
+    return 0;
+}
+
+// The batches of a query: `n` items (a radiance query's paths, a gather query's points) of `pathsEach` paths each, perBatch items at a time in
+// the renderer's path buffers, one batch after the other on st; batch(plan, fp, done, m) enqueues the items [done, done + m) with trace_batch
+// and what follows it.  Ordered against the buffers' other users by events, both ways and without a host wait: st waits for what the renderer
+// has in flight (the default stream's, the look-ahead's, a render or a query on a caller's stream: batch_fence_wait and the fork below),
+// nothing of it is discarded, and the fence recorded behind the last launch is what the next user waits for.
+template <class Batch>
+int trace_caller_batches(tinsel_hip* r, size_t n, size_t perBatch, size_t pathsEach, int generate, int maxDepth, hipStream_t st, Batch batch)
+{
+    const BatchPlan plan = plan_batch(r, perBatch*pathsEach, 1, /*mayOverlap*/ false, generate);
+    if (ensure_batch(r, plan, maxDepth) || batch_fence_wait(r, st) || own_streams_wait(r, st))
+        return -1;
 
     // no pixel, no pass, no shard: the generation count, the depth and the roulette start are all the kernels behind the generation kernel read
     FrameParams fp;

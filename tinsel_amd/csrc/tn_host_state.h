@@ -191,6 +191,18 @@ struct tinsel_hip
     Event idsFence;
     hipStream_t idsFenceStream = nullptr;
     bool idsFencePending = false;
+    // light groups (tinsel_hip_render_light_groups*, tn_host_light_groups.h): the planes' records of a batch (16 bytes per group and path
+    // slot), the call's own seed table, the primitives' groups (one byte each; groupsTableHost: what was uploaded last), the statistics its
+    // kernels count into (never read), the host entry's planes -- grown on demand, freed with the renderer -- and the event behind the last
+    // call's last launch, which a call on another stream waits for before it writes them
+    DevBuf<unsigned char> groupsRec, groupsOut;
+    DevBuf<uint32_t> groupsSeeds;
+    DevBuf<int8_t> groupsTable;
+    std::vector<int8_t> groupsTableHost;
+    DevBuf<unsigned long long> groupsStats;
+    Event groupsFence;
+    hipStream_t groupsFenceStream = nullptr;
+    bool groupsFencePending = false;
     // denoise stage (tinsel_hip_denoise*, tn_host_denoise.h): [0] the filter's colour input U, [1] its patch means, [2] (albedo, depth),
     // [3] the mean normal -- sized to the largest frame denoised -- the host entries' inputs (beauty, planes) and output on the device, and
     // the event behind the last call's last launch, which a call on another stream waits for before it writes them

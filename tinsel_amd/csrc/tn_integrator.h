@@ -417,6 +417,46 @@ TN_D bool roulette_survives(PathRegs& p)
     return true;
 }
 
+// Light groups (k_shade_groups, tn_split.h) deposit each term the integrator adds to totalRadiance into its emitter's plane.  The two
+// functions below restate on_hit_begin's and on_miss's adds -- the same operations on the same operands in the same order: the same bits --
+// for that twin alone; the functions the other kernels compile stay as they are.
+// hit_emission_term: what on_hit_begin adds for the hit primitive's emission (render.cpp:282-309), read AFTER on_hit_begin (Beer-Lambert
+// has been applied to the throughput; nothing else it reads has changed); false where on_hit_begin adds nothing.
+TN_D bool hit_emission_term(const PathRegs& p, const Mat& mat, float t, V3 n, int bounce, V3& term)
+{
+    if (bounce == 0)
+    {
+        term = mat.emission;
+        return true;
+    }
+    float lightArea = mat.area;
+    if (!(lightArea > 0.0f))
+        return false;
+    float lightPdf = (mat.rcpArea*t*t)/clampT(dot(-p.d, n), 1.e-3f, 1.0f);
+    float cbsdf = mat.cbsdf;
+    float clight = mat.clight;
+    float weight = cbsdf*p.bsdfPdf/(cbsdf*p.bsdfPdf + clight*lightPdf);
+    if (p.rayType == kSpecular)
+        weight = 1.0f;
+    term = weight*p.thr*mat.emission;
+    return true;
+}
+
+// miss_term: what on_miss adds (render.cpp:365-383)
+TN_D V3 miss_term(const DevScene& sc, const PathRegs& p, int bounce)
+{
+    float weight = 1.0f;
+    if (sc.probe.valid && bounce > 0 && p.rayType != kSpecular)
+    {
+        float skyPdf = probe_pdf(sc.probe, p.d);
+        int N = int(kProbeSamples + kBsdfSamples);
+        float cbsdf = kBsdfSamples/N;
+        float csky = float(kProbeSamples)/N;
+        weight = cbsdf*p.bsdfPdf/(cbsdf*p.bsdfPdf + csky*skyPdf);
+    }
+    return weight*sky_eval(sc, p.d)*p.thr;
+}
+
 // render.cpp:365-383
 TN_D void on_miss(const DevScene& sc, PathRegs& p, int bounce)
 {

@@ -94,7 +94,10 @@ namespace tn {
     X(PK_FEATURES_LDS,          kBlock, 0, FEATURES, k_features<true>)                                              \
     X(PK_FEATURES,              kBlock, 0, FEATURES, k_features<false>)                                             \
     X(PK_IDS_LDS,               kBlock, 0, FEATURES, k_ids<true>)                                                   \
-    X(PK_IDS,                   kBlock, 0, FEATURES, k_ids<false>)
+    X(PK_IDS,                   kBlock, 0, FEATURES, k_ids<false>)                                                  \
+    X(PK_SHADE_GROUPS_MIXED,    kBlock, 0, SHADE_GROUPS, k_shade_groups<true, true>)                                \
+    X(PK_SHADE_GROUPS_LDS,      kBlock, 0, SHADE_GROUPS, k_shade_groups<true>)                                      \
+    X(PK_SHADE_GROUPS,          kBlock, 0, SHADE_GROUPS, k_shade_groups<false>)
 
 enum PathKernel : int
 {
@@ -131,6 +134,7 @@ struct LaunchArgs
     GatherJob gather;               // k_generate_gather, k_gather_reduce, k_gather_sh_reduce
     int shOrder;                    // k_gather_sh_reduce: the highest band
     FeatureJob features;            // k_features, k_ids
+    GroupState groups;              // k_shade_groups
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -150,6 +154,7 @@ struct LaunchArgs
 #define TN_ARGS_GATHER_REDUCE a.ps.rad, a.gather
 #define TN_ARGS_GATHER_SH_REDUCE a.ps.rad, a.gather, a.shOrder
 #define TN_ARGS_FEATURES a.scene, a.features, a.cam, a.fp, a.passSeeds, a.stackEntries
+#define TN_ARGS_SHADE_GROUPS TN_ARGS_SHADE, a.groups
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

@@ -322,6 +322,18 @@ struct SplitState
     int32_t neePerPath; // K
 };
 
+// Light groups (tinsel_hip_render_light_groups*): what k_shade_groups is handed beside the SplitState -- a kernel argument of its own, behind
+// the others, so that no other kernel's argument block moves.  A path's planes are addressed by the slot it carries: nothing moves when a
+// path is compacted, and the lane that owns the path is the only writer of its 16-byte records (one load, x = x + term, one store).
+constexpr int kMaxLightGroups = 8;
+struct GroupState
+{
+    float4* grp;            // [g*stride + slot] plane g's radiance of the batch's paths, laid out as the accumulate kernels read radOut; zeroed per batch
+    const int8_t* groupOf;  // [numPrims] the group a primitive's emission lands in, -1: in none
+    int32_t envGroup;       // ... the sky's / probe's
+    uint32_t stride;        // slots per plane
+};
+
 TN_D uint32_t wave_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 // this wave's index in its workgroup, as a SCALAR (threadIdx.x/64 is wave-uniform, but only readfirstlane tells the compiler: what hangs off it --
 // region index, base, length, pool pointer -- then lives in SGPRs, or their spill lanes, instead of a VGPR each)

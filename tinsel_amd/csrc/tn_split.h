@@ -470,11 +470,27 @@ struct ShadeFetch
     }
 };
 
+// Light groups: one term into plane g of the path's slot (GroupState, tn_path_state.h) -- a 16-byte load, x = x + term, a 16-byte store; the
+// lane that owns the path is the only writer.  g < 0: the emitter is in no group.
+TN_D void group_deposit(const GroupState& gs, int g, uint32_t slot, V3 term)
+{
+    if (g < 0)
+        return;
+    float4* const at = gs.grp + (size_t)g*gs.stride + slot;
+    float4 x = *at;
+    x.x = x.x + term.x;
+    x.y = x.y + term.y;
+    x.z = x.z + term.z;
+    *at = x;
+}
+
 // the shading half of one path (shared by the two k_shade kernels): on_hit_begin / on_miss, the BSDF terms of the arriving light
 // samples, the BSDF step; true when the path goes on (its state in `p`, `front`: its next ray enters a mesh in HBM)
-template <class SC>
+// GROUPS (k_shade_groups, light groups): every term the integrator adds to totalRadiance is also deposited into the plane of its emitter's
+// group (gs->grp), and the path's own radiance goes nowhere -- the call reads the planes.
+template <class SC, bool GROUPS = false>
 TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int bounce, int maxDepth, int rrStart, const BinPrims& bp,
-                     PathRegs& p, uint32_t& slot, bool& front)
+                     PathRegs& p, uint32_t& slot, bool& front, const GroupState* gs = nullptr)
 {
     const int K = ss.neePerPath;
     bool alive = false;
@@ -483,6 +499,8 @@ TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int boun
     const int prim = f.prim;
     if (prim < 0)
     {
+        if constexpr (GROUPS)
+            group_deposit(*gs, gs->envGroup, slot, miss_term(sc, p, bounce));
         on_miss(sc, p, bounce);
     }
     else
@@ -492,6 +510,12 @@ TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int boun
 
         HitCtx h;
         on_hit_begin(p, mat, hh.x, V3(hh.y, hh.z, hh.w), bounce, h, prim);
+        if constexpr (GROUPS)
+        {
+            V3 term;
+            if (hit_emission_term(p, mat, hh.x, V3(hh.y, hh.z, hh.w), bounce, term))
+                group_deposit(*gs, gs->groupOf[prim], slot, term);
+        }
 
         // SampleLights, after the traces (render.cpp:118-139, 171-224): k_shadow left, per shadow ray, the primitive
         // whose emission arrives; the BSDF terms are evaluated for those rays only
@@ -501,23 +525,59 @@ TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int boun
             LightCursor lights;
             const float2* res = ss.neeRes + qn;
             const float4* wis = ss.neeRay + (size_t)ss.capacity + qn;       // {wi, nl} of ray k at wis[k*2*capacity]
-            V3 sum = nee_sum(sc, [&](int k) -> V3 {
+            // (GROUPS: the samples whose emitter -- the primitive whose emission arrives, or the probe -- is in group `want`; the others add
+            // an exact zero, as they do in a scene where only that group emits)
+            [[maybe_unused]] int want = -1;
+            auto contrib = [&](int k) -> V3 {
                 const float2 rk = res[(size_t)k*ss.capacity];
                 const int hp = __float_as_int(rk.x);
                 if (sc.probe.valid && k == 0)
                 {
                     if (hp < 0)
                         return V3(0.0f);
+                    if constexpr (GROUPS)
+                        if (gs->envGroup != want)
+                            return V3(0.0f);
                     const float4 w = wis[0], sky = ss.neeSky[qn];
                     return nee_contrib_probe(mat, h, V3(w.x, w.y, w.z), V3(sky.x, sky.y, sky.z), sky.w);
                 }
                 const int light = lights.next(sc);
                 if (hp < 0)
                     return V3(0.0f);
+                if constexpr (GROUPS)
+                    if (gs->groupOf[hp] != want)
+                        return V3(0.0f);
                 const float4 w = wis[(size_t)(k*2)*ss.capacity];
                 return nee_contrib_light(sc, mat, h, V3(w.x, w.y, w.z), w.w, light, hp, rk.y);
-            });
-            p.rad = p.rad + p.thr*sum;
+            };
+            if constexpr (GROUPS)
+            {
+                // which groups have a sample arriving: the K 8-byte results alone, no BSDF work; then nee_sum once per such group, so
+                // that each arriving sample's BSDF terms are evaluated once and no per-group array is indexed dynamically
+                uint32_t present = 0u;
+                for (int k = 0; k < K; ++k)
+                {
+                    const int hp = __float_as_int(res[(size_t)k*ss.capacity].x);
+                    if (hp < 0)
+                        continue;
+                    const int g = (sc.probe.valid && k == 0) ? gs->envGroup : (int)gs->groupOf[hp];
+                    if (g >= 0)
+                        present |= 1u << g;
+                }
+                while (present)
+                {
+                    want = __builtin_ctz(present);
+                    present &= present - 1u;
+                    lights = LightCursor();
+                    const V3 sum = nee_sum(sc, contrib);
+                    group_deposit(*gs, want, slot, p.thr*sum);
+                }
+            }
+            else
+            {
+                V3 sum = nee_sum(sc, contrib);
+                p.rad = p.rad + p.thr*sum;
+            }
         }
 
         // the last iteration's BSDF sample is never used by the oracle's loop (render.cpp:250)
@@ -528,8 +588,9 @@ TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int boun
         if (alive)
             front = bp.count == 0 || ray_enters_big_mesh(sc.primBoxes, bp, p.o, p.d);
     }
-    if (!alive)
-        ss.radOut[slot] = make_float4(p.rad.x, p.rad.y, p.rad.z, __int_as_float(p.rayType));
+    if constexpr (!GROUPS)
+        if (!alive)
+            ss.radOut[slot] = make_float4(p.rad.x, p.rad.y, p.rad.z, __int_as_float(p.rayType));
     return alive;
 }
 
@@ -567,6 +628,49 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade(DevScene scIn,
             uint32_t slot = 0;
             if (j < n)
                 alive = shade_path(sc, ss, f, bounce, maxDepth, rrStart, bp, p, slot, front);
+            const uint32_t np = out.push(alive, front);
+            if (alive)
+                store_state(ss, nxt, np, p, slot);
+        }
+        if (lane == 0)
+        {
+            ss.segFront[(size_t)(bounce + 1)*ss.numRegions + r] = out.nFront;
+            ss.segBack[(size_t)(bounce + 1)*ss.numRegions + r] = out.nBack;
+        }
+    }
+}
+
+// k_shade_groups: k_shade for tinsel_hip_render_light_groups* -- the same loop over the same state, shade_path's GROUPS form, and the planes as
+// an argument of its own behind k_shade's (a kernel of its own name: k_shade's instances and their argument blocks stay what they are)
+template <bool LDS, bool MIXED = false>
+__global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade_groups(DevScene scIn, SplitState ss, int bounce, int maxDepth, int rrStart, BinPrims bp,
+                                                                         const uint32_t* __restrict__ order, GroupState gs)
+{
+    extern __shared__ uint32_t s_arena[];
+    SceneT<LDS, false, 2, MIXED> sc;
+    stage_scene_lds(sc, scIn, s_arena);
+    const uint32_t lane = __lane_id();
+    const int cur = bounce & 1, nxt = cur ^ 1;
+    const int K = ss.neePerPath;
+    const bool hasMedia = sc.hasMedia != 0;
+
+    for (uint32_t b = blockIdx.x; b < ss.numRegions/kRegionsPerBlock; b += gridDim.x)
+    {
+        const uint32_t r = (order ? order[b] : b)*kRegionsPerBlock + wave_in_block();
+        const uint32_t nFront = wave_uniform(ss.segFront[(size_t)bounce*ss.numRegions + r]);
+        const uint32_t n = nFront + wave_uniform(ss.segBack[(size_t)bounce*ss.numRegions + r]);
+        const uint32_t rBase = region_base(ss, r), rLen = region_len(ss, r);
+        RegionAppend out = { rBase, rLen, 0u, 0u };
+        for (uint32_t j0 = 0; j0 < n; j0 += kWave)
+        {
+            const uint32_t j = j0 + lane;
+            ShadeFetch f;
+            f.issue(ss, cur, region_pos(rBase, rLen, nFront, j < n ? j : 0u), j < n, hasMedia, K > 0, bounce == 0);
+            bool alive = false, front = true;
+            PathRegs p;
+            uint32_t slot = 0;
+            if (j < n)
+                alive = shade_path<SceneT<LDS, false, 2, MIXED>, true>(sc, ss, f, bounce, maxDepth, rrStart, bp, p, slot, front, &gs);
             const uint32_t np = out.push(alive, front);
             if (alive)
                 store_state(ss, nxt, np, p, slot);

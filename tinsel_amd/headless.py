@@ -7,6 +7,7 @@
                                   [-probes=probes.npz -probes_at=positions.npy] [-probes_spp=N] [-probes_order=0|1|2]
                                   [-features=features.npz] [-features_spp=N] [-denoise[=RADIUS]]
                                   [-mattes=FILE.npz] [-mattes_spp=N] [-mattes_slots=K]
+                                  [-lightgroups=FILE.npz] [-lightgroups_spp=N]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -57,6 +58,11 @@ float32: weighted sum xyz, weight sum w) and tinsel_amd.feature_images of them: 
 -features_spp), -mattes_slots pairs per pixel (default 6, 1 .. 8), filtered with the render's filter exactly as the image is.  The file
 holds `ids` [K, H, W] int32 (-1: the sample left the scene, -2: an unused slot), `weights` [K, H, W], `residual` [H, W], `total` [H, W]
 and `passes`; tinsel_amd.matte turns them into the coverage of a set of primitives.  Refused with what -features is refused with.
+-lightgroups=FILE.npz writes, beside a normal render, the light groups a compositor re-balances lights with (HipRenderer.light_groups):
+the render's own passes [0, -lightgroups_spp) (default min(spp, 16), as -features_spp) split by which emitter produced the radiance, one
+plane per group of tinsel_amd.default_light_groups -- every emitting primitive its own, the environment last.  The file holds `planes`
+[G, H, W, 4] float32 (accumulators: the render's clamp applies per plane), `group_of_primitive`, `env_group`, `names` and `passes`;
+tinsel_amd.relight mixes the planes.  Refused with what -features is refused with.
 -denoise[=RADIUS] does a normal render, then takes the features of its passes [0, spp), denoises the accumulator with the library's
 defaults (HipRenderer.denoise: the feature-guided filter on linear radiance; RADIUS 1 .. 8 replaces the default search radius), runs the
 display stage on the denoised image (HipRenderer.present_image) and writes that to -out (a .pfm gets the denoised linear radiance).
@@ -72,7 +78,7 @@ import numpy as np
 
 from . import abi
 from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
-from .renderer import Scene, create_gpu_renderer, denoise_params, feature_images, gather_points
+from .renderer import Scene, create_gpu_renderer, default_light_groups, denoise_params, feature_images, gather_points
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
 
@@ -82,7 +88,7 @@ def parse_args(argv):
         raise SystemExit(__doc__)
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
-           "mattes": None, "mattes_spp": None, "mattes_slots": None,
+           "mattes": None, "mattes_spp": None, "mattes_slots": None, "lightgroups": None, "lightgroups_spp": None,
            "denoise": None, "over": {}}
     for a in argv[1:-1]:
         if a == "-denoise":
@@ -100,7 +106,7 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups"):
             cfg[k] = v
         elif k == "denoise":
             cfg[k] = int(v)
@@ -110,6 +116,10 @@ def parse_args(argv):
             cfg[k] = int(v)
             if cfg[k] < 1:
                 raise SystemExit("-features_spp=%s: want 1 or more" % v)
+        elif k == "lightgroups_spp":
+            cfg[k] = int(v)
+            if cfg[k] < 1:
+                raise SystemExit("-lightgroups_spp=%s: want 1 or more" % v)
         elif k == "mattes_spp":
             cfg[k] = int(v)
             if cfg[k] < 1:
@@ -281,6 +291,19 @@ def mattes(r, cam, opt, cfg):
                                                                                        int((m["residual"] > 0).sum())))
 
 
+def lightgroups(r, scene, cam, opt, cfg):
+    """-lightgroups: the render's own samples of passes [0, N) split per emitter group (tinsel_hip_render_light_groups)"""
+    n = cfg["lightgroups_spp"] if cfg["lightgroups_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
+    table, env, names = default_light_groups(scene)
+    if not names:
+        raise SystemExit("-lightgroups: the scene has no emitter and no environment")
+    ts = time.perf_counter()
+    planes = r.light_groups(cam, opt, 0, n, table, env)
+    ms = (time.perf_counter() - ts)*1000.0
+    np.savez(cfg["lightgroups"], passes=np.int64(n), planes=planes, group_of_primitive=table, env_group=np.int64(env), names=np.array(names))
+    print("wrote %s: %dx%d, %d passes, %d groups (%s) in %.3fms" % (cfg["lightgroups"], opt.width, opt.height, n, len(names), ", ".join(names), ms))
+
+
 def denoise(r, cam, opt, cfg, samples):
     """-denoise: the features of the render's own passes, the denoise stage on the accumulator, the display stage on its result;
     returns (presented image, denoised linear image)"""
@@ -305,6 +328,12 @@ def main(argv=None):
     if cfg["mattes"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                           cfg["probes_at"]):
         raise SystemExit("-mattes writes the ID mattes of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
+                         "-firsthit, -irradiance or -probes")
+    if cfg["lightgroups_spp"] and not cfg["lightgroups"]:
+        raise SystemExit("-lightgroups_spp goes with -lightgroups=OUT.npz")
+    if cfg["lightgroups"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                               cfg["probes_at"]):
+        raise SystemExit("-lightgroups writes the light groups of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
                          "-firsthit, -irradiance or -probes")
     if cfg["denoise"] is not None and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                                        cfg["probes_at"]):
@@ -369,6 +398,8 @@ def main(argv=None):
         features(r, cam, opt, cfg)
     if cfg["mattes"]:
         mattes(r, cam, opt, cfg)
+    if cfg["lightgroups"]:
+        lightgroups(r, scene, cam, opt, cfg)
     linear = None
     if cfg["denoise"] is not None:
         image, linear = denoise(r, cam, opt, cfg, samples)

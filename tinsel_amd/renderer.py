@@ -105,6 +105,9 @@ def load_library():
     if hasattr(L, "tinsel_hip_render_id_mattes"):      # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_render_id_mattes.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, vp]
         L.tinsel_hip_render_id_mattes_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, vp, vp]
+    if hasattr(L, "tinsel_hip_render_light_groups"):   # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_light_groups.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, ci, vp]
+        L.tinsel_hip_render_light_groups_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, ci, vp, vp]
     if hasattr(L, "tinsel_hip_denoise"):               # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_denoise_params_init.restype = None
         L.tinsel_hip_denoise_params_init.argtypes = [C.POINTER(abi.DenoiseParams)]
@@ -196,6 +199,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_gather_sh", "tinsel_hip_gather_sh_device",
     "tinsel_hip_render_features", "tinsel_hip_render_features_device",
     "tinsel_hip_render_id_mattes", "tinsel_hip_render_id_mattes_device",
+    "tinsel_hip_render_light_groups", "tinsel_hip_render_light_groups_device",
     "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
 
@@ -402,6 +406,65 @@ def feature_images(planes):
     return out
 
 
+def default_light_groups(scene, max_groups=abi.MAX_LIGHT_GROUPS):
+    """A grouping for HipRenderer.light_groups: (group_of_primitive int32 [num_primitives], env_group, names).  Every primitive with
+    non-zero emission, in index order, gets a group of its own ("prim<i>"); when there are more of them than fit, the rest share the last
+    light group; the environment ("env") gets the group after the lights if the scene has a probe or a non-zero sky, else env_group is
+    -1.  Primitives that do not emit are in no group (-1)."""
+    max_groups = int(max_groups)
+    if not 1 <= max_groups <= abi.MAX_LIGHT_GROUPS:
+        raise ValueError("default_light_groups: max_groups is 1 .. %d" % abi.MAX_LIGHT_GROUPS)
+    d = scene.desc
+    prims = C.cast(d.primitives, C.POINTER(abi.Primitive))
+    emitters = [i for i in range(d.num_primitives) if any(v != 0.0 for v in prims[i].material.emission)]
+    env = bool(d.probe_valid) or any(v != 0.0 for v in tuple(d.sky_horizon) + tuple(d.sky_zenith))
+    room = max_groups - (1 if env else 0)
+    if emitters and room < 1:
+        raise ValueError("default_light_groups: max_groups = %d leaves no group for the lights beside the environment" % max_groups)
+    table = np.full(d.num_primitives, -1, np.int32)
+    names = []
+    for k, i in enumerate(emitters):
+        g = min(k, room - 1)
+        table[i] = g
+        if g == len(names):
+            names.append("prim%d" % i)
+        elif not names[g].endswith("+"):
+            names[g] += "+"
+    env_group = -1
+    if env:
+        env_group = len(names)
+        names.append("env")
+    return table, env_group, names
+
+
+def relight(planes, gains):
+    """The light mix: sum over g of gains[g]*planes[g] for planes [G, H, W, 4] (HipRenderer.light_groups) -- a gain is a scalar or an RGB
+    triple per group -- as an accumulator: float32 [H, W, 4] whose weight channel is plane 0's (every plane carries the beauty's), so the
+    result drops into present_image and denoise.  numpy arrays or torch tensors (the result is of the planes' kind); the sum runs in
+    float32, groups ascending."""
+    G = int(planes.shape[0])
+    if planes.ndim != 4 or planes.shape[-1] != 4 or G < 1:
+        raise ValueError("relight: planes [G, H, W, 4] are expected")
+    g = np.asarray(gains, np.float32)
+    if g.shape not in ((G,), (G, 3)):
+        raise ValueError("relight: one gain, or one RGB triple, per group is expected: shape (%d,) or (%d, 3)" % (G, G))
+    g = np.broadcast_to(g.reshape(G, -1), (G, 3))
+    if _is_tensor(planes):
+        import torch
+        gt = torch.as_tensor(np.ascontiguousarray(g), device=planes.device)
+        out = planes[0].clone()
+        out[..., :3] = planes[0][..., :3]*gt[0]
+        for k in range(1, G):
+            out[..., :3] += planes[k][..., :3]*gt[k]
+        return out
+    planes = np.asarray(planes, np.float32)
+    out = planes[0].copy()
+    out[..., :3] = planes[0][..., :3]*g[0]
+    for k in range(1, G):
+        out[..., :3] += planes[k][..., :3]*g[k]
+    return out
+
+
 def denoise_params(**fields):
     """tinsel_hip_denoise_params: the library's defaults (tinsel_hip_denoise_params_init) with `fields` over them -- radius, patch_radius,
     k_color, k_albedo, k_normal, k_depth, demodulate, albedo_floor"""
@@ -551,6 +614,7 @@ class HipRenderer:
             msg = L.tinsel_hip_last_error()
             raise TinselHipError("tinsel_hip_create failed: %s" % (msg.decode() if msg else "?"))
         self.device = device
+        self.num_primitives = int(scene.desc.num_primitives)     # (light_groups: the table the library reads has one entry each)
         self.width = self.height = 0
         self._accum_tensor = None
 
@@ -767,6 +831,42 @@ class HipRenderer:
             _check(self._L.tinsel_hip_render_features(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), mask,
                                                       out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_features")
         return {n: out[k] for k, n in enumerate(names)}
+
+    def light_groups(self, camera, options, pass_begin, passes, groups, env_group=None, out=None):
+        """Light groups (tinsel_hip_render_light_groups*): the beauty of passes [pass_begin, pass_begin + passes) split by which emitter
+        produced it, in one trace -- float32 [G, H, W, 4], plane g the accumulator a render would give with every emitter outside group g
+        black (bit for bit; options.clamp applies per plane).  `groups`: int [num_primitives], the group of each primitive's emission, -1
+        for none (default_light_groups makes one); env_group: the sky's / probe's group (None or -1: none).  G is the highest group
+        named + 1.  `out`: a contiguous float32 torch tensor [G, H, W, 4] on this renderer's device takes the device entry on torch's
+        current stream, not waited for; a numpy array of that shape is filled by the host entry.  Needs init() at the options' frame size;
+        leaves the accumulator, pass index, pass seeds and statistics as they were.  relight() mixes the planes."""
+        table = np.ascontiguousarray(np.asarray(groups).reshape(-1), np.int32)
+        env = -1 if env_group is None else int(env_group)
+        if out is not None:
+            G = int(out.shape[0])
+        else:
+            G = max(int(table.max()) if table.size else -1, env) + 1
+        if table.size != self.num_primitives:
+            raise ValueError("light_groups: groups has %d entries, the scene %d primitives" % (table.size, self.num_primitives))
+        H, W = int(options.height), int(options.width)
+        shape = (max(G, 1), H, W, 4)
+        if _is_tensor(out):
+            import torch
+            if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError("light_groups: a contiguous float32 tensor %s on the GPU is expected" % (shape,))
+            if out.device.index != self.device:
+                raise ValueError("light_groups: the tensor is on %s, the renderer on device %d" % (out.device, self.device))
+            _check(self._L.tinsel_hip_render_light_groups_device(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), G,
+                                                                 _host_ptr(table), env, out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "tinsel_hip_render_light_groups_device")
+        else:
+            if out is None:
+                out = np.zeros(shape, np.float32)
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("light_groups: a C-contiguous float32 array %s is expected" % (shape,))
+            _check(self._L.tinsel_hip_render_light_groups(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), G,
+                                                          _host_ptr(table), env, out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_light_groups")
+        return out
 
     def id_mattes(self, camera, options, pass_begin=0, passes=1, slots=6, out=None):
         """ID mattes (tinsel_hip_render_id_mattes*): per pixel the ranked list of (primitive id, filter-weight sum) pairs of the beauty's own
