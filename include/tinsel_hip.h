@@ -215,6 +215,7 @@ typedef struct tinsel_hip_tuning {
     int32_t walk_grid_mult;     /* 0 default (1) | k_walk's grid in resident sets of workgroups: each workgroup a contiguous 1/grid of the work list */
     int32_t quads_in_scan;      /* -1 auto | 0: a quad (two-triangle mesh: a lamp) beside meshes walked by k_walk sends the scene to the general scan kernels (inline mesh walk compiled in) */
     int32_t bounce_fit;         /* -1 auto | 0: k_bounce's general instance even where one compiled for the scene's feature set exists */
+    int32_t plane_pairs;        /* -1 auto | 0: the flat scan's plane table holds single planes only (no two opposing planes share a division) */
 } tinsel_hip_tuning;
 enum { TINSEL_ACCUMULATE_AUTO = 0, TINSEL_ACCUMULATE_TILED = 1, TINSEL_ACCUMULATE_WIDE = 2, TINSEL_ACCUMULATE_PIPED = 3, TINSEL_ACCUMULATE_FULL_WINDOW = 4 };
 
@@ -796,6 +797,17 @@ int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2);
 /* The SCENE's share of those bits (media, probe, motion, mesh walk, sphere, transmission) from a scene description alone: no device, no
  * renderer.  What a renderer created from `scene` with the default tuning reports until a primitive is moved or a mesh tree rebuilt. */
 unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene);
+/* The pairing RULE on a scene description (no device, no renderer): among the planes whose leaf of the scene BVH is an "infinite" box,
+ * two whose eight coefficients are finite and whose normal components are each other's bitwise negation (or both zeros of any sign)
+ * are a pair, greedily in primitive order, no plane twice.  Writes up to `capacity` pairs as (a, b) primitive indices, a < b, into
+ * out_pairs[2*capacity] (NULL: count only) and returns the number of pairs; *out_singles (where given) is the number of such planes left
+ * single.  Whether a renderer of the scene HAS a plane table, and pairs in it, is decided at create: no table with fewer than four
+ * such planes and no mesh in HBM, or beyond the flat scan; no pairs with two or more mesh primitives that all ride in the arena, or
+ * with tinsel_hip_tuning::plane_pairs = 0.  tinsel_hip_plane_table reports what a live renderer holds. */
+int tinsel_hip_scene_plane_pairs(const tinsel_scene_desc* scene, int32_t* out_pairs, int capacity, int* out_singles);
+/* The plane table of the scene level in force: out2[0] = opposing pairs, out2[1] = single planes (both 0 where the scene has no table).
+ * Follows tinsel_hip_rebuild_scene, tinsel_hip_refit_mesh and tinsel_hip_tuning::plane_pairs. */
+int tinsel_hip_plane_table(tinsel_hip* r, int* out2);
 /* 1 where a path of `scene` carries the SLIM state in the fused kernel's compiled instances (kinds 2 and 3), else 0: no media, probe, motion,
  * mesh walk or transmission among the bits above, and every material's `subsurface` is +0.0f BY ITS BITS (-0.0f is not).  A scene that is
  * not slim runs the general kernel (kind 0) whatever its bits; the bits themselves do not know about subsurface.  No device, no renderer. */

@@ -773,6 +773,14 @@ int tinsel_hip_set_tuning(tinsel_hip* r, const tinsel_hip_tuning* tuning)
         r->batchSlotsExplicit = false;
     }
     free_batch(r);          // (the region arrays are sized by grid_mult)
+    if (pairs_planes(r, was) != pairs_planes(r, t) && !r->planeTablePrims.empty())
+    {
+        // the plane table once more, with or without its pairs: the scene level in force, derived again
+        SceneLevel lvl;
+        if (!build_scene_level(r->sceneBvhHost, r->primsHost, r->planeTablePrims, pairs_planes(r, t), lvl))
+            return fail("set_tuning: the scene level could not be derived again");
+        return upload_scene_level(r, lvl);
+    }
     return 0;
 }
 
@@ -890,6 +898,46 @@ unsigned int tinsel_hip_scene_features(const tinsel_scene_desc* scene)
         }
     }
     return f;
+}
+
+int tinsel_hip_scene_plane_pairs(const tinsel_scene_desc* scene, int32_t* out_pairs, int capacity, int* out_singles)
+{
+    if (out_singles)
+        *out_singles = 0;
+    if (!scene || !scene->primitives || !scene->bvh_nodes || capacity < 0)
+        return 0;
+    // the planes create would put into the table: those whose leaf of the scene BVH is an "infinite" box
+    std::vector<int32_t> planes;
+    std::vector<float> eqs;
+    for (int n = 0; n < scene->num_bvh_nodes; ++n)
+    {
+        const tinsel_bvh_node& nd = scene->bvh_nodes[n];
+        if (!ref_is_leaf(nd) || nd.left_index >= (uint32_t)scene->num_primitives || scene->primitives[nd.left_index].type != TINSEL_GEOM_PLANE)
+            continue;
+        if (make_prim_box(nd).alwaysHit && std::find(planes.begin(), planes.end(), (int32_t)nd.left_index) == planes.end())
+            planes.push_back((int32_t)nd.left_index);
+    }
+    std::sort(planes.begin(), planes.end());
+    for (const int32_t k : planes)
+        eqs.insert(eqs.end(), scene->primitives[k].geo.plane.plane, scene->primitives[k].geo.plane.plane + 4);
+    const std::vector<std::pair<int, int>> pairs = pair_planes(eqs);
+    for (size_t q = 0; q < pairs.size() && out_pairs && (int)q < capacity; ++q)
+    {
+        out_pairs[2*q] = planes[(size_t)pairs[q].first];
+        out_pairs[2*q + 1] = planes[(size_t)pairs[q].second];
+    }
+    if (out_singles)
+        *out_singles = (int)planes.size() - 2*(int)pairs.size();
+    return (int)pairs.size();
+}
+
+int tinsel_hip_plane_table(tinsel_hip* r, int* out2)
+{
+    if (!r || !out2)
+        return fail("plane_table: bad arguments");
+    out2[0] = r->planePairs;
+    out2[1] = r->planeSingles;
+    return 0;
 }
 
 int tinsel_hip_scene_slim(const tinsel_scene_desc* scene)

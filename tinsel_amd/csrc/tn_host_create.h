@@ -228,7 +228,7 @@ int SceneBuild::add_primitives()
 // the scene level (tn_host_scene.h; the plane table is decided in assemble_arena) and the traversal stack over it
 int SceneBuild::scene_level()
 {
-    if (!build_scene_level(std::vector<tinsel_bvh_node>(desc->bvh_nodes, desc->bvh_nodes + desc->num_bvh_nodes), prims, {}, lvl))
+    if (!build_scene_level(std::vector<tinsel_bvh_node>(desc->bvh_nodes, desc->bvh_nodes + desc->num_bvh_nodes), prims, {}, false, lvl))
         return fail("create: malformed scene BVH");
     const int need = lvl.bvh.maxLeafDepth + 1 + maxMeshNeed;
     r->stackNeed = pick_stack(need);
@@ -312,15 +312,17 @@ int SceneBuild::assemble_arena()
         for (int k = 0; k < P; ++k)
             if (prims[(size_t)k].type == kPrimPlane && lvl.boxes[(size_t)k].alwaysHit)
                 r->planeTablePrims.push_back(k);
-        mark_plane_table(lvl, prims, r->planeTablePrims);
+        // Opposing planes of the table are tested as pairs (trace_flat), except where the fused kernel would defer mesh walks (two or more
+        // mesh primitives, all in the arena): those instances of k_bounce have no scalar registers left for the pair block and carry none
+        int meshPrimCount = 0;
+        for (int k = 0; k < P; ++k)
+            meshPrimCount += prims[(size_t)k].type == kPrimMesh ? 1 : 0;
+        r->pairablePlanes = !(meshPrimCount >= 2 && !anyMeshInHbm);
+        mark_plane_table(lvl, prims, r->planeTablePrims, pairs_planes(r, tune));
     }
-    std::vector<float> planeEq = lvl.planeEq;
-    std::vector<int32_t> planeIdx = r->planeTablePrims;
-    while (planeIdx.size() % 4)
-    {
-        planeEq.insert(planeEq.end(), { 0.0f, 0.0f, 0.0f, 0.0f });      // d == 0: IntersectRayPlane's own "no hit"
-        planeIdx.push_back(0);
-    }
+    // (the table's slots are reserved once: pairs dissolve and form again as planes move, mark_plane_table keeps within them)
+    const std::vector<float>& planeEq = lvl.planeEq;
+    const std::vector<int32_t>& planeIdx = lvl.planeIdx;
     const size_t offBoxes = arena.add(lvl.boxes.data(), lvl.boxes.size());
     const size_t offPlaneEq = arena.add(planeEq.data(), planeEq.size());
     const size_t offPlaneIdx = arena.add(planeIdx.data(), planeIdx.size());
@@ -360,7 +362,6 @@ int SceneBuild::assemble_arena()
     sc.primBoxes = reinterpret_cast<const PrimBox*>(arenaDev + offBoxes);
     sc.planeEq = reinterpret_cast<const float4*>(arenaDev + offPlaneEq);
     sc.planeIdx = reinterpret_cast<const int32_t*>(arenaDev + offPlaneIdx);
-    sc.numPlanes = (int32_t)r->planeTablePrims.size();
     adopt_scene_level(r, lvl);
     r->arenaOffNodes = offNodes;
     r->arenaOffBoxes = offBoxes;

@@ -72,44 +72,135 @@ void union_ancestors(std::vector<tinsel_bvh_node>& tree)
     }
 }
 
-// The scene level: the device form of a scene BVH and what the flat scan derives from it.  A pure function of the tree, the primitives
-// and the plane table (build_scene_level): create, tinsel_hip_rebuild_scene and tinsel_hip_refit_mesh all go through it.
+// The scene level: the device form of a scene BVH and what the flat scan derives from it.  A pure function of the tree, the primitives,
+// the plane table and whether it may pair planes (build_scene_level): create, tinsel_hip_rebuild_scene and tinsel_hip_refit_mesh all go through it.
 struct SceneLevel
 {
     std::vector<tinsel_bvh_node> tree;  // in the reference's format (tinsel_hip::sceneBvhHost once in force)
     ConvertedBvh bvh;
     std::vector<PrimBox> boxes;         // by primitive: its leaf's box; 2 for a plane of the plane table
-    std::vector<float> planeEq;         // four per plane-table entry (DevScene::planeEq without create's padding)
+    std::vector<float> planeEq;         // DevScene::planeEq, four per slot, and DevScene::planeIdx: as many slots as create reserved, whatever is in them
+    std::vector<int32_t> planeIdx;
+    int32_t numPlanes = 0, planePairEnd = 0;    // DevScene's
+    int planePairs = 0, planeSingles = 0;       // what the table holds (tinsel_hip_plane_table)
     unsigned long long scanMask = 0;    // DevScene::scanMask: the primitives < 64 the scan loop tests (those not in the plane table)
     bool everyPrimHasALeaf = true;
 };
 
-// The plane table (the flat scan's always-hit planes, tested four at a time ahead of the loop) on the level's boxes.  A table plane whose
-// leaf box is no longer "infinite" (the primitive was scaled below 0.1, or the caller's tree has a tighter leaf) is box-tested in the loop
-// like everything else -- its table entry becomes d == 0, IntersectRayPlane's own "no hit" -- and one whose box is infinite again gets its
-// equation back (the table used to be written at create only).
-void mark_plane_table(SceneLevel& lvl, const std::vector<Prim64>& prims, const std::vector<int32_t>& planeTable)
+// May two planes of the plane table be tested as an OPPOSING PAIR (trace_flat, tn_plane.h)?  All eight coefficients finite, and each normal
+// component of B the bitwise negation of A's, or both zeros of any sign -- what makes B's dot products the exact negations of A's.
+bool plane_pair_ok(const float a[4], const float b[4])
 {
-    lvl.planeEq.assign(planeTable.size()*4, 0.0f);
-    for (size_t t = 0; t < planeTable.size(); ++t)
+    for (int c = 0; c < 4; ++c)
+        if (!std::isfinite(a[c]) || !std::isfinite(b[c]))
+            return false;
+    for (int c = 0; c < 3; ++c)
     {
-        const int32_t k = planeTable[t];
+        uint32_t ua, ub;
+        memcpy(&ua, &a[c], 4); memcpy(&ub, &b[c], 4);
+        if (ub != (ua ^ 0x80000000u) && !(a[c] == 0.0f && b[c] == 0.0f))
+            return false;
+    }
+    return true;
+}
+
+// The pairs among `eqs` (four floats per plane), greedily in order, no plane twice: (a, b) positions with a < b, by a
+std::vector<std::pair<int, int>> pair_planes(const std::vector<float>& eqs)
+{
+    const int n = (int)(eqs.size()/4);
+    std::vector<char> used((size_t)n, 0);
+    std::vector<std::pair<int, int>> out;
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n && !used[(size_t)a]; ++b)
+            if (!used[(size_t)b] && plane_pair_ok(&eqs[(size_t)a*4], &eqs[(size_t)b*4]))
+            {
+                used[(size_t)a] = used[(size_t)b] = 1;
+                out.emplace_back(a, b);
+            }
+    return out;
+}
+
+// Slots of a plane table of `pairs` pairs and `singles` single planes: a block of eight per two pairs (A0 B0 A1 B1 R - - -: a single rides
+// with them; an odd pair's block has no second pair), then the singles left, in fours (DevScene::planePairEnd)
+int plane_table_slots(int pairs, int singles)
+{
+    const int blocks = (pairs + 1)/2, riders = std::min(blocks, singles);
+    return 8*blocks + (singles - riders + 3)/4*4;
+}
+
+// The plane table (the flat scan's always-hit planes, tested ahead of the loop: opposing pairs with one division each, then the singles four
+// at a time; plane_table_slots) on the level's boxes.  A table plane whose leaf box is no longer "infinite" (the primitive was scaled below 0.1, or the caller's
+// tree has a tighter leaf) is box-tested in the loop like everything else and leaves the table -- a pair it was in dissolves, its partner is
+// a single -- and one whose box is infinite again comes back (the table used to be written at create only).  Empty slots hold
+// d == 0, IntersectRayPlane's own "no hit".  `pairPlanes` false (tinsel_hip_tuning::plane_pairs = 0): singles only.
+void mark_plane_table(SceneLevel& lvl, const std::vector<Prim64>& prims, const std::vector<int32_t>& planeTable, bool pairPlanes)
+{
+    std::vector<int32_t> live;
+    std::vector<float> eqs;
+    for (const int32_t k : planeTable)
         if (lvl.boxes[(size_t)k].alwaysHit)
         {
             lvl.boxes[(size_t)k].alwaysHit = 2u;
             const Prim64& pp = prims[(size_t)k];
-            lvl.planeEq[t*4 + 0] = pp.g0; lvl.planeEq[t*4 + 1] = pp.g1; lvl.planeEq[t*4 + 2] = pp.g2; lvl.planeEq[t*4 + 3] = pp.g3;
+            live.push_back(k);
+            eqs.insert(eqs.end(), { pp.g0, pp.g1, pp.g2, pp.g3 });
         }
+    // What create reserved is what the table has, whatever moves later: room for every table plane as a single, and for the pairing of all of
+    // them.  A later pairing that would take more (a pair dissolved, and its partner no longer fits a block of four) gives up pairs, last first.
+    std::vector<float> all;
+    for (const int32_t k : planeTable)
+        all.insert(all.end(), { prims[(size_t)k].g0, prims[(size_t)k].g1, prims[(size_t)k].g2, prims[(size_t)k].g3 });
+    const int allPairs = (int)pair_planes(all).size();
+    const size_t cap = (size_t)std::max(plane_table_slots(0, (int)planeTable.size()), plane_table_slots(allPairs, (int)planeTable.size() - 2*allPairs));
+    std::vector<std::pair<int, int>> pairs = pairPlanes ? pair_planes(eqs) : std::vector<std::pair<int, int>>();
+    while ((size_t)plane_table_slots((int)pairs.size(), (int)live.size() - 2*(int)pairs.size()) > cap)
+        pairs.pop_back();
+    std::vector<char> paired(live.size(), 0);
+    for (const auto& ab : pairs)
+        paired[(size_t)ab.first] = paired[(size_t)ab.second] = 1;
+    std::vector<int> singles;
+    for (size_t t = 0; t < live.size(); ++t)
+        if (!paired[t])
+            singles.push_back((int)t);
+
+    lvl.planeEq.assign(cap*4, 0.0f);
+    lvl.planeIdx.assign(cap, 0);
+    auto put = [&](size_t slot, int t) {
+        std::copy(eqs.begin() + (size_t)t*4, eqs.begin() + (size_t)t*4 + 4, lvl.planeEq.begin() + slot*4);
+        lvl.planeIdx[slot] = live[(size_t)t];
+    };
+    size_t slot = 0, nextSingle = 0;
+    for (size_t q = 0; q < pairs.size(); q += 2, slot += 8)
+    {
+        put(slot, pairs[q].first); put(slot + 1, pairs[q].second);
+        if (q + 1 < pairs.size())
+        {
+            put(slot + 2, pairs[q + 1].first); put(slot + 3, pairs[q + 1].second);
+        }
+        if (nextSingle < singles.size())
+            put(slot + 4, singles[nextSingle++]);
+        // (the four pair slots' indices once more, as the bytes of the first unused slot's word: trace_flat)
+        lvl.planeIdx[slot + 5] = lvl.planeIdx[slot] | (lvl.planeIdx[slot + 1] << 8) | (lvl.planeIdx[slot + 2] << 16) | (lvl.planeIdx[slot + 3] << 24);
     }
+    lvl.planePairEnd = (int32_t)slot;
+    while (nextSingle < singles.size())
+        put(slot++, singles[nextSingle++]);
+    lvl.numPlanes = (int32_t)slot;
+    lvl.planePairs = (int)pairs.size();
+    lvl.planeSingles = (int)singles.size();
+
     lvl.scanMask = 0;
     for (size_t k = 0; k < lvl.boxes.size() && k < 64; ++k)
         if (lvl.boxes[k].alwaysHit != 2u)
             lvl.scanMask |= 1ull << k;
 }
 
+// Does the plane table of this renderer's scene pair its opposing planes under `tune`?
+bool pairs_planes(const tinsel_hip* r, const tinsel_hip_tuning& tune) { return tune.plane_pairs != 0 && r->pairablePlanes; }
+
 // The scene level of `tree` over `prims` (their count is what a leaf may index) and `planeTable`.  False, with nothing derived, where
 // convert_bvh refuses the tree.
-bool build_scene_level(std::vector<tinsel_bvh_node> tree, const std::vector<Prim64>& prims, const std::vector<int32_t>& planeTable, SceneLevel& out)
+bool build_scene_level(std::vector<tinsel_bvh_node> tree, const std::vector<Prim64>& prims, const std::vector<int32_t>& planeTable, bool pairPlanes, SceneLevel& out)
 {
     const int P = (int)prims.size();
     if (!convert_bvh(tree.data(), (int)tree.size(), P, 0, out.bvh))
@@ -124,7 +215,7 @@ bool build_scene_level(std::vector<tinsel_bvh_node> tree, const std::vector<Prim
             seen[nd.left_index] = 1;
         }
     out.everyPrimHasALeaf = std::find(seen.begin(), seen.end(), 0) == seen.end();
-    mark_plane_table(out, prims, planeTable);
+    mark_plane_table(out, prims, planeTable, pairPlanes);
     out.tree = std::move(tree);
     return true;
 }
@@ -134,6 +225,10 @@ void adopt_scene_level(tinsel_hip* r, SceneLevel& lvl)
 {
     r->scene.root = lvl.bvh.root;
     r->scene.scanMask = lvl.scanMask;
+    r->scene.numPlanes = lvl.numPlanes;
+    r->scene.planePairEnd = lvl.planePairEnd;
+    r->planePairs = lvl.planePairs;
+    r->planeSingles = lvl.planeSingles;
     r->sceneStackNeed = lvl.bvh.maxLeafDepth + 1;
     r->sceneBvhHost = std::move(lvl.tree);
 }
@@ -146,7 +241,10 @@ int upload_scene_level(tinsel_hip* r, SceneLevel& lvl)
         HIP_TRY(hipMemcpy(arenaDev + r->arenaOffNodes, lvl.bvh.nodes.data(), sizeof(Node64)*lvl.bvh.nodes.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(arenaDev + r->arenaOffBoxes, lvl.boxes.data(), sizeof(PrimBox)*lvl.boxes.size(), hipMemcpyHostToDevice));
     if (!lvl.planeEq.empty())
+    {
         HIP_TRY(hipMemcpy(const_cast<float4*>(r->scene.planeEq), lvl.planeEq.data(), sizeof(float)*lvl.planeEq.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(const_cast<int32_t*>(r->scene.planeIdx), lvl.planeIdx.data(), sizeof(int32_t)*lvl.planeIdx.size(), hipMemcpyHostToDevice));
+    }
     adopt_scene_level(r, lvl);
     return 0;
 }
@@ -314,7 +412,7 @@ int tinsel_hip_refit_mesh(tinsel_hip* r, int primitive, const float* positions_x
     // (all P leaf boxes and the plane table are uploaded again: the other primitives' come from the same leaves as before, and a mesh is
     // never in the plane table)
     SceneLevel lvl;
-    if (!build_scene_level(std::move(tree), r->primsHost, r->planeTablePrims, lvl))
+    if (!build_scene_level(std::move(tree), r->primsHost, r->planeTablePrims, pairs_planes(r, r->tune), lvl))
         return fail("refit_mesh: the scene BVH could not be refitted");
     return upload_scene_level(r, lvl);
 }
@@ -406,7 +504,7 @@ int tinsel_hip_rebuild_scene(tinsel_hip* r, int mode, const tinsel_bvh_node* nod
 
     // every check before anything is uploaded: a refused tree leaves the previous one in force
     SceneLevel lvl;
-    if (!build_scene_level(std::move(ref), r->primsHost, r->planeTablePrims, lvl))
+    if (!build_scene_level(std::move(ref), r->primsHost, r->planeTablePrims, pairs_planes(r, r->tune), lvl))
         return fail("rebuild_scene: malformed scene BVH");
     if ((int)lvl.bvh.nodes.size() != (P > 1 ? P - 1 : 0))
         return fail("rebuild_scene: the scene BVH must have one leaf per primitive");

@@ -17,7 +17,7 @@ inline tinsel_hip_tuning tuning_defaults()
     t.tail_divide = 4;
     t.accumulate = TINSEL_ACCUMULATE_AUTO;
     t.walk_block = 0;
-    t.walk_single = t.walk_lds_stack = t.quads_in_scan = t.bounce_fit = -1;
+    t.walk_single = t.walk_lds_stack = t.quads_in_scan = t.bounce_fit = t.plane_pairs = -1;
     t.walk_refill_min = t.walk_leaf_min = t.walk_grid_mult = 0;
     return t;
 }
@@ -67,6 +67,8 @@ struct tinsel_hip
     std::vector<tinsel_bvh_node> sceneBvhHost;
     size_t arenaOffNodes = 0, arenaOffBoxes = 0;
     std::vector<int32_t> planeTablePrims;       // the planes DevScene::planeEq holds (their PrimBox says 2: re-marked when the boxes are rewritten)
+    bool pairablePlanes = true;                 // false: this scene's fused instances carry no pair code (several arena meshes, none in HBM)
+    int planePairs = 0, planeSingles = 0;       // ... of them as opposing pairs / single planes in the scene level in force
     int sceneStackNeed = 1;
     std::string prepRefused;            // non-empty: a kernel whose dynamic-LDS limit the runtime refused to raise (prepare_kernels_once)
     bool sceneEnclosed = false;         // two planes face each other: (practically) no ray leaves the scene (k_bounce's shading pools stay off)

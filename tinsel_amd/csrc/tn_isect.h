@@ -8,6 +8,7 @@
 #pragma once
 
 #include "tn_scene.h"
+#include "tn_plane.h"
 
 namespace tn {
 
@@ -128,14 +129,10 @@ TN_D bool ray_sphere(V3 center, float radius, V3 o, V3 d, float& outT, V3& outN)
     return true;
 }
 
-// IntersectRayPlane (intersection.h:85-99); Dot(Vec4,Vec4) keeps the w term (maths.h:331)
+// IntersectRayPlane (intersection.h:85-99): tn_plane.h
 TN_D bool ray_plane(V3 p, V3 dir, float px, float py, float pz, float pw, float& t)
 {
-    float d = px*dir.x + py*dir.y + pz*dir.z + pw*0.0f;
-    if (d == 0.0f)
-        return false;
-    t = -(px*p.x + py*p.y + pz*p.z + pw*1.0f)/d;
-    return t > 0.0f;
+    return ray_plane_eq(p.x, p.y, p.z, dir.x, dir.y, dir.z, px, py, pz, pw, t);
 }
 
 // IntersectRayTriTwoSided (intersection.h:117-145)
@@ -533,12 +530,58 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
     // ray_aabb_minmax above) -- 12 instructions per box instead of 24
     const bool finiteAll = __all(finite_bits(rcp.x) && finite_bits(rcp.y) && finite_bits(rcp.z) &&
                                  finite_bits(o.x) && finite_bits(o.y) && finite_bits(o.z));
-    // The scene's always-hit planes FOUR AT A TIME, ahead of the loop (DevScene::planeEq: the same equations, padded with planes no ray
-    // meets; their boxes say 2 and the loop below passes them by).  Every lane is at the same primitive in this scan, so one
+    // The scene's always-hit planes ahead of the loop, the single ones FOUR AT A TIME (DevScene::planeEq: the same equations, its unused slots
+    // planes no ray meets; their boxes say 2 and the loop below passes them by).  Every lane is at the same primitive in this scan, so one
     // IntersectRayPlane after the other is one IEEE division's dependent chain after the other; four in one block are four independent
     // chains the scheduler interleaves (then two, then one: what is left).  The order of the accept() calls does not matter (above).
     const int numPlanes = sc.numPlanes;
     int pk = 0;
+    // OPPOSING PAIRS come first in the table (DevScene::planePairEnd; the host pairs them: plane_pair_ok, tn_host_scene.h): a ray that starts
+    // between the two planes of a pair can only hit the one its numerator's and the shared denominator's signs point at, so the pair
+    // shares its two dot products and takes ONE division, t > 0 test and accept() (tn_plane.h; DESIGN.md section 5 has the bit argument).
+    auto accept_of_pair = [&](const PlanePair& pp, const ConstF4V& ea, const ConstF4V& eb, int ia, int ib) {
+        float t;
+        if (plane_pair_hit(pp, t))
+        {
+            if (fabsf(t - minT) <= 1e-5f*fabsf(t))      // (accept(), with the chosen plane's index and normal -- B's as stored -- picked per lane)
+                tie = true;
+            if (t < minT)
+            {
+                minT = t;
+                if (pp.b) { closest = ib; cn = V3(eb.x, eb.y, eb.z); }
+                else      { closest = ia; cn = V3(ea.x, ea.y, ea.z); }
+            }
+        }
+    };
+    // A block is eight slots, A0 B0 A1 B1 R - - -: two pairs and a single plane that rides with them (a missing second pair or rider is a
+    // plane no ray meets) -- one request, three independent division chains (cornell: its four walls and the back wall).  Every slot
+    // has its index word; the sixth slot's holds the indices of A0 B0 A1 B1 once more as its four bytes (a flat-scan scene has at most 64
+    // primitives), so that the block keeps two index scalars, not five.
+    // Where any lane of the wave has both planes of a pair ahead, the wave leaves the pairs: the single-plane code below takes the table
+    // from this block on, slot by slot -- the IntersectRayPlane calls as they were, plus the empty slots'.
+    // Two kinds of k_bounce instance are short of scalar registers or code bytes (profiles/r19_plane_pairs.md):
+    //  * for deferred mesh walks (kDefer == 1): no pair code at all, which is always correct -- the code below then takes every slot --
+    //    and the host forms no pairs in their scenes (tn_host_create.h);
+    //  * the closed FIT instance (kCompactSingles): the first block only, not in a loop; further blocks go through the code below.
+    typedef const __attribute__((address_space(4))) uint32_t* ConstU32;
+    constexpr bool kCompactSingles = SC::kFeatures != kFeatAll && SC::kDefer != 1;
+    const int pairEnd = SC::kDefer != 1 ? (kCompactSingles ? min(sc.planePairEnd, 8) : sc.planePairEnd) : 0;
+    for (; pk + 8 <= pairEnd; pk += 8)
+    {
+        const ConstF4V e0 = sc.kPlaneEq[pk], e1 = sc.kPlaneEq[pk + 1], e2 = sc.kPlaneEq[pk + 2], e3 = sc.kPlaneEq[pk + 3], e4 = sc.kPlaneEq[pk + 4];
+        const uint32_t idr = ((ConstU32)sc.kPlaneIdx)[pk + 4], ids = ((ConstU32)sc.kPlaneIdx)[pk + 5];
+        const PlanePair p0 = plane_pair_pick(o.x, o.y, o.z, d.x, d.y, d.z, e0.x, e0.y, e0.z, e0.w, e1.w);
+        const PlanePair p1 = plane_pair_pick(o.x, o.y, o.z, d.x, d.y, d.z, e2.x, e2.y, e2.z, e2.w, e3.w);
+        if (__any(p0.both || p1.both))
+            break;
+        float t4;
+        const bool h4 = ray_plane(o, d, e4.x, e4.y, e4.z, e4.w, t4);
+        accept_of_pair(p0, e0, e1, (int)(ids & 255u), (int)((ids >> 8) & 255u));
+        accept_of_pair(p1, e2, e3, (int)((ids >> 16) & 255u), (int)(ids >> 24));
+        if (h4) accept((int)idr, t4, V3(e4.x, e4.y, e4.z));
+    }
+    // The single planes, four at a time; then the one, two or three that are left -- as a block of two and one of one, except in the closed
+    // FIT instance, which is held under 49 008 B of code (tests/test_slim_state.py) and takes them one after the other.
     for (; pk + 4 <= numPlanes; pk += 4)
     {
         const ConstF4V e0 = sc.kPlaneEq[pk], e1 = sc.kPlaneEq[pk + 1], e2 = sc.kPlaneEq[pk + 2], e3 = sc.kPlaneEq[pk + 3];
@@ -553,9 +596,21 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
         if (h2) accept(__float_as_int(id.z), t2, V3(e2.x, e2.y, e2.z));
         if (h3) accept(__float_as_int(id.w), t3, V3(e3.x, e3.y, e3.z));
     }
-    if (pk < numPlanes)
+    if constexpr (kCompactSingles)
     {
-        // the one, two or three that are left (the table is padded to a multiple of four: the loads are in bounds)
+        // the one, two or three that are left, one after the other
+        for (; pk < numPlanes; ++pk)
+        {
+            const ConstF4V e0 = sc.kPlaneEq[pk];
+            const uint32_t id = ((ConstU32)sc.kPlaneIdx)[pk];
+            float t0;
+            if (ray_plane(o, d, e0.x, e0.y, e0.z, e0.w, t0))
+                accept((int)id, t0, V3(e0.x, e0.y, e0.z));
+        }
+    }
+    else if (pk < numPlanes)
+    {
+        // the one, two or three that are left (the table's allocation is padded to a multiple of four slots: the loads are in bounds)
         const ConstF4V id = sc.kPlaneIdx[pk >> 2];
         const int left = numPlanes - pk;
         if (left >= 2)

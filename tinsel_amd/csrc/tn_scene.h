@@ -192,7 +192,11 @@ struct DevScene
     // their primitive indices, in the arena (trace_flat, tn_isect.h)
     const float4* planeEq;
     const int32_t* planeIdx;
-    int32_t numPlanes;              // (the table is padded to a multiple of four)
+    int32_t numPlanes;              // the slot after the last single plane (the table's ALLOCATION is a multiple of four slots; unused ones hold planes no ray meets)
+    // slots [0, planePairEnd) hold OPPOSING PAIRS (trace_flat tests a pair with one division): blocks of eight slots, A0 B0 A1 B1 R - - -
+    // (two pairs and a single plane that rides with them; planeIdx of the sixth slot: the four pair indices as bytes); the singles follow
+    // in fours.  0: no pairs
+    int32_t planePairEnd;
     // the primitives the flat scan's loop visits: bit i clear = primitive i is a plane of the table above, tested ahead of the loop (the loop
     // used to fetch such a primitive's leaf box only to read "pass by": five of cornell's eight scalar round trips per ray)
     unsigned long long scanMask;

@@ -142,6 +142,9 @@ def load_library():
         L.tinsel_hip_scene_features.argtypes = [C.POINTER(abi.SceneDesc)]
     if hasattr(L, "tinsel_hip_scene_slim"):           # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_scene_slim.argtypes = [C.POINTER(abi.SceneDesc)]
+    if hasattr(L, "tinsel_hip_scene_plane_pairs"):    # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_scene_plane_pairs.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]
+        L.tinsel_hip_plane_table.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "tinsel_hip_queue_counts"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_queue_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.tinsel_hip_set_lookahead.argtypes = [vp, ci]
@@ -179,7 +182,7 @@ def load_library():
 
 
 EXPORTED_SYMBOLS = [
-    "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_scene_slim", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
+    "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_scene_slim", "tinsel_hip_scene_plane_pairs", "tinsel_hip_plane_table", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
     "tinsel_hip_reset_stats", "tinsel_hip_stats_detail", "tinsel_hip_set_detail_counters", "tinsel_hip_render_cost", "tinsel_hip_kernel_times", "tinsel_hip_kernel_time_bytes",
@@ -527,6 +530,16 @@ class Scene:
         """tinsel_hip_scene_slim: do this scene's paths carry the slim state in the fused kernel's compiled instances (no device needed)"""
         return bool(load_library().tinsel_hip_scene_slim(C.byref(self.desc)))
 
+    def plane_pairs(self):
+        """tinsel_hip_scene_plane_pairs: ([(a, b), ...], singles) -- the pairing rule on this scene's always-hit planes, as primitive indices,
+        and how many of them stay single (no device needed).  Whether a renderer has a plane table and pairs in it is decided at create
+        (include/tinsel_hip.h); HipRenderer.plane_table() reports it."""
+        n = max(1, self.num_primitives//2)
+        out = (C.c_int32*(2*n))()
+        singles = C.c_int(0)
+        k = load_library().tinsel_hip_scene_plane_pairs(C.byref(self.desc), out, n, C.byref(singles))
+        return [(out[2*q], out[2*q + 1]) for q in range(k)], singles.value
+
 
 def _bytes_at(ptr, n):
     return C.string_at(ptr, n) if (ptr and n > 0) else b""
@@ -712,6 +725,12 @@ class HipRenderer:
         fields (abi.Tuning.CREATE_FIELDS) belong to create_gpu_renderer(scene, device, tuning)."""
         t = (tuning if tuning is not None else self.get_tuning()).replace(**fields)
         _check(self._L.tinsel_hip_set_tuning(self._h, C.byref(t)), "tinsel_hip_set_tuning")
+
+    def plane_table(self):
+        """tinsel_hip_plane_table: (opposing pairs, single planes) of the flat scan's plane table in force"""
+        out = (C.c_int*2)()
+        _check(self._L.tinsel_hip_plane_table(self._h, out), "tinsel_hip_plane_table")
+        return out[0], out[1]
 
     def get_tuning(self):
         t = abi.Tuning()
