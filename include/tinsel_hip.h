@@ -560,6 +560,53 @@ int tinsel_hip_render_light_groups_device(tinsel_hip* r, const tinsel_camera* ca
                                           uint32_t pass_begin, int passes, int num_groups, const int32_t* group_of_primitive, int env_group,
                                           float* out_dev, void* stream);
 
+/* View batches: the frames of MANY cameras on the one resident scene in one call -- the faces of a cube map, a stereo pair, a turntable,
+ * a few hundred small views as a training set -- where a loop over tinsel_hip_set_pass_index and tinsel_hip_render pays every launch of
+ * every bounce and an accumulate launch of a few tiles once per view.
+ * Plane v of `out`, out[((v*H + j)*W + i)*4 + c], is DEFINED as the accumulator tinsel_hip_render gives for cameras[v] from a zeroed
+ * accumulator at pass index pass_begin after `passes` passes: bit for bit in all four channels, the weight included.  All views share one
+ * seed table, pass_seed(pass_begin + s) for s in [0, passes); the path of (view v, pass s, pixel i, j) is the camera sample of cameras[v]
+ * seeded with i + j*W + pass_seed(pass_begin + s), traced with options->max_depth and the renderer's Russian-roulette setting, and added
+ * with options->filter and options->clamp by AddSample's rule, each pixel's adds in pass order, then raster order of the generating pixels.
+ * flags: TINSEL_VIEWS_ADD adds to what `out` holds instead of starting every plane from zero -- the passes [0, a) followed by [a, b) with
+ * the flag equal [0, b) in one call, bit for bit; TINSEL_VIEWS_ACCUMULATE_SINGLY adds every view's batch with a launch of the render's own
+ * accumulate kernels instead of one launch for all views of a batch (the same bits; the A/B arm, and what filters wider than 2 take anyway).
+ * The paths run the split or the paired pipeline, as a radiance query's do, also on a scene a render takes through the fused kernel and
+ * under every tinsel_hip_set_pipeline setting: k_generate_views in the place of k_generate -- timed under the name "k_generate" in
+ * tinsel_hip_kernel_times, the name table does not grow --, then one "k_accumulate" per batch (k_views_accumulate) or per view and batch.
+ * A batch is a run of consecutive views times a run of consecutive passes, as tinsel_hip_plan_views states it for the renderer's
+ * batch_paths; each pixel's adds stay in pass order, so the cut shows nowhere.
+ * The seeds, the cameras' table, the batch's radiance and the statistics the kernels count into are the call's own: the accumulator, the
+ * pass index, the renderer's seed table, tinsel_hip_stats, the tuning and look-ahead work in flight are left as they were, and a render, a
+ * views call and the render that follows give the images of the two renders alone.  The paths themselves live in the renderer's path
+ * buffers, used under the fences of the radiance queries.  A scene with moved or refitted primitives is served as radiance queries serve it
+ * (after tinsel_hip_rebuild_scene).  A group has no entry.
+ * options->max_depth < 1 zeroes the planes (with TINSEL_VIEWS_ADD: leaves them untouched).  Returns -1 before anything is launched or
+ * written for: a null argument, num_views outside 1 .. TINSEL_MAX_VIEWS, passes < 1 (or so many that a view's slots passes*W*H reach 2^32 -
+ * 1), another mode than TINSEL_MODE_PATHTRACE, a frame size that does not match the last tinsel_hip_init, a moved primitive without
+ * tinsel_hip_rebuild_scene, a sharded renderer (world > 1), TINSEL_ARITH_FAST (the contract is a bit contract), unknown flag bits, and
+ * for the device entry an out_dev that is not 16-byte aligned.
+ * Memory, kept until tinsel_hip_destroy: 16 bytes per path slot of a batch, 96 bytes per view, 4 bytes per pass, and for the host entry
+ * num_views*W*H*16 bytes of planes. */
+#define TINSEL_MAX_VIEWS 4096
+#define TINSEL_VIEWS_ADD               1u  /* add to what `out` holds instead of starting every plane from zero */
+#define TINSEL_VIEWS_ACCUMULATE_SINGLY 2u  /* one launch of the existing accumulate kernels per view (the A/B arm and the fallback) */
+
+/* host array of num_views*W*H*4 floats (read first with TINSEL_VIEWS_ADD); returns when it is written */
+int tinsel_hip_render_views(tinsel_hip* r, const tinsel_camera* cameras, int num_views, const tinsel_options* options,
+                            uint32_t pass_begin, int passes, unsigned flags, float* out_rgba_host);
+/* device array, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for; the cameras are a HOST array, read
+ * before the call returns.  The stream waits, on the device, for what the renderer's path buffers still serve and for an earlier views
+ * call on another stream. */
+int tinsel_hip_render_views_device(tinsel_hip* r, const tinsel_camera* cameras, int num_views, const tinsel_options* options,
+                                   uint32_t pass_begin, int passes, unsigned flags, float* out_rgba_dev, void* stream);
+/* The batch cut of a views call, host arithmetic only (no GPU needed): out3 = { views per batch, passes per batch, batches } for a limit
+ * of slot_limit path slots per batch (the renderer's batch_paths).  If one view's passes fit -- passes*W*H <= slot_limit -- a batch takes
+ * min(num_views, floor(slot_limit/(passes*W*H))) whole views with all their passes, the last batch the remainder; otherwise a batch takes
+ * ONE view with min(passes, max(1, floor(slot_limit/(W*H)))) passes.  There is always at least one pass of one view per batch, however
+ * small the limit.  Returns -1 for a bad argument and where a batch would have 2^32 - 1 slots or more. */
+int tinsel_hip_plan_views(unsigned long long slot_limit, int width, int height, int passes, int num_views, int* out3);
+
 /* Feature-guided denoise: a joint non-local-means filter on LINEAR radiance, in front of the display stage, guided by the planes above.
  * With features == 0 and demodulate == 0 it is NonLocalMeansFilter (nlm.cpp:35-77) on the normalised colour, bit for bit, falloff =
  * k_color and AverageFilter's radius = patch_radius; the guide terms add to the exponent.  Everything is fp32, one rounding per

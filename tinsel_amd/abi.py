@@ -171,6 +171,9 @@ FEATURE_NAMES = ("albedo", "normal", "depth")
 ID_MISS, ID_EMPTY, ID_MAX_SLOTS = -1, -2, 8
 # tinsel_hip_render_light_groups*: the most planes a call takes
 MAX_LIGHT_GROUPS = 8
+# tinsel_hip_render_views*: the most views a call takes, and its flags
+MAX_VIEWS = 4096
+VIEWS_ADD, VIEWS_ACCUMULATE_SINGLY = 1, 2
 
 
 class DenoiseParams(C.Structure):

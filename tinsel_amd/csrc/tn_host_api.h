@@ -300,6 +300,56 @@ int tinsel_hip_render_light_groups(tinsel_hip* r, const tinsel_camera* camera, c
     return 0;
 }
 
+// View batches (tn_views.h, tn_host_views.h): the frames of many cameras in one call, k_generate_views in front of a radiance query's
+// pipeline and one accumulate launch per batch of views behind it.  Own seeds, own radiance, own statistics block: nothing of the
+// renderer's frame state is written; the path buffers are used under the radiance queries' fences, look-ahead work in flight is waited for
+// on the device and kept.
+int tinsel_hip_render_views_device(tinsel_hip* r, const tinsel_camera* cameras, int num_views, const tinsel_options* options, uint32_t pass_begin,
+                                   int passes, unsigned flags, float* out_rgba_dev, void* stream)
+{
+    const char* const who = "render_views_device";
+    if (views_args(r, cameras, num_views, options, passes, flags, out_rgba_dev, who))
+        return -1;
+    if (query_arrays({ { out_rgba_dev, (size_t)r->width*r->height*sizeof(float4)*(size_t)num_views } }, who) || query_ready(r, who))
+        return -1;
+    return views_enqueue(r, cameras, num_views, options, pass_begin, passes, flags, (float4*)out_rgba_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_views(tinsel_hip* r, const tinsel_camera* cameras, int num_views, const tinsel_options* options, uint32_t pass_begin,
+                            int passes, unsigned flags, float* out_rgba_host)
+{
+    const char* const who = "render_views";
+    if (views_args(r, cameras, num_views, options, passes, flags, out_rgba_host, who) || query_ready(r, who))
+        return -1;
+    const size_t bytes = (size_t)r->width*r->height*sizeof(float4)*(size_t)num_views;
+    // (TINSEL_VIEWS_ADD without a bounce leaves the planes untouched: nothing to carry to the device and back)
+    if ((flags & TINSEL_VIEWS_ADD) && options->max_depth < 1)
+        return 0;
+    if (query_buffer(r->viewsOut, bytes))
+        return -1;
+    // (the staging planes are the host entry's alone, and it returns when they have been read: nothing in flight touches them)
+    if (flags & TINSEL_VIEWS_ADD)
+        HIP_TRY(hipMemcpy(r->viewsOut.get(), out_rgba_host, bytes, hipMemcpyHostToDevice));
+    if (views_enqueue(r, cameras, num_views, options, pass_begin, passes, flags, (float4*)r->viewsOut.get(), nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_rgba_host, r->viewsOut.get(), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tinsel_hip_plan_views(unsigned long long slot_limit, int width, int height, int passes, int num_views, int* out3)
+{
+    if (!out3 || width < 1 || height < 1 || passes < 1 || num_views < 1)
+        return fail("plan_views: bad arguments");
+    ViewsCut c;
+    if (!plan_views((size_t)slot_limit, width, height, passes, num_views, c))
+        return fail("plan_views: a batch would not fit the 32-bit slot index");
+    out3[0] = c.viewsPerBatch;
+    out3[1] = c.passesPerBatch;
+    out3[2] = (int)std::min<long long>(c.batches, 0x7fffffffll);
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

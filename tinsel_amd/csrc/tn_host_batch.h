@@ -627,7 +627,7 @@ struct BatchPlan
 };
 
 // perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve);
-// generate: the kernel that makes the batch's paths -- the camera's, or a query's (PK_GENERATE_RAYS / _GATHER), which run radiance_pipeline's choice;
+// generate: the kernel that makes the batch's paths -- the camera's, or a query's or a views call's (PK_GENERATE_RAYS / _GATHER / _VIEWS), which run radiance_pipeline's choice;
 // groups: a light-groups call's batch (tn_host_light_groups.h) -- the split pipeline whatever the setting, planned as a render's, with
 // k_shade's GROUPS twin as its shading kernel (k_shade_sorted has none)
 BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE, bool groups = false)
@@ -1175,8 +1175,8 @@ int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L
         *grid = std::max(1, std::min(*grid, (int)(seg_prefix_max_regions(r)/(kBlock/kWave))));
     if (cut_batch(p, L, a, slots, grid))
         return -1;
-    // (the plan says which paths: the camera's, a radiance query's -- k_generate_rays reads a.radiance and no camera -- or a gather
-    // query's: k_generate_gather reads a.gather)
+    // (the plan says which paths: the camera's, a radiance query's -- k_generate_rays reads a.radiance and no camera --, a gather
+    // query's -- k_generate_gather reads a.gather -- or a views call's: k_generate_views reads a.views, a.fp and its own seed table)
     ScopedTimer t(r, generate_timer(p.generate), st);
     a.grid = *grid;
     a.variant = p.generate;
@@ -1381,7 +1381,8 @@ struct CallerPaths
 {
     const RadianceJob* rays = nullptr;      // a radiance query's records (k_generate_rays, tn_host_radiance.h)
     const GatherJob* gather = nullptr;      // a gather query's points (k_generate_gather, tn_host_gather.h)
-    int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : PK_NONE; }
+    const ViewsJob* views = nullptr;        // a views call's cameras (k_generate_views, tn_host_views.h)
+    int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : views ? PK_GENERATE_VIEWS : PK_NONE; }
 };
 
 // What a side call over the camera's own paths replaces of a render's batch (light groups): the seed table k_generate reads, the statistics
@@ -1394,8 +1395,8 @@ struct TraceOverrides
 };
 
 // The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
-// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query -- the split or the paired pipeline
-// behind k_generate_rays / k_generate_gather, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
+// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query or a views call -- the split or the paired
+// pipeline behind k_generate_rays / k_generate_gather / k_generate_views, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
 int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
                 size_t slots, const CallerPaths* starts = nullptr, const TraceOverrides* over = nullptr)
 {
@@ -1413,6 +1414,8 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
         a.radiance = *starts->rays;
     if (starts && starts->gather)
         a.gather = *starts->gather;
+    if (starts && starts->views)
+        a.views = *starts->views;
     a.fp = fp;
     a.passSeeds = r->passSeeds;
     if (over)

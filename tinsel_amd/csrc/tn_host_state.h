@@ -205,6 +205,17 @@ struct tinsel_hip
     Event groupsFence;
     hipStream_t groupsFenceStream = nullptr;
     bool groupsFencePending = false;
+    // view batches (tinsel_hip_render_views*, tn_host_views.h): the radiance of a batch's paths by slot ([view][pass][pixel]), the cameras'
+    // table, the call's own seed table, the statistics its kernels count into (never read), the host entry's planes -- grown on demand,
+    // freed with the renderer -- and the event behind the last call's last launch, which a call on another stream waits for before it
+    // writes them
+    DevBuf<unsigned char> viewsRad, viewsOut;
+    DevBuf<ViewCamera> viewsCameras;
+    DevBuf<uint32_t> viewsSeeds;
+    DevBuf<unsigned long long> viewsStats;
+    Event viewsFence;
+    hipStream_t viewsFenceStream = nullptr;
+    bool viewsFencePending = false;
     // denoise stage (tinsel_hip_denoise*, tn_host_denoise.h): [0] the filter's colour input U, [1] its patch means, [2] (albedo, depth),
     // [3] the mean normal -- sized to the largest frame denoised -- the host entries' inputs (beauty, planes) and output on the device, and
     // the event behind the last call's last launch, which a call on another stream waits for before it writes them

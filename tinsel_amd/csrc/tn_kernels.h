@@ -13,6 +13,7 @@
 //   tn_radiance.h     k_generate_rays: radiance queries -- the split and paired pipelines entered with paths the caller starts
 //   tn_gather.h       k_generate_gather, k_gather_reduce, k_gather_sh_reduce: gather queries -- S paths per surface point drawn on the device, one mean (or its SH projection) per point
 //   tn_features.h     k_features: the first-hit features (albedo, normal, depth) of the camera's own paths, by slot, for the accumulate kernels
+//   tn_views.h        k_generate_views, k_views_accumulate: view batches -- many cameras' frames of one scene, generated and accumulated a batch of views at a time
 //   tn_ids.h          k_ids, k_ids_accumulate(_tiled), k_ids_rank: ID mattes -- the hit primitive of the camera's own paths, by slot, gathered into ranked per-pixel (id, weight) lists
 //   here              k_mega (one lane per whole path: the A/B arm), k_cost (its counters as a per-pixel map), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
 //
@@ -35,6 +36,7 @@
 #include "tn_gather.h"
 #include "tn_features.h"
 #include "tn_ids.h"
+#include "tn_views.h"
 
 namespace tn {
 

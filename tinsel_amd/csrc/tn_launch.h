@@ -97,7 +97,8 @@ namespace tn {
     X(PK_IDS,                   kBlock, 0, FEATURES, k_ids<false>)                                                  \
     X(PK_SHADE_GROUPS_MIXED,    kBlock, 0, SHADE_GROUPS, k_shade_groups<true, true>)                                \
     X(PK_SHADE_GROUPS_LDS,      kBlock, 0, SHADE_GROUPS, k_shade_groups<true>)                                      \
-    X(PK_SHADE_GROUPS,          kBlock, 0, SHADE_GROUPS, k_shade_groups<false>)
+    X(PK_SHADE_GROUPS,          kBlock, 0, SHADE_GROUPS, k_shade_groups<false>)                                     \
+    X(PK_GENERATE_VIEWS,        kBlock, 0, GENERATE_VIEWS, k_generate_views)
 
 enum PathKernel : int
 {
@@ -135,6 +136,7 @@ struct LaunchArgs
     int shOrder;                    // k_gather_sh_reduce: the highest band
     FeatureJob features;            // k_features, k_ids
     GroupState groups;              // k_shade_groups
+    ViewsJob views;                 // k_generate_views
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -155,6 +157,7 @@ struct LaunchArgs
 #define TN_ARGS_GATHER_SH_REDUCE a.ps.rad, a.gather, a.shOrder
 #define TN_ARGS_FEATURES a.scene, a.features, a.cam, a.fp, a.passSeeds, a.stackEntries
 #define TN_ARGS_SHADE_GROUPS TN_ARGS_SHADE, a.groups
+#define TN_ARGS_GENERATE_VIEWS a.ss, a.ctl, a.views, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
 
 // false: a.variant is not in the list (nothing is launched)
 inline bool launch_path_kernel(const LaunchArgs& a, hipStream_t st)

@@ -8,6 +8,7 @@
                                   [-features=features.npz] [-features_spp=N] [-denoise[=RADIUS]]
                                   [-mattes=FILE.npz] [-mattes_spp=N] [-mattes_slots=K]
                                   [-lightgroups=FILE.npz] [-lightgroups_spp=N]
+                                  [-views=FILE.npz -views_orbit=N] [-views_spp=S] [-views_center=X,Y,Z]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -63,6 +64,11 @@ the render's own passes [0, -lightgroups_spp) (default min(spp, 16), as -feature
 plane per group of tinsel_amd.default_light_groups -- every emitting primitive its own, the environment last.  The file holds `planes`
 [G, H, W, 4] float32 (accumulators: the render's clamp applies per plane), `group_of_primitive`, `env_group`, `names` and `passes`;
 tinsel_amd.relight mixes the planes.  Refused with what -features is refused with.
+-views=FILE.npz -views_orbit=N writes, beside a normal render, a turntable of the scene in one call (HipRenderer.views): N views of the
+scene's camera turned about the vertical through -views_center (default: what the camera sees at the centre of the frame, first_hit; the
+origin if that ray leaves the scene) by tinsel_amd.orbit_cameras, passes [0, -views_spp) (default min(spp, 16), as -features_spp) each --
+view 0 is the render's own first passes.  The file holds `planes` [N, H, W, 4] float32 (accumulators), `cameras` [N, 10] float32 (position,
+rotation x y z w, fov, shutter start and end), `center` and `passes`.  Refused with what -features is refused with.
 -denoise[=RADIUS] does a normal render, then takes the features of its passes [0, spp), denoises the accumulator with the library's
 defaults (HipRenderer.denoise: the feature-guided filter on linear radiance; RADIUS 1 .. 8 replaces the default search radius), runs the
 display stage on the denoised image (HipRenderer.present_image) and writes that to -out (a .pfm gets the denoised linear radiance).
@@ -78,7 +84,7 @@ import numpy as np
 
 from . import abi
 from .display import COST_CHANNELS, cost_heatmap, cost_mean, write_pfm, write_png
-from .renderer import Scene, create_gpu_renderer, default_light_groups, denoise_params, feature_images, gather_points
+from .renderer import Scene, camera_rays, create_gpu_renderer, default_light_groups, denoise_params, feature_images, gather_points, orbit_cameras
 
 FRAME_PASSES = 16          # numSamples of main.cpp:240
 
@@ -89,6 +95,7 @@ def parse_args(argv):
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
            "mattes": None, "mattes_spp": None, "mattes_slots": None, "lightgroups": None, "lightgroups_spp": None,
+           "views": None, "views_orbit": None, "views_spp": None, "views_center": None,
            "denoise": None, "over": {}}
     for a in argv[1:-1]:
         if a == "-denoise":
@@ -106,7 +113,7 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups", "views"):
             cfg[k] = v
         elif k == "denoise":
             cfg[k] = int(v)
@@ -116,6 +123,14 @@ def parse_args(argv):
             cfg[k] = int(v)
             if cfg[k] < 1:
                 raise SystemExit("-features_spp=%s: want 1 or more" % v)
+        elif k in ("views_orbit", "views_spp"):
+            cfg[k] = int(v)
+            if not 1 <= cfg[k] <= (abi.MAX_VIEWS if k == "views_orbit" else 1 << 20):
+                raise SystemExit("-%s=%s: want 1 or more%s" % (k, v, " and %d at most" % abi.MAX_VIEWS if k == "views_orbit" else ""))
+        elif k == "views_center":
+            cfg[k] = tuple(float(x) for x in v.split(","))
+            if len(cfg[k]) != 3:
+                raise SystemExit("-views_center=%s: want X,Y,Z" % v)
         elif k == "lightgroups_spp":
             cfg[k] = int(v)
             if cfg[k] < 1:
@@ -304,6 +319,26 @@ def lightgroups(r, scene, cam, opt, cfg):
     print("wrote %s: %dx%d, %d passes, %d groups (%s) in %.3fms" % (cfg["lightgroups"], opt.width, opt.height, n, len(names), ", ".join(names), ms))
 
 
+def views(r, cam, opt, cfg):
+    """-views: a turntable of N cameras about the vertical through the centre, the passes [0, S) of each in one call (tinsel_hip_render_views)"""
+    n = cfg["views_spp"] if cfg["views_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
+    center = cfg["views_center"]
+    if center is None:
+        t, primitive, _ = r.first_hit(cam, opt.width, opt.height)
+        j, i = opt.height//2, opt.width//2
+        center = (0.0, 0.0, 0.0)
+        if primitive[j, i] >= 0:
+            origin, directions = camera_rays(cam, opt.width, opt.height)
+            center = tuple(float(v) for v in origin + float(t[j, i])*directions[j, i])
+    cams = orbit_cameras(cam, center, cfg["views_orbit"])
+    ts = time.perf_counter()
+    planes = r.views(cams, opt, 0, n)
+    ms = (time.perf_counter() - ts)*1000.0
+    table = np.array([tuple(c.position) + tuple(c.rotation) + (c.fov, c.shutter_start, c.shutter_end) for c in cams], np.float32)
+    np.savez(cfg["views"], passes=np.int64(n), planes=planes, cameras=table, center=np.array(center, np.float32))
+    print("wrote %s: %d views of %dx%d, %d passes each, about (%g, %g, %g) in %.3fms" % ((cfg["views"], len(cams), opt.width, opt.height, n) + tuple(center) + (ms,)))
+
+
 def denoise(r, cam, opt, cfg, samples):
     """-denoise: the features of the render's own passes, the denoise stage on the accumulator, the display stage on its result;
     returns (presented image, denoised linear image)"""
@@ -335,6 +370,12 @@ def main(argv=None):
                                cfg["probes_at"]):
         raise SystemExit("-lightgroups writes the light groups of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
                          "-firsthit, -irradiance or -probes")
+    if bool(cfg["views"]) != bool(cfg["views_orbit"]) or ((cfg["views_spp"] or cfg["views_center"]) and not cfg["views"]):
+        raise SystemExit("-views=OUT.npz and -views_orbit=N go together; -views_spp and -views_center go with them")
+    if cfg["views"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                         cfg["probes_at"]):
+        raise SystemExit("-views writes a turntable beside a normal render: no batch mode, no -resume, -complexity, -firsthit, -irradiance "
+                         "or -probes")
     if cfg["denoise"] is not None and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                                        cfg["probes_at"]):
         raise SystemExit("-denoise filters a normal render with the guide buffers of its passes [0, N): no batch mode, no -resume, -complexity, "
@@ -400,6 +441,8 @@ def main(argv=None):
         mattes(r, cam, opt, cfg)
     if cfg["lightgroups"]:
         lightgroups(r, scene, cam, opt, cfg)
+    if cfg["views"]:
+        views(r, cam, opt, cfg)
     linear = None
     if cfg["denoise"] is not None:
         image, linear = denoise(r, cam, opt, cfg, samples)

@@ -108,6 +108,10 @@ def load_library():
     if hasattr(L, "tinsel_hip_render_light_groups"):   # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_render_light_groups.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, ci, vp]
         L.tinsel_hip_render_light_groups_device.argtypes = [vp, C.POINTER(abi.Camera), C.POINTER(abi.Options), C.c_uint32, ci, ci, vp, ci, vp, vp]
+    if hasattr(L, "tinsel_hip_render_views"):          # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_views.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
+        L.tinsel_hip_render_views_device.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
+        L.tinsel_hip_plan_views.argtypes = [C.c_ulonglong, ci, ci, ci, ci, C.POINTER(C.c_int)]
     if hasattr(L, "tinsel_hip_denoise"):               # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_denoise_params_init.restype = None
         L.tinsel_hip_denoise_params_init.argtypes = [C.POINTER(abi.DenoiseParams)]
@@ -203,6 +207,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_render_features", "tinsel_hip_render_features_device",
     "tinsel_hip_render_id_mattes", "tinsel_hip_render_id_mattes_device",
     "tinsel_hip_render_light_groups", "tinsel_hip_render_light_groups_device",
+    "tinsel_hip_render_views", "tinsel_hip_render_views_device", "tinsel_hip_plan_views",
     "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
 
@@ -438,6 +443,71 @@ def default_light_groups(scene, max_groups=abi.MAX_LIGHT_GROUPS):
         env_group = len(names)
         names.append("env")
     return table, env_group, names
+
+
+def _quat_mul(a, b):
+    """Hamilton product of two quaternions (x, y, z, w): the rotation b followed by the rotation a"""
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw*bx + ax*bw + ay*bz - az*by, aw*by - ax*bz + ay*bw + az*bx, aw*bz + ax*by - ay*bx + az*bw, aw*bw - ax*bx - ay*by - az*bz])
+
+
+def _quat_rotate(q, v):
+    """q*v*q^-1 for a unit quaternion (x, y, z, w)"""
+    u, w = np.asarray(q[:3], np.float64), float(q[3])
+    v = np.asarray(v, np.float64)
+    return v + 2.0*np.cross(u, np.cross(u, v) + w*v)
+
+
+def orbit_cameras(camera, center, count, axis=(0, 1, 0)):
+    """A turntable for HipRenderer.views: `count` copies of `camera` (abi.Camera), copy k rotated by 2*pi*k/count about the line through
+    `center` along `axis` -- the position is turned about the centre and the rotation with it, so the camera keeps looking at what it
+    looked at; fov and shutter are kept.  Copy 0 is the camera itself, bit for bit.  The arithmetic runs in float64 and is rounded to the
+    camera's float32 once."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("orbit_cameras: count must be >= 1")
+    n = np.asarray(axis, np.float64).reshape(3)
+    if not np.isfinite(n).all() or not np.linalg.norm(n) > 0.0:
+        raise ValueError("orbit_cameras: axis must be a finite non-zero vector")
+    n = n/np.linalg.norm(n)
+    c = np.asarray(center, np.float64).reshape(3)
+    p0, q0 = np.array(tuple(camera.position), np.float64), np.array(tuple(camera.rotation), np.float64)
+    out = (abi.Camera*count)()
+    for k in range(count):
+        cam = abi.Camera.from_buffer_copy(bytes(camera))
+        if k:
+            a = 2.0*np.pi*k/count
+            q = np.concatenate([n*np.sin(0.5*a), [np.cos(0.5*a)]])
+            p = c + _quat_rotate(q, p0 - c)
+            r = _quat_mul(q, q0)
+            cam.position = abi.Vec3(*(float(v) for v in p))
+            cam.rotation = abi.Vec4(*(float(v) for v in r))
+        out[k] = cam
+    return out
+
+
+def cube_cameras(position, shutter=(0.0, 0.0)):
+    """The six faces of a cube map around `position` for HipRenderer.views: cameras with a 90-degree field of view (render them at a
+    square frame size) looking along +x, -x, +y, -y, +z, -z, in that order.  The convention is the reference's camera (CameraSampler): a
+    camera looks along its local -z, its local +y is the top of the image and its local +x the right.  Up, the top of the image, is
+    world +y on the four side faces (+x, -x, +z, -z), world +z on the +y face and world -z on the -y face: the -z face is the identity
+    rotation, the other sides are it turned about y, and the +y / -y faces are it pitched up / down by 90 degrees about x."""
+    s = float(np.sqrt(0.5))
+    quats = [(0.0, -s, 0.0, s), (0.0, s, 0.0, s), (s, 0.0, 0.0, s), (-s, 0.0, 0.0, s), (0.0, 1.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0)]
+    out = (abi.Camera*6)()
+    for k, q in enumerate(quats):
+        out[k] = abi.Camera(abi.Vec3(*(float(v) for v in position)), abi.Vec4(*q), float(np.pi/2), float(shutter[0]), float(shutter[1]))
+    return out
+
+
+def plan_views(slot_limit, width, height, passes, num_views):
+    """tinsel_hip_plan_views: (views per batch, passes per batch, batches) of a views call under a limit of slot_limit path slots per batch
+    (host arithmetic only, no GPU needed)"""
+    L = load_library()
+    out = (C.c_int*3)()
+    _check(L.tinsel_hip_plan_views(int(slot_limit), int(width), int(height), int(passes), int(num_views), out), "tinsel_hip_plan_views")
+    return tuple(int(v) for v in out)
 
 
 def relight(planes, gains):
@@ -885,6 +955,42 @@ class HipRenderer:
                 raise ValueError("light_groups: a C-contiguous float32 array %s is expected" % (shape,))
             _check(self._L.tinsel_hip_render_light_groups(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), G,
                                                           _host_ptr(table), env, out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_light_groups")
+        return out
+
+    def views(self, cameras, options, pass_begin=0, passes=1, out=None, add=False, singly=False):
+        """View batches (tinsel_hip_render_views*): the frames of many cameras on the resident scene in one call -- float32 [V, H, W, 4],
+        plane v the accumulator render() gives for cameras[v] from a zeroed accumulator at pass index pass_begin after `passes` passes, bit
+        for bit.  `cameras`: a sequence of abi.Camera or a ctypes array of them (orbit_cameras and cube_cameras make one).  add: the passes
+        are added to what `out` holds instead of starting every plane from zero; singly: one accumulate launch per view instead of one per
+        batch of views (the same bits).  `out`: a contiguous float32 torch tensor [V, H, W, 4] on this renderer's device takes the device
+        entry on torch's current stream, not waited for; a numpy array of that shape is filled by the host entry.  Needs init() at the
+        options' frame size; leaves the accumulator, pass index, pass seeds, statistics and tuning as they were."""
+        if not isinstance(cameras, C.Array):
+            cameras = list(cameras)
+            cameras = (abi.Camera*len(cameras))(*cameras)
+        V = len(cameras)
+        cams = C.cast(cameras, C.POINTER(abi.Camera))
+        flags = (abi.VIEWS_ADD if add else 0) | (abi.VIEWS_ACCUMULATE_SINGLY if singly else 0)
+        H, W = int(options.height), int(options.width)
+        shape = (V, H, W, 4)
+        if _is_tensor(out):
+            import torch
+            if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError("views: a contiguous float32 tensor %s on the GPU is expected" % (shape,))
+            if out.device.index != self.device:
+                raise ValueError("views: the tensor is on %s, the renderer on device %d" % (out.device, self.device))
+            _check(self._L.tinsel_hip_render_views_device(self._h, cams, V, C.byref(options), int(pass_begin), int(passes), flags,
+                                                          out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "tinsel_hip_render_views_device")
+        else:
+            if out is None:
+                if add:
+                    raise ValueError("views: add=True needs the planes to add to (out)")
+                out = np.zeros(shape, np.float32)
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("views: a C-contiguous float32 array %s is expected" % (shape,))
+            _check(self._L.tinsel_hip_render_views(self._h, cams, V, C.byref(options), int(pass_begin), int(passes), flags,
+                                                   out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_views")
         return out
 
     def id_mattes(self, camera, options, pass_begin=0, passes=1, slots=6, out=None):
