@@ -810,7 +810,10 @@ long long tinsel_hip_read_batch_radiance(tinsel_hip* r, float* out_rgbx, unsigne
  * inline functions.  op: 0 Random, 1 CameraSampler::GenerateRay, 2 BSDFEval+BSDFPdf, 3 BSDFSample,
  * 4 PrimitiveIntersect, 5 PrimitiveSample, 6 ProbeSample/ProbePdf/Sky::Eval, 7 libm restatements,
  * 8 display-stage functions (row layouts: tn_kernels.h LeafOp).
- * `index` = primitive (its material for ops 2,3). */
+ * `index` = primitive (its material for ops 2,3).
+ * The hook follows the renderer's arithmetic arm: the exact build's functions by default, the tolerance build's (the same kernel
+ * compiled from tinsel_fast.hip) after tinsel_hip_set_arithmetic(r, TINSEL_ARITH_FAST) -- what tests/test_gpu_fast_leaf.py tables
+ * against a float64 statement of the same functions (tests/shade_f64.py).  Random (op 0) is integer arithmetic: the same bits in both. */
 int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, int in_stride, const uint32_t* seeds,
                     float* out, int out_stride, const tinsel_camera* camera, int width, int height);
 

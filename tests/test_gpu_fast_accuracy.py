@@ -22,8 +22,9 @@ RAY QUERIES (trace_rays).  Rays per scene: the sets of tests/test_gpu_ray_query.
      query runs k_query / k_query_refill whatever the pipeline, so the pipelines add no kernel here (every record is bit-equal); the
      tuning arms change where the scene lives and which walk k_query takes.
 RADIANCE QUERIES, per path and by depth; FEATURE PLANES and GATHERS: see the sections below.  The tolerance build's k_walk, k_walk_rays,
-k_swalk, k_step, k_shade* and k_mega are held by test_paths_under_every_pipeline alone (depth 2, three scenes).  NOT covered: the
-tolerance build's k_leaf -- tinsel_hip_leaf launches the exact arm's only.
+k_swalk, k_step, k_shade* and k_mega are held by test_paths_under_every_pipeline alone (depth 2, three scenes).  The build's leaf
+functions -- BSDF, samplers, camera ray, light sample, probe, transcendentals -- have their own tables, function by function against a
+float64 statement: tests/test_gpu_fast_leaf.py.
 
 Measured figures: profiles/fast_arm_accuracy.md."""
 import functools

@@ -31,3 +31,11 @@ extern "C" int tinsel_fast_prepare_path_kernels(int sharedMemLimit, const char**
 }
 
 extern "C" unsigned tinsel_fast_launch_args_size(void) { return (unsigned)sizeof(tn_fast::LaunchArgs); }
+
+// the test hook's kernel of THIS build (tinsel_hip_leaf after tinsel_hip_set_arithmetic(TINSEL_ARITH_FAST)): enqueues tn_fast::k_leaf on `stream`
+extern "C" void tinsel_fast_launch_leaf(const void* leafArgs, void* stream)
+{
+    tn_fast::launch_leaf(*static_cast<const tn_fast::LeafArgs*>(leafArgs), (hipStream_t)stream);
+}
+
+extern "C" unsigned tinsel_fast_leaf_args_size(void) { return (unsigned)sizeof(tn_fast::LeafArgs); }

@@ -77,13 +77,23 @@ TN_D float smith_ggx(float NDotv, float alphaG)    // disney.h:71-76
     return rcpf_cr(NDotv + sqrtf_cr(a + b - a*b));
 }
 
+// etaI/etaT as Fr and BSDFSample take it.  The tolerance build divides by multiplying with v_rcp_f32, and 1.5f*rcp(1.5f) is 1 + 2^-23, not 1: an
+// interface between EQUAL indices (a surface met inside a medium of its own index) became one with a critical angle -- SinThetaT2 > 1 below
+// VDotN = 5e-4, so F = 1 and a finite pdf where the reference computes 0/0 and drops the sample (VDotN == 0), and Refract() refused the straight
+// line.  Found by tests/test_gpu_fast_leaf.py's edge rows; equal indices have the ratio 1 in this build too.
+#if TN_FAST
+TN_D float index_ratio(float a, float b) { return a == b ? 1.0f : a/b; }
+#else
+TN_D float index_ratio(float a, float b) { return a/b; }
+#endif
+
 TN_D float fresnel_dielectric(float VDotN, float etaI, float etaT)     // Fr, disney.h:79-96
 {
-    float SinThetaT2 = sqr(etaI/etaT)*(1.0f - VDotN*VDotN);
+    float SinThetaT2 = sqr(index_ratio(etaI, etaT))*(1.0f - VDotN*VDotN);
     if (SinThetaT2 > 1.0f)
         return 1.0f;
     float LDotN = sqrtf_cr(1.0f - SinThetaT2);
-    float eta = etaT/etaI;
+    float eta = index_ratio(etaT, etaI);
     float r1 = (VDotN - eta*LDotN)/(VDotN + eta*LDotN);
     float r2 = (LDotN - eta*VDotN)/(LDotN + eta*VDotN);
     return 0.5f*(sqr(r1) + sqr(r2));
@@ -160,7 +170,7 @@ TN_D void bsdf_sample(const Mat& mat, float etaI, float etaO, V3 U, V3 Vt, V3 N,
         }
         else
         {
-            float eta = etaI/etaO;
+            float eta = index_ratio(etaI, etaO);
             if (refract(view, N, eta, light))   // disney.h:209-219
             {
                 type = kSpecular;

@@ -864,6 +864,8 @@ int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, in
     if ((op == kLeafBsdfEval || op == kLeafBsdfSample || op == kLeafPrimIntersect || op == kLeafPrimSample) &&
         (index < 0 || index >= r->scene.numPrims))
         return fail("leaf: primitive index out of range");
+    if (r->arith == TINSEL_ARITH_FAST && tinsel_fast_leaf_args_size() != sizeof(LeafArgs))
+        return fail("leaf: the two builds of k_leaf disagree on the argument record");
     HIP_TRY(hipSetDevice(r->device));
     DevBuf<float> dIn, dOut;
     DevBuf<uint32_t> dSeeds;
@@ -877,8 +879,21 @@ int tinsel_hip_leaf(tinsel_hip* r, int op, int index, int n, const float* in, in
         return fail("leaf: seed upload failed");
     if (dOut.alloc((size_t)n*out_stride))
         return fail("leaf: output allocation failed");
-    hipLaunchKernelGGL(k_leaf, dim3((n + kBlock - 1)/kBlock), dim3(kBlock), stack_bytes(r), nullptr, r->scene, op, index, n, dIn.get(), in_stride,
-                       dSeeds.get(), dOut.get(), out_stride, cam, r->stackNeed);
+    LeafArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene = r->scene;
+    a.op = op; a.index = index; a.n = n;
+    a.in = dIn.get(); a.inStride = in_stride;
+    a.seeds = dSeeds.get();
+    a.out = dOut.get(); a.outStride = out_stride;
+    a.cam = cam;
+    a.stackEntries = r->stackNeed;
+    a.ldsBytes = (uint32_t)stack_bytes(r);
+    // the renderer's arm (tinsel_hip_set_arithmetic): this translation unit's k_leaf, or the tolerance build's
+    if (r->arith == TINSEL_ARITH_FAST)
+        tinsel_fast_launch_leaf(&a, nullptr);
+    else
+        launch_leaf(a, nullptr);
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess)
         return fail("leaf: kernel failed");
     if (hipMemcpy(out, dOut.get(), sizeof(float)*(size_t)n*out_stride, hipMemcpyDeviceToHost) != hipSuccess)

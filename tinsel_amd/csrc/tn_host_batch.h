@@ -208,6 +208,8 @@ size_t stack_bytes(const tinsel_hip* r) { return stack_bytes(r, r->stackNeed); }
 extern "C" int tinsel_fast_launch_path_kernel(const void* launchArgs, void* stream);
 extern "C" int tinsel_fast_prepare_path_kernels(int sharedMemLimit, const char** first);
 extern "C" unsigned tinsel_fast_launch_args_size(void);
+extern "C" void tinsel_fast_launch_leaf(const void* leafArgs, void* stream);
+extern "C" unsigned tinsel_fast_leaf_args_size(void);
 
 // Raises the dynamic-LDS limit of every kernel that needs more than the default launch limit, for both arithmetic arms (tn_launch.h).  Called by
 // tinsel_hip_create, which falls back to planning within 64 KB per workgroup when the runtime refuses a kernel (r->prepRefused: "kernel name (arm)").

@@ -355,4 +355,26 @@ __global__ __launch_bounds__(kBlock) void k_leaf(DevScene scIn, int op, int inde
     }
 }
 
+// One k_leaf launch as a plain argument block, so that the host can hand it to either arm's build of the kernel (tinsel_hip_leaf launches
+// this translation unit's, or tinsel_fast.hip's through tinsel_fast_launch_leaf, after the renderer's arithmetic arm).  Device pointers.
+struct LeafArgs
+{
+    DevScene scene;
+    int op, index, n;
+    const float* in;
+    int inStride;
+    const uint32_t* seeds;
+    float* out;
+    int outStride;
+    CameraParams cam;
+    int stackEntries;
+    uint32_t ldsBytes;              // dynamic LDS of the launch
+};
+
+inline void launch_leaf(const LeafArgs& a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_leaf, dim3((unsigned)((a.n + kBlock - 1)/kBlock)), dim3(kBlock), a.ldsBytes, st, a.scene, a.op, a.index, a.n, a.in, a.inStride,
+                       a.seeds, a.out, a.outStride, a.cam, a.stackEntries);
+}
+
 } // namespace tn

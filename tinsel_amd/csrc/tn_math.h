@@ -519,8 +519,20 @@ TN_D float m_atan2f(float y, float x)
 TN_D void m_sincosf(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
 TN_D float m_sinf(float x) { return ::sinf(x); }
 TN_D float m_cosf(float x) { return ::cosf(x); }
-TN_D float m_expf(float x) { return ::expf(x); }
-template <class Tab> TN_D float m_expf_tab(float x, const Tab&) { return ::expf(x); }
+// expf: under this build's flags ::expf is v_exp_f32(x*log2e) with the product in ONE float, and the product's rounding, |x| 2^-24, is the
+// relative error of the result (2.7e-6 at x = -80: tests/test_gpu_fast_leaf.py's table found it 48x the exact arm's at the 99th percentile).
+// Here the integer part n of the product goes through v_ldexp_f32 and the rest is ONE FMA of the exact product, x*log2e - n, plus log2e's
+// own low part: v_exp_f32 sees [-0.5, 0.5] and its 1 ulp is the error.  (Written as fmaf: under -ffp-contract=fast a `t - n` of the rounded
+// product t is contracted to this FMA anyway, and a separate correction for t's rounding would then count it twice.)  The two selects keep
+// (int)n in range and pass a NaN through: exp(-104) is below the smallest denormal, exp(89) above FLT_MAX.
+TN_D float m_expf(float x)
+{
+    x = x < -104.0f ? -104.0f : x;
+    x = x > 89.0f ? 89.0f : x;
+    const float n = rintf(x*1.442695041f);
+    return ldexpf(exp2f(fmaf(x, 1.442695041f, -n) + x*1.925963033e-8f), (int)n);
+}
+template <class Tab> TN_D float m_expf_tab(float x, const Tab&) { return m_expf(x); }
 TN_D float m_logf(float x) { return __logf(x); }
 TN_D float m_acosf(float x) { return ::acosf(x); }
 TN_D float m_atan2f(float y, float x) { return ::atan2f(y, x); }

@@ -1300,7 +1300,8 @@ class HipRenderer:
         return out[:, :3].reshape(passes, height, width, 3).copy()
 
     def leaf(self, op, index, n, out_stride, rows=None, seeds=None, camera=None, width=0, height=0):
-        """Test hook: device leaf function `op` on `n` rows (see include/tinsel_hip.h: tinsel_hip_leaf)."""
+        """Test hook: device leaf function `op` on `n` rows (see include/tinsel_hip.h: tinsel_hip_leaf), of the arithmetic arm in force
+        (set_arithmetic): the exact build's by default, the tolerance build's after set_arithmetic(abi.ARITH_FAST)."""
         out = np.zeros((n, out_stride), np.float32)
         rp, rs = None, 0
         if rows is not None:
