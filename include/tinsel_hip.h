@@ -607,6 +607,54 @@ int tinsel_hip_render_views_device(tinsel_hip* r, const tinsel_camera* cameras, 
  * small the limit.  Returns -1 for a bad argument and where a batch would have 2^32 - 1 slots or more. */
 int tinsel_hip_plan_views(unsigned long long slot_limit, int width, int height, int passes, int num_views, int* out3);
 
+/* Sample maps: a per-pixel pass count in one call -- a crop or region re-render whose pixels equal the full frame's, more samples where
+ * the image is still noisy and none where it has converged, foveated budgets, the few pixels around a firefly -- where every other entry
+ * traces whole frames, passes x W x H paths.  The entry is the mechanism only: the caller says how many passes each pixel gets; statistics,
+ * error estimates and stopping rules live in the caller's code on top of it.
+ * SAMPLES TRACED.  Pixel q = (i, j) gets the samples of levels t = 0 .. counts[j*W + i] - 1.  The sample of (q, t) is exactly the path a
+ * render starts for pixel q in pass pass_begin + t: its camera sample is seeded i + j*W + pass_seed(pass_begin + t), and it is traced with
+ * options->max_depth and the renderer's Russian-roulette setting.
+ * HOW THEY ARE ADDED.  out[H][W][4] starts from zero, or with TINSEL_SAMPLES_ADD from what it holds, and receives AddSample of exactly
+ * those samples with options->filter and options->clamp, each receiving pixel's adds in level order, then in raster order of the
+ * generating pixels.  A sample that does not exist is skipped -- it is not added as zero: the weight channel does not see it.
+ * WHAT FOLLOWS.  A uniform map n gives the accumulator of n passes from zero at pass_begin, bit for bit (tinsel_hip_render_views with this
+ * one camera).  A uniform call of a passes followed by a map c at pass_begin + a with TINSEL_SAMPLES_ADD equals the single map a + c at
+ * pass_begin.  An all-zero map zeroes `out` (with the flag: leaves it untouched); so does options->max_depth < 1.
+ * The counts are a HOST array in both entries, read before the call returns (a device-resident map is not offered).
+ * The paths run the split or the paired pipeline, as a radiance query's do, under every tinsel_hip_set_pipeline setting:
+ * k_generate_samples in the place of k_generate -- timed under the name "k_generate" in tinsel_hip_kernel_times --, then one
+ * "k_accumulate" per batch (k_samples_accumulate), whose tiles run to the largest count among their own candidates and no further.  A
+ * batch is a run of consecutive levels, as tinsel_hip_plan_sample_map states it for the renderer's batch_paths; within a batch the slot
+ * of (q, t) is the number of samples of the pixels before q plus t - t0 (pixel-major, compact).  Every pixel's adds stay in level order
+ * across batches, so the cut shows nowhere.
+ * The seeds, offsets, radiance and statistics are the call's own: the accumulator, the pass index, the renderer's seed table,
+ * tinsel_hip_stats, the tuning and look-ahead work in flight are left as they were, and a render, a sample-map call and the render that
+ * follows give the images of the two renders alone.  A group has no entry.
+ * Returns -1 before anything is launched or written for: a null argument, another mode than TINSEL_MODE_PATHTRACE, a frame size that does
+ * not match the last tinsel_hip_init, a sharded renderer (world > 1), TINSEL_ARITH_FAST (the contract is a bit contract), a moved
+ * primitive without tinsel_hip_rebuild_scene, unknown flag bits, for the device entry an out_dev that is not 16-byte aligned, a batch of
+ * 2^32 - 1 slots or more, and a filter whose footprint the tiled accumulate kernels do not hold (widths above 2: there is no untiled
+ * masked accumulate kernel, and the error text says so).
+ * Memory, kept until tinsel_hip_destroy: 16 bytes per path of a batch, 4 bytes per pixel (the offsets), 4 bytes per level (the
+ * seeds), and for the host entry W*H*16 bytes of plane. */
+#define TINSEL_SAMPLE_MAP_MAX 65535     /* the largest count of a pixel: what a uint16_t holds */
+#define TINSEL_SAMPLES_ADD 1u           /* add to what `out` holds instead of starting from zero */
+
+/* host array of W*H*4 floats (read first with TINSEL_SAMPLES_ADD); returns when it is written */
+int tinsel_hip_render_sample_map(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                 uint32_t pass_begin, const uint16_t* counts, unsigned flags, float* out_rgba_host);
+/* device array, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for -- except between the batches of a
+ * map that needs several: each batch's offsets are uploaded when the batch before has run.  The stream waits, on the device, for what
+ * the renderer's path buffers still serve. */
+int tinsel_hip_render_sample_map_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                        uint32_t pass_begin, const uint16_t* counts, unsigned flags, float* out_rgba_dev, void* stream);
+/* The batch cut of a sample-map call, host arithmetic only (no GPU needed): out4 = { levels per batch, batches, total paths, largest
+ * count } for a limit of slot_limit path slots per batch (the renderer's batch_paths).  Levels are cut into runs of
+ * L = max(1, floor(min(slot_limit, 2^32 - 2)/(W*H))) consecutive levels -- a bound that needs no histogram of the map --, batches =
+ * ceil(largest count / L); the batch [t0, t0 + L) holds sum over q of clamp(counts[q] - t0, 0, L) paths.  Returns -1 for a bad argument
+ * and where one level, W*H slots, would reach 2^32 - 1 (the counts are not read then). */
+int tinsel_hip_plan_sample_map(unsigned long long slot_limit, int width, int height, const uint16_t* counts, unsigned long long* out4);
+
 /* Feature-guided denoise: a joint non-local-means filter on LINEAR radiance, in front of the display stage, guided by the planes above.
  * With features == 0 and demodulate == 0 it is NonLocalMeansFilter (nlm.cpp:35-77) on the normalised colour, bit for bit, falloff =
  * k_color and AverageFilter's radius = patch_radius; the guide terms add to the exponent.  Everything is fp32, one rounding per

@@ -174,6 +174,13 @@ MAX_LIGHT_GROUPS = 8
 # tinsel_hip_render_views*: the most views a call takes, and its flags
 MAX_VIEWS = 4096
 VIEWS_ADD, VIEWS_ACCUMULATE_SINGLY = 1, 2
+# tinsel_hip_render_sample_map*: the largest count of a pixel (a uint16), its flag, and the entries' signatures -- renderer, camera,
+# options, pass_begin, counts (host uint16 [H*W]), flags, out (, stream); slot_limit, width, height, counts, out4
+SAMPLE_MAP_MAX = 65535
+SAMPLES_ADD = 1
+RENDER_SAMPLE_MAP_ARGTYPES = [C.c_void_p, C.POINTER(Camera), C.POINTER(Options), C.c_uint32, C.c_void_p, C.c_uint, C.c_void_p]
+RENDER_SAMPLE_MAP_DEVICE_ARGTYPES = RENDER_SAMPLE_MAP_ARGTYPES + [C.c_void_p]
+PLAN_SAMPLE_MAP_ARGTYPES = [C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_ulonglong)]
 
 
 class DenoiseParams(C.Structure):

@@ -350,6 +350,60 @@ int tinsel_hip_plan_views(unsigned long long slot_limit, int width, int height, 
     return 0;
 }
 
+// Sample maps (tn_samples.h, tn_host_samples.h): a per-pixel pass count in one call, k_generate_samples on compact slots in front of a
+// radiance query's pipeline and one masked accumulate launch per batch of levels behind it.  Own seeds, own radiance, own statistics
+// block, as a views call: nothing of the renderer's frame state is written.
+int tinsel_hip_render_sample_map_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin,
+                                        const uint16_t* counts, unsigned flags, float* out_rgba_dev, void* stream)
+{
+    const char* const who = "render_sample_map_device";
+    if (samples_args(r, camera, options, counts, flags, out_rgba_dev, who))
+        return -1;
+    if (query_arrays({ { out_rgba_dev, (size_t)r->width*r->height*sizeof(float4) } }, who) || query_ready(r, who))
+        return -1;
+    return samples_enqueue(r, camera, options, pass_begin, counts, flags, (float4*)out_rgba_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_sample_map(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin,
+                                 const uint16_t* counts, unsigned flags, float* out_rgba_host)
+{
+    const char* const who = "render_sample_map";
+    if (samples_args(r, camera, options, counts, flags, out_rgba_host, who) || query_ready(r, who))
+        return -1;
+    const size_t npix = (size_t)r->width*r->height, bytes = npix*sizeof(float4);
+    // (nothing to trace: the plane is zeroed, or with TINSEL_SAMPLES_ADD left untouched, without a trip to the device)
+    if (options->max_depth < 1 || std::all_of(counts, counts + npix, [](uint16_t c) { return c == 0; }))
+    {
+        if (!(flags & TINSEL_SAMPLES_ADD))
+            memset(out_rgba_host, 0, bytes);
+        return 0;
+    }
+    if (query_buffer(r->samplesOut, bytes))
+        return -1;
+    // (the staging plane is the host entry's alone, and it returns when it has been read: nothing in flight touches it)
+    if (flags & TINSEL_SAMPLES_ADD)
+        HIP_TRY(hipMemcpy(r->samplesOut.get(), out_rgba_host, bytes, hipMemcpyHostToDevice));
+    if (samples_enqueue(r, camera, options, pass_begin, counts, flags, (float4*)r->samplesOut.get(), nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_rgba_host, r->samplesOut.get(), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tinsel_hip_plan_sample_map(unsigned long long slot_limit, int width, int height, const uint16_t* counts, unsigned long long* out4)
+{
+    if (!out4 || !counts || width < 1 || height < 1)
+        return fail("plan_sample_map: bad arguments");
+    SamplesCut c;
+    if (!plan_samples(slot_limit, width, height, counts, c))
+        return fail("plan_sample_map: a batch would not fit the 32-bit slot index");
+    out4[0] = c.levels;
+    out4[1] = c.batches;
+    out4[2] = c.paths;
+    out4[3] = c.most;
+    return 0;
+}
+
 float* tinsel_hip_accum_device_ptr(tinsel_hip* r) { return r ? (float*)r->accum : nullptr; }
 
 int tinsel_hip_read_accum(tinsel_hip* r, float* out_rgba)

@@ -629,7 +629,7 @@ struct BatchPlan
 };
 
 // perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve);
-// generate: the kernel that makes the batch's paths -- the camera's, or a query's or a views call's (PK_GENERATE_RAYS / _GATHER / _VIEWS), which run radiance_pipeline's choice;
+// generate: the kernel that makes the batch's paths -- the camera's, or a query's, a views call's or a sample map's (PK_GENERATE_RAYS / _GATHER / _VIEWS / _SAMPLES), which run radiance_pipeline's choice;
 // groups: a light-groups call's batch (tn_host_light_groups.h) -- the split pipeline whatever the setting, planned as a render's, with
 // k_shade's GROUPS twin as its shading kernel (k_shade_sorted has none)
 BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE, bool groups = false)
@@ -1178,7 +1178,8 @@ int cut_and_generate(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L
     if (cut_batch(p, L, a, slots, grid))
         return -1;
     // (the plan says which paths: the camera's, a radiance query's -- k_generate_rays reads a.radiance and no camera --, a gather
-    // query's -- k_generate_gather reads a.gather -- or a views call's: k_generate_views reads a.views, a.fp and its own seed table)
+    // query's -- k_generate_gather reads a.gather --, a views call's -- k_generate_views reads a.views, a.fp and its own seed table -- or a
+    // sample map's: k_generate_samples reads a.samples, a.cam, a.fp and its own seed table)
     ScopedTimer t(r, generate_timer(p.generate), st);
     a.grid = *grid;
     a.variant = p.generate;
@@ -1384,7 +1385,8 @@ struct CallerPaths
     const RadianceJob* rays = nullptr;      // a radiance query's records (k_generate_rays, tn_host_radiance.h)
     const GatherJob* gather = nullptr;      // a gather query's points (k_generate_gather, tn_host_gather.h)
     const ViewsJob* views = nullptr;        // a views call's cameras (k_generate_views, tn_host_views.h)
-    int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : views ? PK_GENERATE_VIEWS : PK_NONE; }
+    const SamplesJob* samples = nullptr;    // a sample map's offsets, beside the camera (k_generate_samples, tn_host_samples.h)
+    int generate() const { return rays ? PK_GENERATE_RAYS : gather ? PK_GENERATE_GATHER : views ? PK_GENERATE_VIEWS : samples ? PK_GENERATE_SAMPLES : PK_NONE; }
 };
 
 // What a side call over the camera's own paths replaces of a render's batch (light groups): the seed table k_generate reads, the statistics
@@ -1397,8 +1399,8 @@ struct TraceOverrides
 };
 
 // The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
-// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query or a views call -- the split or the paired
-// pipeline behind k_generate_rays / k_generate_gather / k_generate_views, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
+// are the camera's (`cam`, fp's passes), or the caller's (`starts`: a radiance or a gather query, a views call or a sample map -- the split or the paired
+// pipeline behind k_generate_rays / k_generate_gather / k_generate_views / k_generate_samples, p.generate; the fused kernel and k_mega generate the camera's paths themselves).
 int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hipStream_t st, const CameraParams* cam, const FrameParams& fp, float4* rad,
                 size_t slots, const CallerPaths* starts = nullptr, const TraceOverrides* over = nullptr)
 {
@@ -1418,6 +1420,8 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
         a.gather = *starts->gather;
     if (starts && starts->views)
         a.views = *starts->views;
+    if (starts && starts->samples)
+        a.samples = *starts->samples;
     a.fp = fp;
     a.passSeeds = r->passSeeds;
     if (over)

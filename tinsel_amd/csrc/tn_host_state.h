@@ -216,6 +216,16 @@ struct tinsel_hip
     Event viewsFence;
     hipStream_t viewsFenceStream = nullptr;
     bool viewsFencePending = false;
+    // sample maps (tinsel_hip_render_sample_map*, tn_host_samples.h): the radiance of a batch's paths by compact slot, the batch's offset
+    // table (W*H + 1 entries, uploaded per batch), the call's own seed table, the statistics its kernels count into (never read), the host
+    // entry's plane -- grown on demand, freed with the renderer -- and the event behind the last call's last launch, which a call on
+    // another stream waits for before it writes them
+    DevBuf<unsigned char> samplesRad, samplesOut;
+    DevBuf<uint32_t> samplesOff, samplesSeeds;
+    DevBuf<unsigned long long> samplesStats;
+    Event samplesFence;
+    hipStream_t samplesFenceStream = nullptr;
+    bool samplesFencePending = false;
     // denoise stage (tinsel_hip_denoise*, tn_host_denoise.h): [0] the filter's colour input U, [1] its patch means, [2] (albedo, depth),
     // [3] the mean normal -- sized to the largest frame denoised -- the host entries' inputs (beauty, planes) and output on the device, and
     // the event behind the last call's last launch, which a call on another stream waits for before it writes them

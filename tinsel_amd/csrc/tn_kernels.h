@@ -14,6 +14,7 @@
 //   tn_gather.h       k_generate_gather, k_gather_reduce, k_gather_sh_reduce: gather queries -- S paths per surface point drawn on the device, one mean (or its SH projection) per point
 //   tn_features.h     k_features: the first-hit features (albedo, normal, depth) of the camera's own paths, by slot, for the accumulate kernels
 //   tn_views.h        k_generate_views, k_views_accumulate: view batches -- many cameras' frames of one scene, generated and accumulated a batch of views at a time
+//   tn_samples.h      k_generate_samples, k_samples_accumulate: sample maps -- a per-pixel pass count on compact slots, accumulated to each tile's own level count
 //   tn_ids.h          k_ids, k_ids_accumulate(_tiled), k_ids_rank: ID mattes -- the hit primitive of the camera's own paths, by slot, gathered into ranked per-pixel (id, weight) lists
 //   here              k_mega (one lane per whole path: the A/B arm), k_cost (its counters as a per-pixel map), k_pass_seeds, k_normals (eNormals), k_leaf (test hook)
 //
@@ -37,6 +38,7 @@
 #include "tn_features.h"
 #include "tn_ids.h"
 #include "tn_views.h"
+#include "tn_samples.h"
 
 namespace tn {
 

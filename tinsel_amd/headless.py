@@ -9,6 +9,7 @@
                                   [-mattes=FILE.npz] [-mattes_spp=N] [-mattes_slots=K]
                                   [-lightgroups=FILE.npz] [-lightgroups_spp=N]
                                   [-views=FILE.npz -views_orbit=N] [-views_spp=S] [-views_center=X,Y,Z]
+                                  [-samplemap=COUNTS.npy -samplemap_out=FILE.npz] [-samplemap_begin=N]
                                   scene.pack
 
 Conventions kept from main.cpp:
@@ -69,6 +70,11 @@ scene's camera turned about the vertical through -views_center (default: what th
 origin if that ray leaves the scene) by tinsel_amd.orbit_cameras, passes [0, -views_spp) (default min(spp, 16), as -features_spp) each --
 view 0 is the render's own first passes.  The file holds `planes` [N, H, W, 4] float32 (accumulators), `cameras` [N, 10] float32 (position,
 rotation x y z w, fov, shutter start and end), `center` and `passes`.  Refused with what -features is refused with.
+-samplemap=COUNTS.npy -samplemap_out=FILE.npz writes, beside a normal render, the plane of a sample-map call (HipRenderer.sample_map):
+COUNTS.npy holds a uint16 array [H, W], the number of passes every pixel gets -- pixel (i, j) the samples a render gives it in the passes
+-samplemap_begin (default 0) .. -samplemap_begin + COUNTS[j, i] - 1, and none beyond; tinsel_amd.crop_sample_map makes a crop.  The file
+holds `plane` [H, W, 4] float32 (an accumulator: divide by the weight channel), `counts` and `pass_begin`.  Refused with what -features is
+refused with.
 -denoise[=RADIUS] does a normal render, then takes the features of its passes [0, spp), denoises the accumulator with the library's
 defaults (HipRenderer.denoise: the feature-guided filter on linear radiance; RADIUS 1 .. 8 replaces the default search radius), runs the
 display stage on the denoised image (HipRenderer.present_image) and writes that to -out (a .pfm gets the denoised linear radiance).
@@ -96,6 +102,7 @@ def parse_args(argv):
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
            "mattes": None, "mattes_spp": None, "mattes_slots": None, "lightgroups": None, "lightgroups_spp": None,
            "views": None, "views_orbit": None, "views_spp": None, "views_center": None,
+           "samplemap": None, "samplemap_out": None, "samplemap_begin": None,
            "denoise": None, "over": {}}
     for a in argv[1:-1]:
         if a == "-denoise":
@@ -113,7 +120,8 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups", "views"):
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups", "views", "samplemap",
+                   "samplemap_out"):
             cfg[k] = v
         elif k == "denoise":
             cfg[k] = int(v)
@@ -127,6 +135,10 @@ def parse_args(argv):
             cfg[k] = int(v)
             if not 1 <= cfg[k] <= (abi.MAX_VIEWS if k == "views_orbit" else 1 << 20):
                 raise SystemExit("-%s=%s: want 1 or more%s" % (k, v, " and %d at most" % abi.MAX_VIEWS if k == "views_orbit" else ""))
+        elif k == "samplemap_begin":
+            cfg[k] = int(v)
+            if not 0 <= cfg[k] < 1 << 32:
+                raise SystemExit("-samplemap_begin=%s: want a pass index, 0 or more" % v)
         elif k == "views_center":
             cfg[k] = tuple(float(x) for x in v.split(","))
             if len(cfg[k]) != 3:
@@ -339,6 +351,20 @@ def views(r, cam, opt, cfg):
     print("wrote %s: %d views of %dx%d, %d passes each, about (%g, %g, %g) in %.3fms" % ((cfg["views"], len(cams), opt.width, opt.height, n) + tuple(center) + (ms,)))
 
 
+def samplemap(r, cam, opt, cfg):
+    """-samplemap: the plane of one sample-map call (tinsel_hip_render_sample_map) with the counts of a .npy file"""
+    counts = np.load(cfg["samplemap"])
+    if counts.dtype != np.uint16 or counts.shape != (opt.height, opt.width):
+        raise SystemExit("-samplemap=%s: want a uint16 array [%d, %d], got %s %s" % (cfg["samplemap"], opt.height, opt.width, counts.dtype, counts.shape))
+    begin = cfg["samplemap_begin"] or 0
+    ts = time.perf_counter()
+    plane = r.sample_map(cam, opt, counts, pass_begin=begin)
+    ms = (time.perf_counter() - ts)*1000.0
+    np.savez(cfg["samplemap_out"], plane=plane, counts=counts, pass_begin=np.int64(begin))
+    print("wrote %s: %dx%d, %d samples on %d pixels (up to %d a pixel) from pass %d in %.3fms" % (
+        cfg["samplemap_out"], opt.width, opt.height, int(counts.sum(dtype=np.int64)), int((counts > 0).sum()), int(counts.max()), begin, ms))
+
+
 def denoise(r, cam, opt, cfg, samples):
     """-denoise: the features of the render's own passes, the denoise stage on the accumulator, the display stage on its result;
     returns (presented image, denoised linear image)"""
@@ -376,6 +402,12 @@ def main(argv=None):
                          cfg["probes_at"]):
         raise SystemExit("-views writes a turntable beside a normal render: no batch mode, no -resume, -complexity, -firsthit, -irradiance "
                          "or -probes")
+    if bool(cfg["samplemap"]) != bool(cfg["samplemap_out"]) or (cfg["samplemap_begin"] is not None and not cfg["samplemap"]):
+        raise SystemExit("-samplemap=COUNTS.npy and -samplemap_out=OUT.npz go together; -samplemap_begin goes with them")
+    if cfg["samplemap"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                             cfg["probes_at"]):
+        raise SystemExit("-samplemap writes a sample-map plane beside a normal render: no batch mode, no -resume, -complexity, -firsthit, "
+                         "-irradiance or -probes")
     if cfg["denoise"] is not None and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                                        cfg["probes_at"]):
         raise SystemExit("-denoise filters a normal render with the guide buffers of its passes [0, N): no batch mode, no -resume, -complexity, "
@@ -443,6 +475,8 @@ def main(argv=None):
         lightgroups(r, scene, cam, opt, cfg)
     if cfg["views"]:
         views(r, cam, opt, cfg)
+    if cfg["samplemap"]:
+        samplemap(r, cam, opt, cfg)
     linear = None
     if cfg["denoise"] is not None:
         image, linear = denoise(r, cam, opt, cfg, samples)

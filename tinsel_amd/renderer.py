@@ -112,6 +112,10 @@ def load_library():
         L.tinsel_hip_render_views.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
         L.tinsel_hip_render_views_device.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
         L.tinsel_hip_plan_views.argtypes = [C.c_ulonglong, ci, ci, ci, ci, C.POINTER(C.c_int)]
+    if hasattr(L, "tinsel_hip_render_sample_map"):     # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_sample_map.argtypes = abi.RENDER_SAMPLE_MAP_ARGTYPES
+        L.tinsel_hip_render_sample_map_device.argtypes = abi.RENDER_SAMPLE_MAP_DEVICE_ARGTYPES
+        L.tinsel_hip_plan_sample_map.argtypes = abi.PLAN_SAMPLE_MAP_ARGTYPES
     if hasattr(L, "tinsel_hip_denoise"):               # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_denoise_params_init.restype = None
         L.tinsel_hip_denoise_params_init.argtypes = [C.POINTER(abi.DenoiseParams)]
@@ -208,6 +212,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_render_id_mattes", "tinsel_hip_render_id_mattes_device",
     "tinsel_hip_render_light_groups", "tinsel_hip_render_light_groups_device",
     "tinsel_hip_render_views", "tinsel_hip_render_views_device", "tinsel_hip_plan_views",
+    "tinsel_hip_render_sample_map", "tinsel_hip_render_sample_map_device", "tinsel_hip_plan_sample_map",
     "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
 
@@ -508,6 +513,36 @@ def plan_views(slot_limit, width, height, passes, num_views):
     out = (C.c_int*3)()
     _check(L.tinsel_hip_plan_views(int(slot_limit), int(width), int(height), int(passes), int(num_views), out), "tinsel_hip_plan_views")
     return tuple(int(v) for v in out)
+
+
+def _sample_counts(counts, width, height, who):
+    """the map as the C entries read it: a C-contiguous uint16 array [H, W]"""
+    counts = np.asarray(counts)
+    if counts.dtype != np.uint16 or counts.shape != (int(height), int(width)):
+        raise ValueError("%s: counts is a uint16 array [%d, %d]" % (who, int(height), int(width)))
+    return np.ascontiguousarray(counts)
+
+
+def plan_sample_map(slot_limit, width, height, counts):
+    """tinsel_hip_plan_sample_map: (levels per batch, batches, total paths, largest count) of a sample-map call with the uint16 map
+    `counts` [H, W] under a limit of slot_limit path slots per batch (host arithmetic only, no GPU needed)"""
+    L = load_library()
+    counts = _sample_counts(counts, width, height, "plan_sample_map")
+    out = (C.c_ulonglong*4)()
+    _check(L.tinsel_hip_plan_sample_map(int(slot_limit), int(width), int(height), _host_ptr(counts), out), "tinsel_hip_plan_sample_map")
+    return tuple(int(v) for v in out)
+
+
+def crop_sample_map(width, height, x0, y0, x1, y1, passes):
+    """A crop for HipRenderer.sample_map: uint16 [height, width], `passes` on the pixels x0 <= i < x1, y0 <= j < y1 (cut to the frame) and
+    0 elsewhere.  The call then gives those pixels' samples of a full-frame render of `passes` passes -- and, splatted by the filter, their
+    share of the pixels within its reach; a pixel farther out stays exactly zero."""
+    passes = int(passes)
+    if not 0 <= passes <= abi.SAMPLE_MAP_MAX:
+        raise ValueError("crop_sample_map: passes must be in 0 .. %d" % abi.SAMPLE_MAP_MAX)
+    counts = np.zeros((int(height), int(width)), np.uint16)
+    counts[max(0, int(y0)):max(0, int(y1)), max(0, int(x0)):max(0, int(x1))] = passes
+    return counts
 
 
 def relight(planes, gains):
@@ -991,6 +1026,38 @@ class HipRenderer:
                 raise ValueError("views: a C-contiguous float32 array %s is expected" % (shape,))
             _check(self._L.tinsel_hip_render_views(self._h, cams, V, C.byref(options), int(pass_begin), int(passes), flags,
                                                    out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_views")
+        return out
+
+    def sample_map(self, camera, options, counts, pass_begin=0, out=None, add=False):
+        """Sample maps (tinsel_hip_render_sample_map*): a per-pixel pass count in one call -- float32 [H, W, 4], AddSample of the samples of
+        levels 0 .. counts[j, i] - 1 of every pixel, level t the path render() starts for the pixel in pass pass_begin + t; a uniform map n
+        is the accumulator of n passes from zero at pass_begin, bit for bit.  `counts`: a numpy uint16 array [H, W] (crop_sample_map makes
+        one), read before the call returns.  add: the samples are added to what `out` holds instead of starting from zero.  `out`: a
+        contiguous float32 torch tensor [H, W, 4] on this renderer's device takes the device entry on torch's current stream and stays on
+        the device; a numpy array of that shape is filled by the host entry.  Needs init() at the options' frame size; leaves the
+        accumulator, pass index, pass seeds, statistics and tuning as they were."""
+        H, W = int(options.height), int(options.width)
+        counts = _sample_counts(counts, W, H, "sample_map")
+        flags = abi.SAMPLES_ADD if add else 0
+        shape = (H, W, 4)
+        if _is_tensor(out):
+            import torch
+            if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError("sample_map: a contiguous float32 tensor %s on the GPU is expected" % (shape,))
+            if out.device.index != self.device:
+                raise ValueError("sample_map: the tensor is on %s, the renderer on device %d" % (out.device, self.device))
+            _check(self._L.tinsel_hip_render_sample_map_device(self._h, C.byref(camera), C.byref(options), int(pass_begin), _host_ptr(counts), flags,
+                                                               out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "tinsel_hip_render_sample_map_device")
+        else:
+            if out is None:
+                if add:
+                    raise ValueError("sample_map: add=True needs the plane to add to (out)")
+                out = np.zeros(shape, np.float32)
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("sample_map: a C-contiguous float32 array %s is expected" % (shape,))
+            _check(self._L.tinsel_hip_render_sample_map(self._h, C.byref(camera), C.byref(options), int(pass_begin), _host_ptr(counts), flags,
+                                                        out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_sample_map")
         return out
 
     def id_mattes(self, camera, options, pass_begin=0, passes=1, slots=6, out=None):
