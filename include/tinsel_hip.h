@@ -910,6 +910,45 @@ int tinsel_hip_plane_table(tinsel_hip* r, int* out2);
  * mesh walk or transmission among the bits above, and every material's `subsurface` is +0.0f BY ITS BITS (-0.0f is not).  A scene that is
  * not slim runs the general kernel (kind 0) whatever its bits; the bits themselves do not know about subsurface.  No device, no renderer. */
 int tinsel_hip_scene_slim(const tinsel_scene_desc* scene);
+/* BAKED INSTANCES.  The fused kernel's closed instance (kind 2) compiled once more for ONE scene: the wave-uniform scene level -- the plane
+ * table, the leaf boxes and primitive records the flat scan visits, the lights' records and constants -- stated as compile-time constants
+ * in a generated header, so that the kernel fetches none of it and holds none of it in scalar registers.  Same float operations on the same
+ * operands in the same order: results are bit-identical to the library's own instance.  The library generates the text and launches the
+ * result; compiling is the caller's (tinsel_amd/build.py bake(): hipcc with the library's own flags, -DTN_BAKED_HEADER naming the text,
+ * csrc/tinsel_baked.hip, device code only).
+ *
+ * tinsel_hip_bake_source: the header for the scene level IN FORCE (after any move, refit, rebuild or tuning change).  Writes up to
+ * `capacity` bytes of text into out_text (NULL: none), the key -- the sha256 of the text, 64 hex digits and a NUL -- into out_key65 (where
+ * given), and into *out_bakeable 1 where a camera render of this renderer is planned with the closed instance (exactly plan_batch's rule),
+ * else 0, with the failing condition as tinsel_hip_last_error().  Returns the text's length in bytes, or -1.  No device work. */
+long long tinsel_hip_bake_source(tinsel_hip* r, char* out_text, unsigned long long capacity, char* out_key65, int* out_bakeable);
+/* The same from a scene description and a tuning (NULL: the defaults), with no device and no renderer: the text, key and answer a renderer
+ * created from them on a gfx950 device reports until its scene level changes. */
+long long tinsel_hip_bake_source_desc(const tinsel_scene_desc* scene, const tinsel_hip_tuning* tuning, char* out_text, unsigned long long capacity,
+                                      char* out_key65, int* out_bakeable);
+/* Installs the gfx950 code object `image` (`bytes` long) compiled from the text whose key is `key`: loads it, finds the kernel by its
+ * mangled name, raises its dynamic-LDS limit like the library's own.  how: TINSEL_BAKE_COMPILED or TINSEL_BAKE_FROM_CACHE (reported by
+ * tinsel_hip_bake_status).  image == NULL with how == TINSEL_BAKE_NO_COMPILER only records why nothing is installed.  From then on a
+ * launch planned as kind 2 runs the installed function WHILE `key` equals the key of the scene level in force, the arithmetic arm is
+ * TINSEL_ARITH_EXACT and the bake mode (tinsel_hip_set_bounce_bake) is not 0; otherwise the library's instance runs, as before.  A second install
+ * replaces the first.  Returns 0, or -1 (the previous module, if any, stays). */
+int tinsel_hip_install_baked(tinsel_hip* r, const void* image, unsigned long long bytes, const char* key, int how);
+/* out3[0] = the state (below), out3[1..2] = the launches the installed function has served (low, high word); out_key65 (where given): the
+ * installed module's key, or the empty string.  TINSEL_BAKE_OFF: the bake mode is 0; _NOT_BAKEABLE: the plan would not pick kind 2;
+ * _NONE: bakeable, nothing installed; _NO_COMPILER: the caller found no compiler (or its compile failed); _COMPILED / _FROM_CACHE: an
+ * installed module whose key is the live one; _LDS_REFUSED: such a module, but the runtime did not raise its dynamic-LDS limit and this scene's
+ * launches ask for more than the default one, so it serves none; _STALE: an installed module compiled for another scene level (the library's instance runs). */
+int tinsel_hip_bake_status(tinsel_hip* r, uint32_t* out3, char* out_key65);
+/* The bake mode of a renderer: -1 auto (the default) | 0: an installed baked instance never serves a launch and a caller should bake none |
+ * 1: wanted whatever the reservation's size.  The library compiles nothing itself: the mode says whether an installed instance may serve
+ * a launch and tells the caller when to bake (tinsel_amd's Renderer.reserve(): with 1 always, with -1 at reservations of one default
+ * batch, 64 Mi path slots, or more).  It is a setting of its own and not a field of tinsel_hip_tuning, whose layout stays as it is; the
+ * Python binding carries it beside the struct as abi.Tuning's `bounce_bake`.  Set returns 0, or -1 (mode out of range); results are
+ * bit-identical under every mode. */
+int tinsel_hip_set_bounce_bake(tinsel_hip* r, int mode);
+int tinsel_hip_get_bounce_bake(tinsel_hip* r);
+enum { TINSEL_BAKE_OFF = 0, TINSEL_BAKE_NOT_BAKEABLE = 1, TINSEL_BAKE_NO_COMPILER = 2, TINSEL_BAKE_COMPILED = 3, TINSEL_BAKE_FROM_CACHE = 4,
+       TINSEL_BAKE_STALE = 5, TINSEL_BAKE_NONE = 6, TINSEL_BAKE_LDS_REFUSED = 7 };
 enum { TINSEL_BOUNCE_MEDIA = 1, TINSEL_BOUNCE_PROBE = 2, TINSEL_BOUNCE_MOTION = 4, TINSEL_BOUNCE_MESH_WALK = 8, TINSEL_BOUNCE_SPHERE = 16,
        TINSEL_BOUNCE_TRANSMISSION = 32, TINSEL_BOUNCE_POOLS = 64, TINSEL_BOUNCE_SHARE = 128, TINSEL_BOUNCE_SORT = 256, TINSEL_BOUNCE_ROULETTE = 512 };
 

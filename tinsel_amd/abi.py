@@ -206,6 +206,11 @@ BOUNCE_MEDIA, BOUNCE_PROBE, BOUNCE_MOTION, BOUNCE_MESH_WALK, BOUNCE_SPHERE = 1, 
 BOUNCE_TRANSMISSION, BOUNCE_POOLS, BOUNCE_SHARE, BOUNCE_SORT, BOUNCE_ROULETTE = 32, 64, 128, 256, 512
 
 
+# tinsel_hip_bake_status / tinsel_hip_install_baked (include/tinsel_hip.h TINSEL_BAKE_*)
+BAKE_OFF, BAKE_NOT_BAKEABLE, BAKE_NO_COMPILER, BAKE_COMPILED, BAKE_FROM_CACHE, BAKE_STALE, BAKE_NONE, BAKE_LDS_REFUSED = 0, 1, 2, 3, 4, 5, 6, 7
+BAKE_AUTO_MIN_PATHS = 64 << 20      # auto bakes at a reservation of one default batch (64 Mi path slots) or more
+
+
 class Tuning(C.Structure):
     """tinsel_hip_tuning (include/tinsel_hip.h): every choice between two code paths of the library as one plain struct.  Tuning() holds
     the defaults ("the library decides"); Tuning(walk_min_tris=0, small_mesh_bytes=0) overrides fields.  Nothing is read from the
@@ -218,11 +223,16 @@ class Tuning(C.Structure):
                 ("shade_sorted", C.c_int32), ("overlap", C.c_int32), ("scene_walk", C.c_int32), ("swalk_lds", C.c_int32), ("accumulate", C.c_int32),
                 ("walk_block", C.c_int32), ("walk_single", C.c_int32), ("walk_lds_stack", C.c_int32), ("walk_refill_min", C.c_int32), ("walk_leaf_min", C.c_int32),
                 ("walk_grid_mult", C.c_int32), ("quads_in_scan", C.c_int32), ("bounce_fit", C.c_int32), ("plane_pairs", C.c_int32)]
+    # `bounce_bake` (-1 auto | 0 never | 1 always: baked instances, include/tinsel_hip.h tinsel_hip_set_bounce_bake) travels with a Tuning in
+    # this binding -- Tuning(bounce_bake=0), set_tuning(bounce_bake=1), bench.py --tuning -- but is NOT a field of the C struct, whose layout
+    # stays as it is: the renderer hands it to the library through its own setter (HipRenderer._apply_bake_mode)
+    BINDING_FIELDS = ("bounce_bake",)
+    bounce_bake = -1        # (the default of an instance that was not made by __init__, e.g. from_buffer_copy)
     CREATE_FIELDS = ("flat_scan", "lds_scene", "walk", "inline_max_tris", "walk_min_tris", "small_mesh_bytes", "arena_lds_limit")
     _DEFAULTS = dict(flat_scan=-1, lds_scene=-1, walk=-1, inline_max_tris=-1, walk_min_tris=-1, small_mesh_bytes=-1, arena_lds_limit=-1,
                      batch_paths=0, grid_mult=0, bounce_share=-1, repack=-1, tail_split=-1, tail_share=0.0, tail_divide=4,
                      shade_sorted=-1, overlap=-1, scene_walk=-1, swalk_lds=-1, accumulate=0,
-                     walk_block=0, walk_single=-1, walk_lds_stack=-1, walk_refill_min=0, walk_leaf_min=0, walk_grid_mult=0, quads_in_scan=-1, bounce_fit=-1, plane_pairs=-1)
+                     walk_block=0, walk_single=-1, walk_lds_stack=-1, walk_refill_min=0, walk_leaf_min=0, walk_grid_mult=0, quads_in_scan=-1, bounce_fit=-1, plane_pairs=-1, bounce_bake=-1)
 
     def __init__(self, **over):
         super().__init__()

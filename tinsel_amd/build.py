@@ -75,6 +75,94 @@ def _compile(obj_dir, extra=(), verbose=True):
             raise subprocess.CalledProcessError(p.returncode, cmd)
 
 
+SRC_BAKED = os.path.join(HERE, "csrc", "tinsel_baked.hip")
+BAKE_CACHE_ENV = "TINSEL_BAKE_CACHE"
+
+
+def bake_cache_dir():
+    """Where baked code objects are kept: $TINSEL_BAKE_CACHE, else csrc/_obj/baked in the tree (kept out of git like the objects)."""
+    return os.environ.get(BAKE_CACHE_ENV) or os.path.join(OBJ_DIR, "baked")
+
+
+def _bake_cache_name(key, cc):
+    """key (the sha256 of the generated header) + the sha256 of csrc/*.h and the baked unit + the flags + `hipcc --version`"""
+    h = hashlib.sha256()
+    h.update(key.encode())
+    csrc = os.path.join(HERE, "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".h") or f == os.path.basename(SRC_BAKED):
+            h.update(f.encode())
+            h.update(_sha(os.path.join(csrc, f)).encode())
+    h.update(" ".join(HIPCC_FLAGS).encode())
+    h.update(subprocess.run([cc, "--version"], capture_output=True, text=True).stdout.encode())
+    return "k_bounce_baked_%s.co" % h.hexdigest()[:32]
+
+
+def bake_command(cc, header, out, extra=()):
+    """The baked translation unit's compile: the parity flags, device code only, ONE instance -- one core."""
+    return [cc] + HIPCC_FLAGS + list(extra) + ["--cuda-device-only", "-DTN_BAKED_HEADER=\"%s\"" % header, "-c", SRC_BAKED, "-o", out]
+
+
+BAKED_KERNEL = "k_bounce<2,1,0>"
+
+
+def baked_refusal(res):
+    """Why a baked kernel with these resources (the compiler's report, _parse_resources) is not installed, or None.  The host plans every
+    k_bounce launch for four waves per SIMD and no instance of it uses scratch: a scene whose unrolled scan takes more registers than that
+    keeps the library's instance."""
+    if not res:
+        return "the compiler reported no resources for %s" % BAKED_KERNEL
+    if res.get("waves_per_simd") != 4 or res.get("scratch_bytes") != 0 or res.get("vgprs", 0) > 128:
+        return "%s at %s waves per SIMD, %s VGPRs, %s B of scratch (wanted: 4, <= 128, 0)" % (
+            BAKED_KERNEL, res.get("waves_per_simd"), res.get("vgprs"), res.get("scratch_bytes"))
+    return None
+
+
+def bake(text, key, verbose=False):
+    """Compiles the baked instance whose generated header is `text` (tinsel_hip_bake_source; `key` is its sha256), or finds it in the cache.
+    Returns (code object bytes, "cache" | "compiled"), or (None, reason) where there is no compiler, the compile fails or the kernel's
+    resources are not the closed instance's (baked_refusal: only code objects that passed are ever cached) -- never raises:
+    the library's own instance keeps running.  hipcc runs as a CHILD process; the cache file is written under a temporary name and
+    renamed, so processes that race each write a whole file and the last rename wins."""
+    if hashlib.sha256(text.encode()).hexdigest() != key:
+        return None, "the key is not the sha256 of the text"
+    try:
+        cc = hipcc()
+    except RuntimeError:
+        return None, "no compiler"
+    try:
+        path = os.path.join(bake_cache_dir(), _bake_cache_name(key, cc))
+        if os.path.exists(path):
+            with open(path, "rb") as f:
+                return f.read(), "cache"
+        with tempfile.TemporaryDirectory(prefix="tinsel_bake_") as tmp:
+            header = os.path.join(tmp, "scene_%s.h" % key[:16])
+            with open(header, "w") as f:
+                f.write(text)
+            cmd = bake_command(cc, header, "baked.co", extra=["-Rpass-analysis=kernel-resource-usage"])
+            if verbose:
+                print("[tinsel_amd.build] (in %s)" % tmp, " ".join(cmd), flush=True)
+            p = subprocess.run(cmd, cwd=tmp, capture_output=True, text=True)
+            if p.returncode != 0:
+                return None, "compile failed: " + p.stderr[-2000:]
+            why = baked_refusal(_parse_resources(p.stderr).get(BAKED_KERNEL))
+            if why:
+                return None, "refused: " + why
+            with open(os.path.join(tmp, "baked.co"), "rb") as f:
+                image = f.read()
+    except OSError as e:
+        return None, "compiler unavailable: %s" % e
+    try:                # (a cache that cannot be written -- a read-only tree -- costs the next process a compile, nothing else)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        fd, part = tempfile.mkstemp(prefix=".part_", dir=os.path.dirname(path))
+        with os.fdopen(fd, "wb") as f:
+            f.write(image)
+        os.replace(part, path)
+    except OSError:
+        pass
+    return image, "compiled"
+
+
 def _resource_job(tmp):
     """The parity translation unit's device code once more, with -Rpass-analysis=kernel-resource-usage: registers, scratch and occupancy
     of every kernel as the compiler reports them.  (A compile of its own: the flag changes the object's bytes, and the shipped object

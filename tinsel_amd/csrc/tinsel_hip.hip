@@ -67,6 +67,7 @@ int fail(const std::string& msg)
 #include "tn_host_own.h"          // DevBuf, DevPool, Stream, Event, PinnedOutput: the only file that allocates or frees
 #include "tn_host_layout.h"       // BVH re-layout, arena
 #include "tn_host_state.h"        // struct tinsel_hip
+#include "tn_host_bake.h"         // baked instances: the generated scene-level header, its key, the installed module's launch
 #include "tn_host_batch.h"        // launches, grids and regions, render_batch / render_impl
 #include "tn_host_query.h"        // ray queries: k_query's plan and launch, the host entries' staging buffers
 #include "tn_host_radiance.h"     // radiance queries: the split / paired pipeline on paths the caller starts

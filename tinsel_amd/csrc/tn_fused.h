@@ -158,6 +158,16 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
     constexpr int POOL = SLIM ? kPoolFieldsSlim : kPoolFields;
     static_assert(!SLIM || !(FEAT & (kFeatMedia | kFeatMotion | kFeatTransmission | kFeatProbe)), "the slim state has no word for these");
     typedef SceneT<LDS, false, DEFER ? 1 : 0, false, FEAT> SC;
+#if TN_BAKED_SCENE
+    // A baked instance runs at the kBounceWaves (four) waves per SIMD the host plans every k_bounce launch by -- plan_bounce sizes the grid and
+    // the region cut for that many resident workgroups -- also where its registers would let a fifth in (cornell's needs 91): naming v103
+    // makes the kernel's allocation 104 VGPRs, the smallest that holds a SIMD to four waves.  No instruction is emitted.
+    if constexpr (SC::kBaked)
+    {
+        static_assert(kBounceWaves == 4, "v103 is four waves' threshold");
+        asm volatile("" ::: "v103");
+    }
+#endif
     const DevScene& scIn = ka.scIn;
     const SplitState& ss = ka.ss;
     const QueueCtl& q = ka.q;
@@ -399,11 +409,19 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                     HitCtx h;
                     on_hit_begin<SLIM>(p, mat, t, n, bounce, h, prim);
 
-                    if (sc.totalLightSamples > 0)
+#if TN_BAKED_SCENE
+                    constexpr bool BAKED = SC::kBaked;
+                    const bool anyLightSamples = BAKED ? baked::kTotalLightSamples > 0 : sc.totalLightSamples > 0;
+                    baked::LightCursor bakedLights;
+#else
+                    constexpr bool BAKED = false;
+                    const bool anyLightSamples = sc.totalLightSamples > 0;
+#endif
+                    if (anyLightSamples)
                     {
                         const V3 thrAtNee = p.thr;
                         LightCursor lights;
-                        V3 sum = nee_sum(sc, [&](int k) -> V3 {
+                        auto contrib = [&](int k) -> V3 {
                             NeeGeo g;
                             V3 skyColor;
                             float skyPdf = 0.0f;
@@ -412,6 +430,9 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                                 nee_sample_probe(late_sky(), h.p, h.n, p.rng, g, skyColor, skyPdf);
                             else
                             {
+#if TN_BAKED_SCENE
+                                if constexpr (BAKED) light = bakedLights.next(); else
+#endif
                                 light = lights.next(sc);
                                 nee_sample_light(sc, h.p, h.n, p.time, light, p.rng, g);
                             }
@@ -428,8 +449,16 @@ __global__ __launch_bounds__(kBlock, kBounceWaves) void k_bounce(BounceKernargs 
                                 return (hp < 0) ? nee_contrib_probe<SLIM>(mat_at(prim), h, g.wi, skyColor, skyPdf) : V3(0.0f);
                             if (!nee_light_reached(g, hp, ts))
                                 return V3(0.0f);
+#if TN_BAKED_SCENE
+                            if constexpr (BAKED) return nee_contrib_light_baked<SLIM>(sc, mat_at(prim), h, g.wi, g.nl, light, hp, ts);
+#endif
                             return nee_contrib_light<SLIM>(sc, mat_at(prim), h, g.wi, g.nl, light, hp, ts);
-                        });
+                        };
+#if TN_BAKED_SCENE
+                        const V3 sum = BAKED ? nee_sum_baked(contrib) : nee_sum(sc, contrib);
+#else
+                        const V3 sum = nee_sum(sc, contrib);
+#endif
                         p.rad = p.rad + thrAtNee*sum;
                     }
 

@@ -1080,6 +1080,81 @@ int tinsel_hip_bounce_plan(tinsel_hip* r, uint32_t* out2)
     return 0;
 }
 
+long long tinsel_hip_bake_source(tinsel_hip* r, char* out_text, unsigned long long capacity, char* out_key65, int* out_bakeable)
+{
+    if (!r)
+        return fail("bake_source: null renderer");
+    return bake_source_of(r, out_text, capacity, out_key65, out_bakeable);
+}
+
+int tinsel_hip_install_baked(tinsel_hip* r, const void* image, unsigned long long bytes, const char* key, int how)
+{
+    if (!r)
+        return fail("install_baked: null renderer");
+    if (!image && how == TINSEL_BAKE_NO_COMPILER)
+    {
+        if (!r->baked.fn)
+            r->baked.how = how;
+        return 0;
+    }
+    if (!image || bytes < 64 || !key || strlen(key) != 64 || (how != TINSEL_BAKE_COMPILED && how != TINSEL_BAKE_FROM_CACHE))
+        return fail("install_baked: bad arguments (a code object, its 64-digit key, TINSEL_BAKE_COMPILED or _FROM_CACHE)");
+    lookahead_cancel(r);
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipDeviceSynchronize());            // (a launch in flight may be running the module this one replaces)
+    Module fresh;
+    if (fresh.load(image))
+        return -1;
+    hipFunction_t fn = nullptr;
+    HIP_TRY(hipModuleGetFunction(&fn, fresh, kBakedKernelName));
+    // the raised dynamic-LDS limit of the library's own instance (prepare_path_kernels); where the runtime has no such attribute for a
+    // module's function, the instance serves the launches that stay within the default limit
+    uint32_t ldsLimit = 65536;
+    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, r->sharedMemLimit) == hipSuccess)
+        ldsLimit = (uint32_t)r->sharedMemLimit;
+    else
+        (void)hipGetLastError();
+    r->baked.module = std::move(fresh);
+    r->baked.fn = fn;
+    r->baked.key = key;
+    r->baked.how = how;
+    r->baked.ldsLimit = ldsLimit;
+    r->baked.launches = 0;
+    return 0;
+}
+
+int tinsel_hip_set_bounce_bake(tinsel_hip* r, int mode)
+{
+    if (!r || mode < -1 || mode > 1)
+        return fail("set_bounce_bake: bad arguments (-1 auto, 0 never, 1 always)");
+    lookahead_cancel(r);
+    r->baked.mode = mode;
+    return 0;
+}
+
+int tinsel_hip_get_bounce_bake(tinsel_hip* r) { return r ? r->baked.mode : -1; }
+
+int tinsel_hip_bake_status(tinsel_hip* r, uint32_t* out3, char* out_key65)
+{
+    if (!r || !out3)
+        return fail("bake_status: bad arguments");
+    if (out_key65)
+        memcpy(out_key65, r->baked.fn ? r->baked.key.c_str() : "", r->baked.fn ? 65 : 1);
+    out3[1] = (uint32_t)(r->baked.launches & 0xffffffffull);
+    out3[2] = (uint32_t)(r->baked.launches >> 32);
+    if (r->baked.mode == 0)
+        out3[0] = TINSEL_BAKE_OFF;
+    else if (!plans_fit_closed(r, nullptr))
+        out3[0] = TINSEL_BAKE_NOT_BAKEABLE;
+    else if (!r->baked.fn)
+        out3[0] = r->baked.how == TINSEL_BAKE_NO_COMPILER ? TINSEL_BAKE_NO_COMPILER : TINSEL_BAKE_NONE;
+    else
+        // (a closed launch asks for the traversal stacks and the staged arena, no pools: stack_bytes)
+        out3[0] = r->baked.key != bake_live_key(r) ? (uint32_t)TINSEL_BAKE_STALE :
+                  stack_bytes(r) > (size_t)r->baked.ldsLimit ? (uint32_t)TINSEL_BAKE_LDS_REFUSED : (uint32_t)r->baked.how;
+    return 0;
+}
+
 int tinsel_hip_queue_counts(tinsel_hip* r, uint32_t* out, int max_bounces)
 {
     if (!r || !out || max_bounces < 1)

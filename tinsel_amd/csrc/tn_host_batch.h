@@ -501,6 +501,39 @@ int fit_bounce(uint32_t need, bool deferMeshes)
     return within(kBounceFitClosed) ? PK_BOUNCE_FIT_CLOSED : PK_NONE;
 }
 
+// Would a camera render's plan give this scene the closed FIT instance (plan_batch below: the fused pipeline, the whole scene in LDS, the flat
+// scan, no detail counters, bounce_fit on, a slim scene whose features lie inside the closed set, no deferred walks)?  `why`: the first
+// condition that fails.  This is the rule a baked instance is offered by (tinsel_hip_bake_source).
+bool plans_fit_closed(const tinsel_hip* r, std::string* why)
+{
+    auto no = [&](const char* w) { if (why) *why = w; return false; };
+    if (resolve_pipeline(r) != TINSEL_PIPELINE_WAVEFRONT)
+        return no("the scene does not run the fused pipeline");
+    if (residency(r->scene, r->scene.arenaLdsBytes) != RES_LDS)
+        return no("the scene is not staged whole into LDS");
+    if (r->countDetail)
+        return no("detail counters are on");
+    if (!r->scene.flatScan)
+        return no("the scene level is not a flat scan");
+    if (r->tune.bounce_fit == 0)
+        return no("tinsel_hip_tuning::bounce_fit is 0");
+    int resident = 0;
+    const uint32_t need = bounce_features(r, plan_bounce(r, &resident));
+    if (!scene_slim(need, r->anySubsurface))
+        return no("the scene is not slim (a medium, a probe, motion, a walked mesh, transmission or subsurface)");
+    if (fit_bounce(need, r->scene.deferMeshes != 0) != PK_BOUNCE_FIT_CLOSED)
+        return no(r->scene.deferMeshes ? "the scene defers its mesh walks (the deferred FIT instance is not baked)" : "the scene's features lie outside the closed FIT set");
+    return true;
+}
+
+// Does the installed baked function serve this launch of PK_BOUNCE_FIT_CLOSED?  Only the exact arithmetic arm, only within the dynamic LDS
+// the function may ask for, and only where its key is the key of the scene level in force NOW
+bool baked_serves(const tinsel_hip* r, const LaunchArgs& a)
+{
+    return r->baked.fn != nullptr && r->baked.mode != 0 && r->arith == TINSEL_ARITH_EXACT && a.ldsBytes <= r->baked.ldsLimit &&
+           r->baked.key == bake_live_key(r);
+}
+
 // k_walk's launches of a render call (plan_walk): instance, workgroup, workgroups per CU, dynamic LDS, the job's fixed part
 struct WalkPlan
 {
@@ -1225,6 +1258,9 @@ int trace_fused(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
                         (a.variant == PK_BOUNCE_COUNT_LDS || a.variant == PK_BOUNCE_COUNT) ? kBounceCount : kBounceGeneral;
     r->lastBounceFeatures = p.bounceFeatures | (a.fp.share ? kFeatShare : 0u);
     ScopedTimer t(r, KN_BOUNCE, st);
+    // a baked instance of the closed FIT kernel, where one is installed for exactly the scene level in force (tn_host_bake.h)
+    if (a.variant == PK_BOUNCE_FIT_CLOSED && baked_serves(r, a))
+        return launch_baked(r, a, st);
     return launch_path(r, a, st);
 }
 

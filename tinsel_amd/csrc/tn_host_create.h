@@ -30,9 +30,13 @@ struct SceneBuild
     bool sceneHasBigMesh = false;
     SceneLevel lvl;
     bool flatScan = false;
+    // DRY: the host's half only -- every record, offset, flag and count as create derives them, nothing allocated or uploaded, device
+    // addresses stand-ins that are never read through (tinsel_hip_bake_source_desc: a scene description's baked header without a device)
+    bool dry = false;
+    template <class T> T* dry_address() const { return reinterpret_cast<T*>(uintptr_t(128)); }
 
-    SceneBuild(tinsel_hip* r_, const tinsel_scene_desc* d)
-        : r(r_), sc(r_->scene), desc(d), tune(r_->tune), P(d->num_primitives), prims((size_t)P), mats((size_t)P), moving((size_t)P)
+    SceneBuild(tinsel_hip* r_, const tinsel_scene_desc* d, bool dry_ = false)
+        : r(r_), sc(r_->scene), desc(d), tune(r_->tune), P(d->num_primitives), prims((size_t)P), mats((size_t)P), moving((size_t)P), dry(dry_)
     {
         for (int i = 0; i < P; ++i)
             if (desc->primitives[i].type == TINSEL_GEOM_MESH && mesh_bytes_estimate(desc->primitives[i].geo.mesh) > kSmallMeshBytes)
@@ -138,6 +142,10 @@ int SceneBuild::add_mesh(const tinsel_mesh_geometry& g, Prim64& o)
         dm.offTris = (uint32_t)arena.add(tris.data(), tris.size());
         dm.offNormals = (uint32_t)arena.add(&g.normals[0].x, (size_t)g.num_vertices*3);
         dm.offCdf = (uint32_t)arena.add(g.cdf, (size_t)numTris);
+    }
+    else if (dry)
+    {
+        dm.nodes = dry_address<const Node64>(); dm.tris = dry_address<const Tri48>(); dm.normals = dry_address<const float>(); dm.cdf = dry_address<const float>();
     }
     else
     {
@@ -293,6 +301,9 @@ int SceneBuild::assemble_arena()
     for (size_t l = 0; l < lights.size(); ++l)
         lightRecs[l] = { lights[l], mats[(size_t)lights[l]].lightSamples, mats[(size_t)lights[l]].rcpLightSamples, 0 };
     const size_t offLights = arena.add(lightRecs.data(), lightRecs.size());
+    r->lightMats.clear();
+    for (const int32_t l : lights)
+        r->lightMats.push_back(mats[(size_t)l]);
     const size_t offMeshes = arena.add(meshes.data(), meshes.size());
 
     // The always-hit planes once more, four by four, for the flat scan (trace_flat): four IntersectRayPlane calls in a block are four
@@ -328,7 +339,7 @@ int SceneBuild::assemble_arena()
     const size_t offPlaneIdx = arena.add(planeIdx.data(), planeIdx.size());
     arena.bytes.resize((arena.bytes.size() + 127) & ~size_t(127), 0);
 
-    unsigned char* arenaDev = r->sceneMem.upload(arena.bytes.data(), arena.bytes.size());
+    unsigned char* arenaDev = dry ? dry_address<unsigned char>() : r->sceneMem.upload(arena.bytes.data(), arena.bytes.size());
     if (!arenaDev)
         return fail("create: device allocation failed (scene arena)");
     // small meshes: offsets -> device pointers, in the host image of the mesh table, then upload once more
@@ -343,7 +354,7 @@ int SceneBuild::assemble_arena()
             hm[m].cdf = reinterpret_cast<const float*>(arenaDev + hm[m].offCdf);
         }
     }
-    if (!meshes.empty() && hipMemcpy(arenaDev + offMeshes, hm, sizeof(DevMesh)*meshes.size(), hipMemcpyHostToDevice) != hipSuccess)
+    if (!dry && !meshes.empty() && hipMemcpy(arenaDev + offMeshes, hm, sizeof(DevMesh)*meshes.size(), hipMemcpyHostToDevice) != hipSuccess)
         return fail("create: device allocation failed (scene arena)");
     r->meshesRef.assign(hm, hm + meshes.size());
     r->meshesNow = r->meshesRef;
@@ -424,6 +435,11 @@ int SceneBuild::upload_probe()
     const size_t n = (size_t)desc->probe_width*desc->probe_height;
     if (!desc->probe_data || !desc->probe_pdf_x || !desc->probe_cdf_x || !desc->probe_pdf_y || !desc->probe_cdf_y || n == 0)
         return fail("create: probe marked valid but arrays missing");
+    if (dry)
+    {
+        sc.probe.valid = 1;
+        return 0;
+    }
     sc.probe.data = (const float4*)r->sceneMem.upload((const float*)desc->probe_data, n*4);
     sc.probe.pdfX = r->sceneMem.upload(desc->probe_pdf_x, n);
     sc.probe.cdfX = r->sceneMem.upload(desc->probe_cdf_x, n);
@@ -442,8 +458,8 @@ int SceneBuild::stats_and_fit()
 {
     r->neePerPath = totalLightSamples + (r->scene.probe.valid ? 1 : 0);
     r->scene.totalLightSamples = r->neePerPath;
-    if (r->statsDev.alloc((size_t)kStatShards*kStatWords) ||
-        hipMemset(r->statsDev.get(), 0, sizeof(unsigned long long)*kStatShards*kStatWords) != hipSuccess)
+    if (!dry && (r->statsDev.alloc((size_t)kStatShards*kStatWords) ||
+        hipMemset(r->statsDev.get(), 0, sizeof(unsigned long long)*kStatShards*kStatWords) != hipSuccess))
         return fail("create: device allocation failed (stats)");
     if (stack_bytes(r) > (size_t)r->sharedMemLimit && r->scene.arenaLdsBytes)
     {
@@ -453,6 +469,47 @@ int SceneBuild::stats_and_fit()
     if (stack_bytes(r) > (size_t)r->sharedMemLimit)
         return fail("create: the traversal stacks of this scene need " + std::to_string(stack_bytes(r)) + " B of LDS per workgroup, the device offers " + std::to_string(r->sharedMemLimit));
     return 0;
+}
+
+// create's steps on `r` (limits and tuning set); dry: SceneBuild::dry
+int build_scene(tinsel_hip* r, const tinsel_scene_desc* desc, bool dry)
+{
+    memset(&r->scene, 0, sizeof(r->scene));
+    SceneBuild b(r, desc, dry);
+    if (b.add_primitives() || b.scene_level())
+        return -1;
+    b.mark_walked_and_quads();
+    if (b.assemble_arena())
+        return -1;
+    b.set_scene_flags();
+    if ((desc->probe_valid && b.upload_probe()) || b.stats_and_fit())
+        return -1;
+    return 0;
+}
+
+// the workgroup LDS limit a scene description is planned with where no device is asked: gfx950's
+constexpr int kDescSharedMemLimit = 160*1024;
+
+// tinsel_hip_bake_source's body (tn_host_api.h has the live entry, this file the description's)
+long long bake_source_of(const tinsel_hip* r, char* out_text, unsigned long long capacity, char* out_key65, int* out_bakeable)
+{
+    const std::string text = bake_text(bake_tables(r));
+    if (out_text && capacity > 0)
+    {
+        const size_t n = std::min<size_t>(text.size(), (size_t)capacity - 1);
+        memcpy(out_text, text.data(), n);
+        out_text[n] = 0;
+    }
+    if (out_key65)
+        memcpy(out_key65, sha256_hex(text).c_str(), 65);
+    if (out_bakeable)
+    {
+        std::string why;
+        *out_bakeable = plans_fit_closed(r, &why) ? 1 : 0;
+        if (!*out_bakeable)
+            g_error = "bake_source: not bakeable: " + why;
+    }
+    return (long long)text.size();
 }
 
 } // namespace
@@ -493,17 +550,23 @@ tinsel_hip* tinsel_hip_create_tuned(const tinsel_scene_desc* desc, int device_in
 
     std::unique_ptr<tinsel_hip> r(new tinsel_hip());
     create_limits(r.get(), device_index, tuning);
-    memset(&r->scene, 0, sizeof(r->scene));
-    SceneBuild b(r.get(), desc);
-    if (b.add_primitives() || b.scene_level())
-        return nullptr;
-    b.mark_walked_and_quads();
-    if (b.assemble_arena())
-        return nullptr;
-    b.set_scene_flags();
-    if ((desc->probe_valid && b.upload_probe()) || b.stats_and_fit())
+    if (build_scene(r.get(), desc, false))
         return nullptr;
     return r.release();
+}
+
+long long tinsel_hip_bake_source_desc(const tinsel_scene_desc* desc, const tinsel_hip_tuning* tuning, char* out_text, unsigned long long capacity,
+                                      char* out_key65, int* out_bakeable)
+{
+    if (!desc || !desc->primitives || desc->num_primitives <= 0 || !desc->bvh_nodes || desc->num_bvh_nodes <= 0)
+        return fail("bake_source_desc: empty scene (Scene::Build must have run)");
+    // create's host half on a renderer that owns nothing on any device: the same records, offsets and plan inputs
+    std::unique_ptr<tinsel_hip> r(new tinsel_hip());
+    r->tune = tuning_from_caller(tuning);
+    r->sharedMemLimit = kDescSharedMemLimit;
+    if (build_scene(r.get(), desc, true))
+        return -1;
+    return bake_source_of(r.get(), out_text, capacity, out_key65, out_bakeable);
 }
 
 void tinsel_hip_destroy(tinsel_hip* r)

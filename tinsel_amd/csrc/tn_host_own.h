@@ -119,6 +119,18 @@ struct Event : DevHandle<hipEvent_t, hipEventDestroy>
     }
 };
 
+// a code object loaded at run time (a baked instance, tn_host_bake.h); its functions live as long as it does
+struct Module : DevHandle<hipModule_t, hipModuleUnload>
+{
+    int load(const void* image)
+    {
+        Module fresh;
+        HIP_TRY(hipModuleLoadData(&fresh.h, image));
+        std::swap(h, fresh.h);
+        return 0;
+    }
+};
+
 // The caller's output array page-locked in place for the read-back DMA (TINSEL_LOOKAHEAD_PIN_OUTPUT: the caller guarantees the array outlives
 // the renderer or the next Init).  A registration must not outlive the memory it names, so it is dropped as soon as it is not asked for.
 struct PinnedOutput

@@ -230,6 +230,9 @@ void adopt_scene_level(tinsel_hip* r, SceneLevel& lvl)
     r->planePairs = lvl.planePairs;
     r->planeSingles = lvl.planeSingles;
     r->sceneStackNeed = lvl.bvh.maxLeafDepth + 1;
+    r->levelPlaneEq = lvl.planeEq;          // (what a baked instance is keyed by: tn_host_bake.h)
+    r->levelPlaneIdx = lvl.planeIdx;
+    r->levelBoxes = lvl.boxes;
     r->sceneBvhHost = std::move(lvl.tree);
 }
 
@@ -286,6 +289,12 @@ int write_mesh_prim_area(tinsel_hip* r, int p)
     unsigned char* mat = const_cast<unsigned char*>(r->scene.arena) + r->arenaOffMats + sizeof(Mat128)*(size_t)p;
     HIP_TRY(hipMemcpy(mat + offsetof(Mat128, area), &area, sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(mat + offsetof(Mat128, rcpArea), &rcpArea, sizeof(float), hipMemcpyHostToDevice));
+    for (size_t l = 0; l < r->lightPrims.size() && l < r->lightMats.size(); ++l)        // (a baked instance states a light's 1/area: its key follows)
+        if (r->lightPrims[l] == p)
+        {
+            r->lightMats[l].area = area;
+            r->lightMats[l].rcpArea = rcpArea;
+        }
     return 0;
 }
 

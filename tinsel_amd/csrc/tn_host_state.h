@@ -79,6 +79,22 @@ struct tinsel_hip
     int lastBounceKind = -1;            // k_bounce's last launch: its kind (tn_fused.h BounceKind) and the features asked of it (tinsel_hip_bounce_plan)
     uint32_t lastBounceFeatures = 0;
     DevPool lbvhTrees;                  // the device-built mesh trees in force (set_mesh_bvh: one generation)
+    // baked instances (tn_host_bake.h): the host's copy of the scene level in force (adopt_scene_level) and of the lights' own Mat128
+    // records (create; write_mesh_prim_area follows a refit) -- what the generated header states --, and the installed code object
+    std::vector<float> levelPlaneEq;
+    std::vector<int32_t> levelPlaneIdx;
+    std::vector<PrimBox> levelBoxes;
+    std::vector<Mat128> lightMats;      // by light, in lightPrims' order
+    struct Baked
+    {
+        Module module;
+        hipFunction_t fn = nullptr;
+        std::string key;                // of the text the module was compiled from
+        int mode = -1;                  // tinsel_hip_set_bounce_bake: -1 auto, 0 never serve, 1 wanted at any size
+        int how = 0;                    // TINSEL_BAKE_COMPILED / _FROM_CACHE (installed), _NO_COMPILER (nothing installed, and why)
+        uint32_t ldsLimit = 65536;      // dynamic LDS a launch of fn may ask for
+        unsigned long long launches = 0;
+    } baked;
 
     int width = 0, height = 0;
     // The accumulator every kernel and entry point reads: a VIEW.  It is accumOwn's buffer (tinsel_hip_init; look-ahead moves buffers between

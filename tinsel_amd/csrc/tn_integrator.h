@@ -142,7 +142,11 @@ struct NeeGeo
 template <class SC>
 TN_D void primitive_sample(const SC& sc, int index, float time, V3& pos, V3& normal, Rng& rng)
 {
+#if TN_BAKED_SCENE
+    Prim64 p = [&] { if constexpr (SC::kBaked) return baked::light_prim(sc, index); else return load_prim(sc.prims, index); }();      // (a baked build: the light's record as constants)
+#else
     Prim64 p = load_prim(sc.prims, index);
+#endif
     if constexpr (!(SC::kFeatures & kFeatMotion))
         p.flags &= ~(uint32_t)kPrimMoving;
     const Xform x = prim_pose(sc, p, time);
@@ -263,16 +267,25 @@ TN_D NeeTerms nee_bsdf_terms(const Mat& surf, const HitCtx& h, V3 wi)
     return e;
 }
 
-TN_D V3 nee_combine_light(const DevScene& sc, const NeeTerms& e, float nl, int light, int hitPrim, float t)
+// (`lm`: where the light's own constants come from -- its Mat128 record, or a baked build's table: tn_baked.h)
+struct LightMatLoaded
+{
+    const Mat128* m;
+    TN_D float rcpArea() const { return m->rcpArea; }
+    TN_D float cbsdf() const { return m->cbsdf; }
+    TN_D float clight() const { return m->clight; }
+};
+
+template <class LM>
+TN_D V3 nee_combine_light_of(const DevScene& sc, const NeeTerms& e, float nl, const LM& lm, int hitPrim, float t)
 {
     V3 L(0.0f);
-    const Mat128* lm = sc.mats + light;
     float tSq = t*t;
-    float lightPdf = (lm->rcpArea*tSq)/nl;          // ((1.0f/lightArea)*t*t)/nl, the reciprocal divided on the host (Mat128)
+    float lightPdf = (lm.rcpArea()*tSq)/nl;         // ((1.0f/lightArea)*t*t)/nl, the reciprocal divided on the host (Mat128)
     if (e.bsdfPdf > 0.0f)
     {
-        float cbsdf = lm->cbsdf;                    // kBsdfSamples/N, float(lightSamples)/N: the host's (Mat128)
-        float clight = lm->clight;
+        float cbsdf = lm.cbsdf();                   // kBsdfSamples/N, float(lightSamples)/N: the host's (Mat128)
+        float clight = lm.clight();
         float weight = clight*lightPdf/(cbsdf*e.bsdfPdf + clight*lightPdf);
         const Mat128* hm = sc.mats + hitPrim;
         V3 em(hm->emission[0], hm->emission[1], hm->emission[2]);
@@ -281,11 +294,42 @@ TN_D V3 nee_combine_light(const DevScene& sc, const NeeTerms& e, float nl, int l
     return L;
 }
 
+TN_D V3 nee_combine_light(const DevScene& sc, const NeeTerms& e, float nl, int light, int hitPrim, float t)
+{
+    return nee_combine_light_of(sc, e, nl, LightMatLoaded{ sc.mats + light }, hitPrim, t);
+}
+
 template <bool SLIM = false>
 TN_D V3 nee_contrib_light(const DevScene& sc, const Mat& surf, const HitCtx& h, V3 wi, float nl, int light, int hitPrim, float t)
 {
     return nee_combine_light(sc, nee_bsdf_terms<SLIM>(surf, h, wi), nl, light, hitPrim, t);
 }
+
+#if TN_BAKED_SCENE
+// nee_contrib_light with the light's constants from the baked table
+template <bool SLIM = false>
+TN_D V3 nee_contrib_light_baked(const DevScene& sc, const Mat& surf, const HitCtx& h, V3 wi, float nl, int light, int hitPrim, float t)
+{
+    return nee_combine_light_of(sc, nee_bsdf_terms<SLIM>(surf, h, wi), nl, baked::LightMat{ light, sc.mats }, hitPrim, t);
+}
+
+// nee_sum with the light table's counts and reciprocals (no probe: the closed FIT instance has none)
+template <class Contrib>
+TN_D V3 nee_sum_baked(Contrib contrib)
+{
+    V3 sum(0.0f);
+    int k = 0;
+    for (int li = 0; li < baked::kNumLights; ++li)
+    {
+        const int numSamples = (int)baked::kLights[li*4 + 1];
+        V3 L(0.0f);
+        for (int s = 0; s < numSamples; ++s)
+            L = L + contrib(k++);
+        sum = sum + L*baked::word_f(baked::kLights[li*4 + 2]);
+    }
+    return sum;
+}
+#endif
 
 // render.cpp:107-116: the probe sample and its shadow ray
 TN_D void nee_sample_probe(const DevScene& sc, V3 hitP, V3 hitN, Rng& rng, NeeGeo& g, V3& skyColor, float& skyPdf)
@@ -323,6 +367,8 @@ TN_D V3 nee_contrib_probe(const Mat& surf, const HitCtx& h, V3 wi, V3 skyColor, 
 // arms.  Reading all three from the one 16-B LightRec measured cornell +0.3-0.8 % in the parity arm but spills 56 VGPRs in the tolerance arm's
 // k_bounce (cornell 7147 -> 5812 Msamples/s, profiles/r06_2t_ab_fast_arm.md); neither shipped build compiled that form.
 // Which light does NEE ray k belong to?  Rays arrive in order (probe first, then lights x samples): the cursor walks along.
+// (TWINS: baked::LightCursor, tn_baked.h, and nee_sum_baked above walk the same lights in the same order over a baked build's light table: a
+// change to next() or to nee_sum is made there too.)
 struct LightCursor
 {
     int li = 0, sInLight = 0;
@@ -336,6 +382,7 @@ struct LightCursor
 
 // Sums per-light contributions in the oracle's order.  `contrib(k)` returns the resolved
 // contribution of NEE ray k (k counts the probe ray first, then lights x samples).
+// (TWIN: nee_sum_baked above.)
 template <class Contrib>
 TN_D V3 nee_sum(const DevScene& sc, Contrib contrib)
 {

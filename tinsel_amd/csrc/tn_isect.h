@@ -495,6 +495,9 @@ TN_D unsigned long long wave_uniform64(unsigned long long v)
     return ((unsigned long long)hi << 32) | lo;
 }
 
+// (TWIN: trace_flat_baked, tn_baked.h, states this scan's closed form -- kCompactSingles, no deferred walks, no any-hit stop -- over a baked
+// build's constants: a change to the pair block, the single planes, the scan loop or accept() here is made there too; tests/test_gpu_bake.py
+// compares the two bit for bit.)
 template <class SC, class Stack, bool COUNT, bool ANYHIT = false>
 TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, float& outT, V3& outN, bool& tie, TraceCounters& ctr, float tStop = 0.0f)
 {
@@ -682,6 +685,12 @@ TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, flo
     return closest;
 }
 
+} // namespace tn
+
+#include "tn_baked.h"       // (a baked build's trace_flat; empty in the library's own translation units)
+
+namespace tn {
+
 // Does this ray pass the leaf-box test of any primitive that is NOT an always-hit plane (flat-scan scenes)?  The
 // producer of a ray queue sorts by this bit: a wave of rays that can only hit the planes skips the sphere and mesh code
 // of trace_flat altogether, and the waves that do run it have their lanes on it.  The same box tests as trace_flat's.
@@ -737,6 +746,14 @@ TN_D int trace(const SC& sc, Stack& st, V3 o, V3 d, float time, float& outT, V3&
         int prim = -1;
         // (the flat scan always runs to its end: stopping it early was measured and costs more in the scan's shape than the
         // skipped tests give back -- cornell 2835 -> 2713 Msamples/s, veach 1454 -> 1366; what stops early is the walks)
+#if TN_BAKED_SCENE
+        if constexpr (SC::kBaked)
+        {
+            if (sane)
+                prim = trace_flat_baked<SC, Stack, COUNT>(sc, st, o, d, rcp, time, outT, outN, tie, ctr);
+        }
+        else
+#endif
         if (sane)
             prim = trace_flat<SC, Stack, COUNT, false>(sc, st, o, d, rcp, time, outT, outN, tie, ctr, 0.0f);
         if (sane && !tie)

@@ -19,6 +19,16 @@
 
 #include "tn_math.h"
 
+// A BAKED build ("Baked instances"): the translation unit names a generated header that states ONE scene's wave-uniform
+// level -- plane table, leaf boxes, primitive records, lights -- as constants (tinsel_hip_bake_source writes it, tinsel_amd/build.py bake()
+// compiles it).  The library's own translation units do not define the macro and compile exactly what they did before it existed.
+#ifdef TN_BAKED_HEADER
+#include TN_BAKED_HEADER
+#define TN_BAKED_SCENE 1
+#else
+#define TN_BAKED_SCENE 0
+#endif
+
 namespace tn {
 
 constexpr uint32_t kLeafBit = 0x80000000u;
@@ -245,6 +255,8 @@ struct SceneT : DevScene
     static constexpr bool kWalkedOnly = WALKED_ONLY != 0;
     static constexpr bool kQuadsInline = WALKED_ONLY == 2;
     static constexpr int kDefer = DEFER;
+    // the constants policy: the closed FIT instance of a baked build reads the scene level from tn::baked (tn_baked.h), everything else loads it
+    static constexpr bool kBaked = TN_BAKED_SCENE != 0 && LDS && WALKED_ONLY == 0 && DEFER == 0 && !MIXED && FEATURES == (uint32_t)kFeatSphere;
     const unsigned char* ldsBase;
     // The flat scan reads primitive records and leaf boxes at a wave-uniform index: through these pointers (the arena's copy
     // in HBM, constant address space) they are scalar loads into SGPRs instead of 64 lanes reading the same LDS words

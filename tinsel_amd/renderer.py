@@ -153,6 +153,15 @@ def load_library():
     if hasattr(L, "tinsel_hip_scene_plane_pairs"):    # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_scene_plane_pairs.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]
         L.tinsel_hip_plane_table.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "tinsel_hip_bake_source"):          # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_bake_source.restype = C.c_longlong
+        L.tinsel_hip_bake_source.argtypes = [vp, C.c_char_p, C.c_ulonglong, C.c_char_p, C.POINTER(C.c_int)]
+        L.tinsel_hip_bake_source_desc.restype = C.c_longlong
+        L.tinsel_hip_bake_source_desc.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.Tuning), C.c_char_p, C.c_ulonglong, C.c_char_p, C.POINTER(C.c_int)]
+        L.tinsel_hip_install_baked.argtypes = [vp, C.c_char_p, C.c_ulonglong, C.c_char_p, ci]
+        L.tinsel_hip_bake_status.argtypes = [vp, C.POINTER(C.c_uint32), C.c_char_p]
+        L.tinsel_hip_set_bounce_bake.argtypes = [vp, ci]
+        L.tinsel_hip_get_bounce_bake.argtypes = [vp]
     if hasattr(L, "tinsel_hip_queue_counts"):        # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_queue_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.tinsel_hip_set_lookahead.argtypes = [vp, ci]
@@ -190,6 +199,7 @@ def load_library():
 
 
 EXPORTED_SYMBOLS = [
+    "tinsel_hip_bake_source", "tinsel_hip_bake_source_desc", "tinsel_hip_install_baked", "tinsel_hip_bake_status", "tinsel_hip_set_bounce_bake", "tinsel_hip_get_bounce_bake",
     "tinsel_hip_bounce_plan", "tinsel_hip_scene_features", "tinsel_hip_scene_slim", "tinsel_hip_scene_plane_pairs", "tinsel_hip_plane_table", "tinsel_hip_create", "tinsel_hip_destroy", "tinsel_hip_init", "tinsel_hip_init_external", "tinsel_hip_render",
     "tinsel_hip_render_async", "tinsel_hip_accum_device_ptr", "tinsel_hip_read_accum", "tinsel_hip_set_shard",
     "tinsel_hip_set_pipeline", "tinsel_hip_set_pass_index", "tinsel_hip_get_pass_index", "tinsel_hip_stats",
@@ -645,6 +655,26 @@ class Scene:
         k = load_library().tinsel_hip_scene_plane_pairs(C.byref(self.desc), out, n, C.byref(singles))
         return [(out[2*q], out[2*q + 1]) for q in range(k)], singles.value
 
+    def bake_source(self, tuning=None):
+        """tinsel_hip_bake_source_desc: (text, key, bakeable, why) -- the generated header a baked instance of this scene is compiled from, its
+        key (the sha256 of the text) and whether a renderer of the scene under `tuning` would be planned with the closed instance, with
+        the failing condition where it would not (no device needed)"""
+        L = load_library()
+        return _bake_source(lambda buf, cap, key, ok: L.tinsel_hip_bake_source_desc(C.byref(self.desc), C.byref(tuning) if tuning is not None else None, buf, cap, key, ok))
+
+
+def _bake_source(call):
+    """the two-call pattern of tinsel_hip_bake_source*: length first, then the text"""
+    key = C.create_string_buffer(65)
+    ok = C.c_int(0)
+    n = call(None, 0, key, C.byref(ok))
+    if n < 0:
+        raise RuntimeError("tinsel_hip_bake_source: " + load_library().tinsel_hip_last_error().decode())
+    why = "" if ok.value else load_library().tinsel_hip_last_error().decode()
+    buf = C.create_string_buffer(int(n) + 1)
+    call(buf, int(n) + 1, key, C.byref(ok))
+    return buf.value.decode(), key.value.decode(), bool(ok.value), why
+
 
 def _bytes_at(ptr, n):
     return C.string_at(ptr, n) if (ptr and n > 0) else b""
@@ -731,10 +761,21 @@ class HipRenderer:
         if not self._h:
             msg = L.tinsel_hip_last_error()
             raise TinselHipError("tinsel_hip_create failed: %s" % (msg.decode() if msg else "?"))
+        if tuning is not None:
+            self._apply_bake_mode(tuning)
         self.device = device
         self.num_primitives = int(scene.desc.num_primitives)     # (light_groups: the table the library reads has one entry each)
         self.width = self.height = 0
         self._accum_tensor = None
+
+    # bake mode 1 ("at the next reserve() or first fused render, whatever the size"): what a render checks before it starts.  The mode and
+    # the key of the last attempt that did not install are kept on this side, so that modes -1 and 0 cost a render one comparison
+    _bake_mode = -1
+    _bake_failed_key = None
+
+    def _bake_before_render(self):
+        if self._bake_mode == 1:
+            self.bake()
 
     # -- Renderer interface ------------------------------------------------
     def init(self, width, height, accum_tensor=None):
@@ -754,6 +795,7 @@ class HipRenderer:
         if output is None and readback:
             output = np.empty((options.height, options.width, 4), np.float32)
         ptr = output.ctypes.data_as(C.c_void_p) if (readback and output is not None) else None
+        self._bake_before_render()
         _check(self._L.tinsel_hip_render(self._h, C.byref(camera), C.byref(options), ptr, passes), "tinsel_hip_render")
         return output
 
@@ -762,6 +804,7 @@ class HipRenderer:
 
     # -- beyond the reference interface -------------------------------------
     def render_async(self, camera, options, passes=1, stream=None):
+        self._bake_before_render()
         _check(self._L.tinsel_hip_render_async(self._h, C.byref(camera), C.byref(options), passes, stream), "tinsel_hip_render_async")
 
     def read_accum(self):
@@ -829,7 +872,16 @@ class HipRenderer:
         """tinsel_hip_set_tuning: the per-render fields of an abi.Tuning (or of the tuning in force with `fields` replaced); the create-time
         fields (abi.Tuning.CREATE_FIELDS) belong to create_gpu_renderer(scene, device, tuning)."""
         t = (tuning if tuning is not None else self.get_tuning()).replace(**fields)
-        _check(self._L.tinsel_hip_set_tuning(self._h, C.byref(t)), "tinsel_hip_set_tuning")
+        # (the binding's own fields alone: no field of the C struct changes, so the path buffers tinsel_hip_set_tuning frees are kept)
+        if not (tuning is None and fields and set(fields) <= set(abi.Tuning.BINDING_FIELDS)):
+            _check(self._L.tinsel_hip_set_tuning(self._h, C.byref(t)), "tinsel_hip_set_tuning")
+        self._apply_bake_mode(t)
+
+    def _apply_bake_mode(self, tuning):
+        """abi.Tuning's `bounce_bake` is carried beside the C struct (abi.Tuning.BINDING_FIELDS): handed over through its own setter"""
+        if hasattr(self._L, "tinsel_hip_set_bounce_bake"):
+            _check(self._L.tinsel_hip_set_bounce_bake(self._h, int(tuning.bounce_bake)), "tinsel_hip_set_bounce_bake")
+            self._bake_mode = int(tuning.bounce_bake)
 
     def plane_table(self):
         """tinsel_hip_plane_table: (opposing pairs, single planes) of the flat scan's plane table in force"""
@@ -840,6 +892,8 @@ class HipRenderer:
     def get_tuning(self):
         t = abi.Tuning()
         _check(self._L.tinsel_hip_get_tuning(self._h, C.byref(t)), "tinsel_hip_get_tuning")
+        if hasattr(self._L, "tinsel_hip_get_bounce_bake"):
+            t.bounce_bake = int(self._L.tinsel_hip_get_bounce_bake(self._h))
         return t
 
     def set_arithmetic(self, mode):
@@ -901,8 +955,46 @@ class HipRenderer:
         _check(self._L.tinsel_hip_set_russian_roulette(self._h, int(start_bounce)), "tinsel_hip_set_russian_roulette")
 
     def reserve(self, passes, max_depth):
-        """Pre-allocates the path buffers for renders of up to `passes` passes at `max_depth`."""
+        """Pre-allocates the path buffers for renders of up to `passes` passes at `max_depth`.  Where the plan picks the fused kernel's closed
+        instance, this is also where its baked instance is compiled (or found in the cache) and installed: always with the bake mode
+        (abi.Tuning's bounce_bake, tinsel_hip_set_bounce_bake) 1, by default (-1) for reservations of abi.BAKE_AUTO_MIN_PATHS path slots or
+        more, never with 0.  With mode 1 the first render after a change of the scene level bakes too (render, render_async)."""
         _check(self._L.tinsel_hip_reserve(self._h, int(passes), int(max_depth)), "tinsel_hip_reserve")
+        want = self.get_tuning().bounce_bake if hasattr(self._L, "tinsel_hip_bake_source") else 0
+        if want > 0 or (want < 0 and int(passes)*self.width*self.height >= abi.BAKE_AUTO_MIN_PATHS):
+            self.bake()
+
+    def bake_source(self):
+        """tinsel_hip_bake_source: (text, key, bakeable, why) for the scene level in force (Scene.bake_source is the description's twin)"""
+        return _bake_source(lambda buf, cap, key, ok: self._L.tinsel_hip_bake_source(self._h, buf, cap, key, ok))
+
+    def bake(self):
+        """Compiles (tinsel_amd.build.bake: a child process, cached by key) and installs the baked instance of the scene level in force, where
+        the plan would pick the closed instance and none is installed for this key yet.  Never an error: without a compiler, or where the
+        compile fails or its code object is refused (build.bake), the library's own instance keeps running and bake_status() says so; a key
+        that did not install is not tried again until the scene level, and with it the key, changes.  Returns bake_status()."""
+        from . import build as hb
+        st = self.bake_status()
+        if st["state"] in (abi.BAKE_NONE, abi.BAKE_STALE, abi.BAKE_NO_COMPILER):
+            text, key, ok, _ = self.bake_source()
+            if key == self._bake_failed_key:
+                return st
+            image, how = hb.bake(text, key) if ok else (None, None)
+            self._bake_failed_key = key if (ok and image is None) else None
+            if image is not None:
+                _check(self._L.tinsel_hip_install_baked(self._h, image, len(image), key.encode(), abi.BAKE_FROM_CACHE if how == "cache" else abi.BAKE_COMPILED),
+                       "tinsel_hip_install_baked")
+            elif ok:
+                _check(self._L.tinsel_hip_install_baked(self._h, None, 0, None, abi.BAKE_NO_COMPILER), "tinsel_hip_install_baked")
+            st = self.bake_status()
+        return st
+
+    def bake_status(self):
+        """tinsel_hip_bake_status: {"state": abi.BAKE_*, "key": the installed module's key or "", "launches": launches it has served}"""
+        out = (C.c_uint32*3)()
+        key = C.create_string_buffer(65)
+        _check(self._L.tinsel_hip_bake_status(self._h, out, key), "tinsel_hip_bake_status")
+        return {"state": int(out[0]), "key": key.value.decode(), "launches": int(out[1]) | (int(out[2]) << 32)}
 
     def get_pass_index(self):
         """Index of the next pass (its seed is the (index+1)-th output of Random(1).Rand())."""
