@@ -560,6 +560,56 @@ int tinsel_hip_render_light_groups_device(tinsel_hip* r, const tinsel_camera* ca
                                           uint32_t pass_begin, int passes, int num_groups, const int32_t* group_of_primitive, int env_group,
                                           float* out_dev, void* stream);
 
+/* Depth planes: the beauty at SEVERAL PATH DEPTHS in one trace of the paths -- direct and indirect light for the compositor and the
+ * denoiser (indirect light is the noisy part and takes the stronger filter), and what every further bounce adds for whoever picks
+ * max_depth, without one render per depth that retraces the bounces before it.  The integrator adds to a path's radiance bounce by bounce,
+ * and nothing it draws or decides at bounce i depends on max_depth except that the loop stops: a path's radiance after the iteration
+ * i = d - 1 IS PathTrace(..., maxDepth = d).
+ * Plane k of `out`, out[((k*H + j)*W + i)*4 + c], is DEFINED as the accumulator tinsel_hip_render gives from a zeroed accumulator at pass
+ * index pass_begin after `passes` passes with options->max_depth replaced by depths[k]: bit for bit in all four channels, the weight
+ * included, wherever that render is finite.  It follows that
+ *   - options->max_depth is not read: the trace runs to depths[num_planes - 1];
+ *   - options->clamp applies to EACH PLANE SEPARATELY (ClampLength is applied per sample): with a finite clamp a deeper plane's colour may
+ *     be below a shallower one's; with clamp = FLT_MAX the colour never decreases from plane to plane (every term is non-negative);
+ *   - the renderer's Russian-roulette setting applies: roulette after bounce b changes only what comes later;
+ *   - the weight channel of every plane is the beauty's.
+ * depths: a HOST array of num_planes int32, strictly ascending, 1 <= depths[0], depths[num_planes - 1] <= TINSEL_MAX_PLANE_DEPTH; read
+ * before the call returns.  flags: TINSEL_DEPTH_PLANES_ADD adds the passes to what `out` holds instead of starting every plane from zero --
+ * the passes [0, a) followed by [a, b) with the flag equal [0, b) in one call, bit for bit; TINSEL_DEPTH_PLANES_ACCUMULATE_SINGLY adds every
+ * plane's batch with a launch of the render's own accumulate kernels instead of one launch for all planes of a batch (the same bits; the
+ * A/B arm, and what filters wider than 2 take anyway).
+ * The call traces the camera's paths through the split pipeline whatever tinsel_hip_set_pipeline says (k_generate, k_extend, k_lights,
+ * k_shadow and the walk and segment kernels as a render plans them; the shading kernel is k_shade_depths, timed under the name "k_shade" in
+ * tinsel_hip_kernel_times -- the name table does not grow): at the end of a bounce's shading the path's own lane writes its radiance, one
+ * 16-byte record, into the plane whose depth that bounce completes, and a path that ends early into every deeper plane too, so every
+ * (path, plane) record is written exactly once.  Then one "k_accumulate" per batch (k_views_accumulate, the planes as its second grid
+ * dimension) or per plane and batch.  The seeds, the planes' records and the statistics the kernels count into are the call's own: the
+ * accumulator, the pass index, the renderer's seed table and tinsel_hip_stats are left as they were, and a render, a depth-planes call and
+ * the render that follows give the images of the two renders alone.  The paths themselves live in the renderer's path buffers, used under
+ * the fences of the radiance queries.
+ * Returns -1 before anything is launched or written for: a null argument, passes < 1, num_planes outside 1 .. TINSEL_MAX_DEPTH_PLANES, a
+ * depths array that is not strictly ascending inside 1 .. TINSEL_MAX_PLANE_DEPTH, unknown flag bits, another mode than
+ * TINSEL_MODE_PATHTRACE, a frame size that does not match the last tinsel_hip_init, a moved primitive without tinsel_hip_rebuild_scene, a
+ * sharded renderer (world > 1), TINSEL_ARITH_FAST (the contract is a bit contract), and for the device entry an out_dev that is not
+ * 16-byte aligned.
+ * Memory, kept until tinsel_hip_destroy: 16 bytes x num_planes per path slot of a batch -- a batch holds whole passes, and those bytes count
+ * against batch_paths beside the 176 bytes of a path's own state: max(1, floor(batch_paths*176/(176 + 16*num_planes) / (W*H))) passes --
+ * plus 4 bytes per pass for the seeds, and for the host entry num_planes*W*H*16 bytes of planes. */
+#define TINSEL_MAX_DEPTH_PLANES 16
+#define TINSEL_MAX_PLANE_DEPTH  64
+#define TINSEL_DEPTH_PLANES_ADD                1   /* add to what `out` holds instead of starting every plane from zero */
+#define TINSEL_DEPTH_PLANES_ACCUMULATE_SINGLY  2   /* one launch of the render's own accumulate kernels per plane (the A/B arm and the fallback) */
+
+/* host array of num_planes*W*H*4 floats (read first with TINSEL_DEPTH_PLANES_ADD); returns when it is written */
+int tinsel_hip_render_depth_planes(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                   uint32_t pass_begin, int passes, int num_planes, const int32_t* depths, int flags,
+                                   float* out_host);
+/* device array, 16-byte aligned; enqueued on `stream` (NULL: the default stream) and not waited for.  The stream waits, on the device, for
+ * what the renderer's path buffers still serve and for an earlier depth-planes call on another stream. */
+int tinsel_hip_render_depth_planes_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options,
+                                          uint32_t pass_begin, int passes, int num_planes, const int32_t* depths, int flags,
+                                          float* out_dev, void* stream);
+
 /* View batches: the frames of MANY cameras on the one resident scene in one call -- the faces of a cube map, a stereo pair, a turntable,
  * a few hundred small views as a training set -- where a loop over tinsel_hip_set_pass_index and tinsel_hip_render pays every launch of
  * every bounce and an accumulate launch of a few tiles once per view.

@@ -174,6 +174,13 @@ MAX_LIGHT_GROUPS = 8
 # tinsel_hip_render_views*: the most views a call takes, and its flags
 MAX_VIEWS = 4096
 VIEWS_ADD, VIEWS_ACCUMULATE_SINGLY = 1, 2
+# tinsel_hip_render_depth_planes*: the most planes a call takes, the deepest plane, its flags, and the entries' signatures -- renderer,
+# camera, options, pass_begin, passes, num_planes, depths (host int32 [num_planes]), flags, out (, stream)
+MAX_DEPTH_PLANES = 16
+MAX_PLANE_DEPTH = 64
+DEPTH_PLANES_ADD, DEPTH_PLANES_ACCUMULATE_SINGLY = 1, 2
+RENDER_DEPTH_PLANES_ARGTYPES = [C.c_void_p, C.POINTER(Camera), C.POINTER(Options), C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+RENDER_DEPTH_PLANES_DEVICE_ARGTYPES = RENDER_DEPTH_PLANES_ARGTYPES + [C.c_void_p]
 # tinsel_hip_render_sample_map*: the largest count of a pixel (a uint16), its flag, and the entries' signatures -- renderer, camera,
 # options, pass_begin, counts (host uint16 [H*W]), flags, out (, stream); slot_limit, width, height, counts, out4
 SAMPLE_MAP_MAX = 65535

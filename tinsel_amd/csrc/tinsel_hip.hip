@@ -76,7 +76,8 @@ int fail(const std::string& msg)
 #include "tn_host_ids.h"          // ID mattes: the hit primitive of the camera's own paths, gathered into ranked per-pixel (id, weight) lists
 #include "tn_host_light_groups.h" // light groups: the beauty split per emitter group, k_shade_groups behind a render's split plan
 #include "tn_host_views.h"        // view batches: many cameras' frames in one call, k_generate_views in front of a query's pipeline, k_views_accumulate behind it
-#include "tn_host_samples.h"      // sample maps: a per-pixel pass count on compact slots, k_generate_samples in front of a query's pipeline, k_samples_accumulate behind it
+#include "tn_host_depth_planes.h" // depth planes: the beauty at several path depths in one trace, k_shade_depths behind a render's split plan, k_views_accumulate behind it
+#include "tn_host_samples.h"     // sample maps: a per-pixel pass count on compact slots, k_generate_samples in front of a query's pipeline, k_samples_accumulate behind it
 #include "tn_host_denoise.h"      // the feature-guided denoise stage on linear radiance
 #include "tn_host_lookahead.h"    // the one-pass-per-call pattern
 #include "tn_host_bvh_build.h"    // device BVH build

@@ -300,6 +300,39 @@ int tinsel_hip_render_light_groups(tinsel_hip* r, const tinsel_camera* camera, c
     return 0;
 }
 
+// Depth planes (tn_split.h k_shade_depths, tn_host_depth_planes.h): the beauty at several path depths in one trace of the camera's paths
+// through the split pipeline.  Own seeds, own planes, own statistics block: nothing of the renderer's frame state is written; the path
+// buffers are used under the radiance queries' fences, look-ahead work in flight is waited for on the device and kept.
+int tinsel_hip_render_depth_planes_device(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                          int num_planes, const int32_t* depths, int flags, float* out_dev, void* stream)
+{
+    const char* const who = "render_depth_planes_device";
+    if (depth_planes_args(r, camera, options, passes, num_planes, depths, flags, out_dev, who))
+        return -1;
+    if (query_arrays({ { out_dev, (size_t)r->width*r->height*sizeof(float4)*(size_t)num_planes } }, who) || query_ready(r, who))
+        return -1;
+    return depth_planes_enqueue(r, camera, options, pass_begin, passes, num_planes, depths, flags, (float4*)out_dev, (hipStream_t)stream);
+}
+
+int tinsel_hip_render_depth_planes(tinsel_hip* r, const tinsel_camera* camera, const tinsel_options* options, uint32_t pass_begin, int passes,
+                                   int num_planes, const int32_t* depths, int flags, float* out_host)
+{
+    const char* const who = "render_depth_planes";
+    if (depth_planes_args(r, camera, options, passes, num_planes, depths, flags, out_host, who) || query_ready(r, who))
+        return -1;
+    const size_t bytes = (size_t)r->width*r->height*sizeof(float4)*(size_t)num_planes;
+    if (query_buffer(r->depthsOut, bytes))
+        return -1;
+    // (the staging planes are the host entry's alone, and it returns when they have been read: nothing in flight touches them)
+    if (flags & TINSEL_DEPTH_PLANES_ADD)
+        HIP_TRY(hipMemcpy(r->depthsOut.get(), out_host, bytes, hipMemcpyHostToDevice));
+    if (depth_planes_enqueue(r, camera, options, pass_begin, passes, num_planes, depths, flags, (float4*)r->depthsOut.get(), nullptr))
+        return -1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_host, r->depthsOut.get(), bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // View batches (tn_views.h, tn_host_views.h): the frames of many cameras in one call, k_generate_views in front of a radiance query's
 // pipeline and one accumulate launch per batch of views behind it.  Own seeds, own radiance, own statistics block: nothing of the
 // renderer's frame state is written; the path buffers are used under the radiance queries' fences, look-ahead work in flight is waited for

@@ -664,9 +664,12 @@ struct BatchPlan
 // perPass x perBatch paths per batch; mayOverlap: the batch may be traced as two chunks (not for a look-ahead, not for tinsel_hip_reserve);
 // generate: the kernel that makes the batch's paths -- the camera's, or a query's, a views call's or a sample map's (PK_GENERATE_RAYS / _GATHER / _VIEWS / _SAMPLES), which run radiance_pipeline's choice;
 // groups: a light-groups call's batch (tn_host_light_groups.h) -- the split pipeline whatever the setting, planned as a render's, with
-// k_shade's GROUPS twin as its shading kernel (k_shade_sorted has none)
-BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE, bool groups = false)
+// k_shade's GROUPS twin as its shading kernel (k_shade_sorted has none); SIDE_DEPTHS: a depth-planes call's (tn_host_depth_planes.h), the
+// same with the DEPTHS twin
+enum { SIDE_NONE = 0, SIDE_GROUPS, SIDE_DEPTHS };
+BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool mayOverlap, int generate = PK_GENERATE, int side = SIDE_NONE)
 {
+    const bool groups = side != SIDE_NONE;          // (what the plan makes of a side call: the split pipeline, k_shade's plain loop)
     BatchPlan p;
     p.generate = generate;
     p.pipeline = groups ? (int)TINSEL_PIPELINE_WAVEFRONT_SPLIT : generate == PK_GENERATE ? resolve_pipeline(r) : radiance_pipeline(r);
@@ -762,8 +765,10 @@ BatchPlan plan_batch(const tinsel_hip* r, size_t perPass, int perBatch, bool may
     p.step = wl == 2 ? PK_STEP_W2_MIXED : wl && mixed ? PK_STEP_W1_MIXED : wl ? PK_STEP_W1 : mixed ? PK_STEP_MIXED : lds ? PK_STEP_LDS : PK_STEP;
     p.lights = lightsDrawn ? PK_NONE : mixed ? PK_LIGHTS_MIXED : lds ? PK_LIGHTS_LDS : PK_LIGHTS;
     p.shade = sorted ? (mixedShade ? PK_SHADE_SORTED_MIXED : lds ? PK_SHADE_SORTED_LDS : PK_SHADE_SORTED) : (mixedShade ? PK_SHADE_MIXED : lds ? PK_SHADE_LDS : PK_SHADE);
-    if (groups)
+    if (side == SIDE_GROUPS)
         p.shade = p.shade == PK_SHADE_MIXED ? PK_SHADE_GROUPS_MIXED : p.shade == PK_SHADE_LDS ? PK_SHADE_GROUPS_LDS : PK_SHADE_GROUPS;
+    if (side == SIDE_DEPTHS)
+        p.shade = p.shade == PK_SHADE_MIXED ? PK_SHADE_DEPTHS_MIXED : p.shade == PK_SHADE_LDS ? PK_SHADE_DEPTHS_LDS : PK_SHADE_DEPTHS;
     // (the detail-counting variants walk the scene BVH: nothing to defer)
     p.bounce = count ? (lds ? PK_BOUNCE_COUNT_LDS : PK_BOUNCE_COUNT) : r->scene.deferMeshes ? (lds ? PK_BOUNCE_LDS_DEFER : PK_BOUNCE_DEFER) : lds ? PK_BOUNCE_LDS : PK_BOUNCE;
     p.bounceShared = p.bounce;
@@ -1426,12 +1431,13 @@ struct CallerPaths
 };
 
 // What a side call over the camera's own paths replaces of a render's batch (light groups): the seed table k_generate reads, the statistics
-// the kernels count into, the planes k_shade_groups deposits into.  Null / zero: the renderer's own.
+// the kernels count into, the planes k_shade_groups deposits into or k_shade_depths writes (depth planes).  Null / zero: the renderer's own.
 struct TraceOverrides
 {
     const uint32_t* passSeeds = nullptr;
     unsigned long long* stats = nullptr;
     GroupState groups = { nullptr, nullptr, -1, 0u };
+    DepthState depths = { nullptr, 0ull, 0u };
 };
 
 // The launches of one batch of `slots` paths in lane L, by the plan's pipeline; a finished path's radiance goes to rad[its slot].  The paths
@@ -1465,6 +1471,7 @@ int trace_batch(tinsel_hip* r, const BatchPlan& p, tinsel_hip::DenseLane& L, hip
         a.passSeeds = over->passSeeds ? over->passSeeds : a.passSeeds;
         a.ctl.stats = over->stats ? over->stats : a.ctl.stats;
         a.groups = over->groups;
+        a.depths = over->depths;
     }
     a.walkRec = p.walk ? L.walkRec : nullptr;
     a.walkPrims = (uint32_t)r->walkPrims.count;

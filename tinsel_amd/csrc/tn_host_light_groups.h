@@ -67,7 +67,7 @@ int light_groups_enqueue(tinsel_hip* r, const tinsel_camera* camera, const tinse
         r->groupsTableHost = table;
     }
 
-    const BatchPlan plan = plan_batch(r, perPass, perBatch, /*mayOverlap*/ false, PK_GENERATE, /*groups*/ true);
+    const BatchPlan plan = plan_batch(r, perPass, perBatch, /*mayOverlap*/ false, PK_GENERATE, SIDE_GROUPS);
     if (ensure_batch(r, plan, fp.maxDepth) || batch_fence_wait(r, st) || own_streams_wait(r, st))
         return -1;
     if (r->groupsFencePending && r->groupsFenceStream != st)

@@ -221,6 +221,15 @@ struct tinsel_hip
     Event groupsFence;
     hipStream_t groupsFenceStream = nullptr;
     bool groupsFencePending = false;
+    // depth planes (tinsel_hip_render_depth_planes*, tn_host_depth_planes.h): the planes' records of a batch (16 bytes per plane and path
+    // slot), the call's own seed table, the statistics its kernels count into (never read), the host entry's planes -- grown on demand, freed
+    // with the renderer -- and the event behind the last call's last launch, which a call on another stream waits for before it writes them
+    DevBuf<unsigned char> depthsRec, depthsOut;
+    DevBuf<uint32_t> depthsSeeds;
+    DevBuf<unsigned long long> depthsStats;
+    Event depthsFence;
+    hipStream_t depthsFenceStream = nullptr;
+    bool depthsFencePending = false;
     // view batches (tinsel_hip_render_views*, tn_host_views.h): the radiance of a batch's paths by slot ([view][pass][pixel]), the cameras'
     // table, the call's own seed table, the statistics its kernels count into (never read), the host entry's planes -- grown on demand,
     // freed with the renderer -- and the event behind the last call's last launch, which a call on another stream waits for before it

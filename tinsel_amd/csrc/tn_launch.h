@@ -99,7 +99,10 @@ namespace tn {
     X(PK_SHADE_GROUPS_LDS,      kBlock, 0, SHADE_GROUPS, k_shade_groups<true>)                                      \
     X(PK_SHADE_GROUPS,          kBlock, 0, SHADE_GROUPS, k_shade_groups<false>)                                     \
     X(PK_GENERATE_VIEWS,        kBlock, 0, GENERATE_VIEWS, k_generate_views)                                        \
-    X(PK_GENERATE_SAMPLES,      kBlock, 0, GENERATE_SAMPLES, k_generate_samples)
+    X(PK_GENERATE_SAMPLES,      kBlock, 0, GENERATE_SAMPLES, k_generate_samples)                                    \
+    X(PK_SHADE_DEPTHS_MIXED,    kBlock, 0, SHADE_DEPTHS, k_shade_depths<true, true>)                                \
+    X(PK_SHADE_DEPTHS_LDS,      kBlock, 0, SHADE_DEPTHS, k_shade_depths<true>)                                      \
+    X(PK_SHADE_DEPTHS,          kBlock, 0, SHADE_DEPTHS, k_shade_depths<false>)
 
 enum PathKernel : int
 {
@@ -139,6 +142,7 @@ struct LaunchArgs
     GroupState groups;              // k_shade_groups
     ViewsJob views;                 // k_generate_views
     SamplesJob samples;             // k_generate_samples
+    DepthState depths;              // k_shade_depths
 };
 
 #define TN_ARGS_GENERATE a.ss, a.ctl, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
@@ -160,6 +164,7 @@ struct LaunchArgs
 #define TN_ARGS_FEATURES a.scene, a.features, a.cam, a.fp, a.passSeeds, a.stackEntries
 #define TN_ARGS_SHADE_GROUPS TN_ARGS_SHADE, a.groups
 #define TN_ARGS_GENERATE_VIEWS a.ss, a.ctl, a.views, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
+#define TN_ARGS_SHADE_DEPTHS TN_ARGS_SHADE, a.depths
 #define TN_ARGS_GENERATE_SAMPLES a.ss, a.ctl, a.samples, a.cam, a.fp, a.passSeeds, a.scene.primBoxes, a.bins
 
 // false: a.variant is not in the list (nothing is launched)

@@ -334,6 +334,19 @@ struct GroupState
     uint32_t stride;        // slots per plane
 };
 
+// Depth planes (tinsel_hip_render_depth_planes*): what k_shade_depths is handed beside the SplitState, as GroupState is.  Plane k holds a
+// path's radiance after the bounce depths[k] - 1, or after its last bounce where it ends sooner: what PathTrace returns with maxDepth =
+// depths[k].  Addressed by the slot the path carries; the lane that owns the path is the only writer, and every (slot, plane) record of a
+// batch is written exactly once (shade_path's DEPTHS form), so nothing is zeroed.
+constexpr int kMaxDepthPlanes = 16;
+constexpr int kMaxPlaneDepth = 64;
+struct DepthState
+{
+    float4* rec;            // [k*stride + slot] plane k's radiance of the batch's paths, laid out as the accumulate kernels read radOut
+    uint64_t mask;          // bit d - 1 set: depth d is asked for; plane k is the k-th set bit, the highest one the depth the trace runs to
+    uint32_t stride;        // slots per plane
+};
+
 TN_D uint32_t wave_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 // this wave's index in its workgroup, as a SCALAR (threadIdx.x/64 is wave-uniform, but only readfirstlane tells the compiler: what hangs off it --
 // region index, base, length, pool pointer -- then lives in SGPRs, or their spill lanes, instead of a VGPR each)

@@ -488,9 +488,13 @@ TN_D void group_deposit(const GroupState& gs, int g, uint32_t slot, V3 term)
 // samples, the BSDF step; true when the path goes on (its state in `p`, `front`: its next ray enters a mesh in HBM)
 // GROUPS (k_shade_groups, light groups): every term the integrator adds to totalRadiance is also deposited into the plane of its emitter's
 // group (gs->grp), and the path's own radiance goes nowhere -- the call reads the planes.
-template <class SC, bool GROUPS = false>
+// DEPTHS (k_shade_depths, depth planes): the path keeps its radiance, and at the end of the bounce's shading -- every term of the iteration
+// added -- the lane writes it as one 16-byte record into the planes whose depth this bounce completes for the path (ds->rec): plane k
+// where bounce + 1 == depths[k] and the path goes on; every plane with depths[k] >= bounce + 1 where it ends here (a miss, a light hit,
+// pdf <= 0, roulette, the trace's own depth).  Every (slot, plane) record is written exactly once, by the path's own lane.
+template <class SC, bool GROUPS = false, bool DEPTHS = false>
 TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int bounce, int maxDepth, int rrStart, const BinPrims& bp,
-                     PathRegs& p, uint32_t& slot, bool& front, const GroupState* gs = nullptr)
+                     PathRegs& p, uint32_t& slot, bool& front, const GroupState* gs = nullptr, const DepthState* ds = nullptr)
 {
     const int K = ss.neePerPath;
     bool alive = false;
@@ -588,7 +592,22 @@ TN_D bool shade_path(SC& sc, const SplitState& ss, const ShadeFetch& f, int boun
         if (alive)
             front = bp.count == 0 || ray_enters_big_mesh(sc.primBoxes, bp, p.o, p.d);
     }
-    if constexpr (!GROUPS)
+    if constexpr (DEPTHS)
+    {
+        // (bit 0 of `from`: depth bounce + 1; the planes below it were written at their own bounces)
+        const float4 rec = make_float4(p.rad.x, p.rad.y, p.rad.z, 0.0f);
+        const uint64_t from = ds->mask >> bounce;
+        float4* at = ds->rec + (size_t)__builtin_popcountll(ds->mask & ((1ull << bounce) - 1ull))*ds->stride + slot;
+        if (alive)
+        {
+            if (from & 1ull)
+                *at = rec;
+        }
+        else
+            for (uint64_t m = from; m; m &= m - 1ull, at += ds->stride)
+                *at = rec;
+    }
+    else if constexpr (!GROUPS)
         if (!alive)
             ss.radOut[slot] = make_float4(p.rad.x, p.rad.y, p.rad.z, __int_as_float(p.rayType));
     return alive;
@@ -671,6 +690,49 @@ __global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade_groups(DevScen
             uint32_t slot = 0;
             if (j < n)
                 alive = shade_path<SceneT<LDS, false, 2, MIXED>, true>(sc, ss, f, bounce, maxDepth, rrStart, bp, p, slot, front, &gs);
+            const uint32_t np = out.push(alive, front);
+            if (alive)
+                store_state(ss, nxt, np, p, slot);
+        }
+        if (lane == 0)
+        {
+            ss.segFront[(size_t)(bounce + 1)*ss.numRegions + r] = out.nFront;
+            ss.segBack[(size_t)(bounce + 1)*ss.numRegions + r] = out.nBack;
+        }
+    }
+}
+
+// k_shade_depths: k_shade for tinsel_hip_render_depth_planes* -- the same loop over the same state, shade_path's DEPTHS form, and the planes as
+// an argument of its own behind k_shade's (a kernel of its own name, as k_shade_groups)
+template <bool LDS, bool MIXED = false>
+__global__ __launch_bounds__(kBlock, TN_WAVES_SHADE) void k_shade_depths(DevScene scIn, SplitState ss, int bounce, int maxDepth, int rrStart, BinPrims bp,
+                                                                         const uint32_t* __restrict__ order, DepthState ds)
+{
+    extern __shared__ uint32_t s_arena[];
+    SceneT<LDS, false, 2, MIXED> sc;
+    stage_scene_lds(sc, scIn, s_arena);
+    const uint32_t lane = __lane_id();
+    const int cur = bounce & 1, nxt = cur ^ 1;
+    const int K = ss.neePerPath;
+    const bool hasMedia = sc.hasMedia != 0;
+
+    for (uint32_t b = blockIdx.x; b < ss.numRegions/kRegionsPerBlock; b += gridDim.x)
+    {
+        const uint32_t r = (order ? order[b] : b)*kRegionsPerBlock + wave_in_block();
+        const uint32_t nFront = wave_uniform(ss.segFront[(size_t)bounce*ss.numRegions + r]);
+        const uint32_t n = nFront + wave_uniform(ss.segBack[(size_t)bounce*ss.numRegions + r]);
+        const uint32_t rBase = region_base(ss, r), rLen = region_len(ss, r);
+        RegionAppend out = { rBase, rLen, 0u, 0u };
+        for (uint32_t j0 = 0; j0 < n; j0 += kWave)
+        {
+            const uint32_t j = j0 + lane;
+            ShadeFetch f;
+            f.issue(ss, cur, region_pos(rBase, rLen, nFront, j < n ? j : 0u), j < n, hasMedia, K > 0, bounce == 0);
+            bool alive = false, front = true;
+            PathRegs p;
+            uint32_t slot = 0;
+            if (j < n)
+                alive = shade_path<SceneT<LDS, false, 2, MIXED>, false, true>(sc, ss, f, bounce, maxDepth, rrStart, bp, p, slot, front, nullptr, &ds);
             const uint32_t np = out.push(alive, front);
             if (alive)
                 store_state(ss, nxt, np, p, slot);

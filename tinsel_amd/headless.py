@@ -8,6 +8,7 @@
                                   [-features=features.npz] [-features_spp=N] [-denoise[=RADIUS]]
                                   [-mattes=FILE.npz] [-mattes_spp=N] [-mattes_slots=K]
                                   [-lightgroups=FILE.npz] [-lightgroups_spp=N]
+                                  [-depthplanes=FILE.npz] [-depthplanes_spp=N] [-depthplanes_at=D1,D2,...]
                                   [-views=FILE.npz -views_orbit=N] [-views_spp=S] [-views_center=X,Y,Z]
                                   [-samplemap=COUNTS.npy -samplemap_out=FILE.npz] [-samplemap_begin=N]
                                   scene.pack
@@ -65,6 +66,12 @@ the render's own passes [0, -lightgroups_spp) (default min(spp, 16), as -feature
 plane per group of tinsel_amd.default_light_groups -- every emitting primitive its own, the environment last.  The file holds `planes`
 [G, H, W, 4] float32 (accumulators: the render's clamp applies per plane), `group_of_primitive`, `env_group`, `names` and `passes`;
 tinsel_amd.relight mixes the planes.  Refused with what -features is refused with.
+-depthplanes=FILE.npz writes, beside a normal render, the beauty at several path depths from one trace (HipRenderer.depth_planes): the
+render's own passes [0, -depthplanes_spp) (default min(spp, 16), as -features_spp), one plane per depth of -depthplanes_at (strictly
+ascending, 1 .. 64, 16 at most; default 1 .. the render's max depth) -- plane k what the render gives with -maxdepth=depths[k].  The file
+holds `planes` [n, H, W, 4] float32 (accumulators: the render's clamp applies per plane), `depths` and `passes`;
+tinsel_amd.depth_contributions turns the planes into direct light and each further bounce's share.  Refused with what -features is
+refused with.
 -views=FILE.npz -views_orbit=N writes, beside a normal render, a turntable of the scene in one call (HipRenderer.views): N views of the
 scene's camera turned about the vertical through -views_center (default: what the camera sees at the centre of the frame, first_hit; the
 origin if that ray leaves the scene) by tinsel_amd.orbit_cameras, passes [0, -views_spp) (default min(spp, 16), as -features_spp) each --
@@ -101,6 +108,7 @@ def parse_args(argv):
     cfg = {"file": argv[-1], "out": None, "nlm": 0, "nlm_falloff": 200.0, "save": None, "resume": None, "complexity": None, "firsthit": None, "irradiance": None,
            "irradiance_spp": 64, "probes": None, "probes_at": None, "probes_spp": 1024, "probes_order": 2, "features": None, "features_spp": None,
            "mattes": None, "mattes_spp": None, "mattes_slots": None, "lightgroups": None, "lightgroups_spp": None,
+           "depthplanes": None, "depthplanes_spp": None, "depthplanes_at": None,
            "views": None, "views_orbit": None, "views_spp": None, "views_center": None,
            "samplemap": None, "samplemap_out": None, "samplemap_begin": None,
            "denoise": None, "over": {}}
@@ -120,7 +128,7 @@ def parse_args(argv):
             cfg["nlm"] = int(parts[0])
             if len(parts) > 1:
                 cfg["nlm_falloff"] = float(parts[1])
-        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups", "views", "samplemap",
+        elif k in ("out", "save", "resume", "firsthit", "irradiance", "probes", "probes_at", "features", "mattes", "lightgroups", "depthplanes", "views", "samplemap",
                    "samplemap_out"):
             cfg[k] = v
         elif k == "denoise":
@@ -147,6 +155,18 @@ def parse_args(argv):
             cfg[k] = int(v)
             if cfg[k] < 1:
                 raise SystemExit("-lightgroups_spp=%s: want 1 or more" % v)
+        elif k == "depthplanes_spp":
+            cfg[k] = int(v)
+            if cfg[k] < 1:
+                raise SystemExit("-depthplanes_spp=%s: want 1 or more" % v)
+        elif k == "depthplanes_at":
+            try:
+                cfg[k] = tuple(int(x) for x in v.split(","))
+            except ValueError:
+                raise SystemExit("-depthplanes_at=%s: want D1,D2,..." % v)
+            if not 1 <= len(cfg[k]) <= abi.MAX_DEPTH_PLANES or cfg[k][0] < 1 or cfg[k][-1] > abi.MAX_PLANE_DEPTH or \
+                    any(b <= a for a, b in zip(cfg[k], cfg[k][1:])):
+                raise SystemExit("-depthplanes_at=%s: want 1 .. %d depths, strictly ascending, in 1 .. %d" % (v, abi.MAX_DEPTH_PLANES, abi.MAX_PLANE_DEPTH))
         elif k == "mattes_spp":
             cfg[k] = int(v)
             if cfg[k] < 1:
@@ -331,6 +351,22 @@ def lightgroups(r, scene, cam, opt, cfg):
     print("wrote %s: %dx%d, %d passes, %d groups (%s) in %.3fms" % (cfg["lightgroups"], opt.width, opt.height, n, len(names), ", ".join(names), ms))
 
 
+def depthplanes(r, cam, opt, cfg):
+    """-depthplanes: the render's own samples of passes [0, N) at several path depths (tinsel_hip_render_depth_planes)"""
+    n = cfg["depthplanes_spp"] if cfg["depthplanes_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
+    depths = cfg["depthplanes_at"]
+    if depths is None:
+        if not 1 <= int(opt.max_depth) <= abi.MAX_DEPTH_PLANES:
+            raise SystemExit("-depthplanes: the render's max depth is %d, name %d depths at most with -depthplanes_at" % (int(opt.max_depth), abi.MAX_DEPTH_PLANES))
+        depths = tuple(range(1, int(opt.max_depth) + 1))
+    ts = time.perf_counter()
+    planes = r.depth_planes(cam, opt, 0, n, depths)
+    ms = (time.perf_counter() - ts)*1000.0
+    np.savez(cfg["depthplanes"], passes=np.int64(n), planes=planes, depths=np.array(depths, np.int32))
+    print("wrote %s: %dx%d, %d passes, %d depths (%s) in %.3fms" % (cfg["depthplanes"], opt.width, opt.height, n, len(depths),
+                                                                  ", ".join(str(d) for d in depths), ms))
+
+
 def views(r, cam, opt, cfg):
     """-views: a turntable of N cameras about the vertical through the centre, the passes [0, S) of each in one call (tinsel_hip_render_views)"""
     n = cfg["views_spp"] if cfg["views_spp"] else max(1, min(int(opt.max_samples), FRAME_PASSES))
@@ -395,6 +431,12 @@ def main(argv=None):
     if cfg["lightgroups"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
                                cfg["probes_at"]):
         raise SystemExit("-lightgroups writes the light groups of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
+                         "-firsthit, -irradiance or -probes")
+    if (cfg["depthplanes_spp"] or cfg["depthplanes_at"]) and not cfg["depthplanes"]:
+        raise SystemExit("-depthplanes_spp and -depthplanes_at go with -depthplanes=OUT.npz")
+    if cfg["depthplanes"] and ("%" in cfg["file"] or cfg["resume"] or cfg["complexity"] or cfg["firsthit"] or cfg["irradiance"] or cfg["probes"] or
+                               cfg["probes_at"]):
+        raise SystemExit("-depthplanes writes the depth planes of a normal render's passes [0, N): no batch mode, no -resume, -complexity, "
                          "-firsthit, -irradiance or -probes")
     if bool(cfg["views"]) != bool(cfg["views_orbit"]) or ((cfg["views_spp"] or cfg["views_center"]) and not cfg["views"]):
         raise SystemExit("-views=OUT.npz and -views_orbit=N go together; -views_spp and -views_center go with them")
@@ -473,6 +515,8 @@ def main(argv=None):
         mattes(r, cam, opt, cfg)
     if cfg["lightgroups"]:
         lightgroups(r, scene, cam, opt, cfg)
+    if cfg["depthplanes"]:
+        depthplanes(r, cam, opt, cfg)
     if cfg["views"]:
         views(r, cam, opt, cfg)
     if cfg["samplemap"]:

@@ -112,6 +112,9 @@ def load_library():
         L.tinsel_hip_render_views.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp]
         L.tinsel_hip_render_views_device.argtypes = [vp, C.POINTER(abi.Camera), ci, C.POINTER(abi.Options), C.c_uint32, ci, C.c_uint, vp, vp]
         L.tinsel_hip_plan_views.argtypes = [C.c_ulonglong, ci, ci, ci, ci, C.POINTER(C.c_int)]
+    if hasattr(L, "tinsel_hip_render_depth_planes"):   # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
+        L.tinsel_hip_render_depth_planes.argtypes = abi.RENDER_DEPTH_PLANES_ARGTYPES
+        L.tinsel_hip_render_depth_planes_device.argtypes = abi.RENDER_DEPTH_PLANES_DEVICE_ARGTYPES
     if hasattr(L, "tinsel_hip_render_sample_map"):     # absent from older builds loaded through TINSEL_HIP_LIB for an A/B
         L.tinsel_hip_render_sample_map.argtypes = abi.RENDER_SAMPLE_MAP_ARGTYPES
         L.tinsel_hip_render_sample_map_device.argtypes = abi.RENDER_SAMPLE_MAP_DEVICE_ARGTYPES
@@ -223,6 +226,7 @@ EXPORTED_SYMBOLS = [
     "tinsel_hip_render_light_groups", "tinsel_hip_render_light_groups_device",
     "tinsel_hip_render_views", "tinsel_hip_render_views_device", "tinsel_hip_plan_views",
     "tinsel_hip_render_sample_map", "tinsel_hip_render_sample_map_device", "tinsel_hip_plan_sample_map",
+    "tinsel_hip_render_depth_planes", "tinsel_hip_render_depth_planes_device",
     "tinsel_hip_denoise_params_init", "tinsel_hip_denoise", "tinsel_hip_denoise_device", "tinsel_hip_present_image_device",
 ]
 
@@ -580,6 +584,29 @@ def relight(planes, gains):
     out[..., :3] = planes[0][..., :3]*g[0]
     for k in range(1, G):
         out[..., :3] += planes[k][..., :3]*g[k]
+    return out
+
+
+def depth_contributions(planes):
+    """What each depth adds: float32 [n, H, W, 3] from the planes [n, H, W, 4] of HipRenderer.depth_planes.  Entry 0 is plane 0's image --
+    colour divided by weight, 0 where the weight is 0 -- and entry k is image k minus image k - 1: for depths 1 .. D direct light (with
+    what the camera sees of the emitters), then each further bounce's share.  The shares add up to the deepest plane's image within fp32
+    rounding.  With options.clamp = FLT_MAX no share is negative; a FINITE clamp applies to each plane's samples separately and can make a
+    share negative.  numpy arrays or torch tensors (the result is of the planes' kind)."""
+    if planes.ndim != 4 or planes.shape[-1] != 4 or int(planes.shape[0]) < 1:
+        raise ValueError("depth_contributions: planes [n, H, W, 4] are expected")
+    if _is_tensor(planes):
+        import torch
+        w = planes[..., 3:4]
+        img = torch.where(w != 0, planes[..., :3]/torch.where(w != 0, w, torch.ones_like(w)), torch.zeros_like(planes[..., :3]))
+        out = img.clone()
+        out[1:] = img[1:] - img[:-1]
+        return out
+    planes = np.asarray(planes, np.float32)
+    w = planes[..., 3:4]
+    img = np.where(w != 0, planes[..., :3]/np.where(w != 0, w, np.float32(1)), np.float32(0)).astype(np.float32)
+    out = img.copy()
+    out[1:] = img[1:] - img[:-1]
     return out
 
 
@@ -1082,6 +1109,44 @@ class HipRenderer:
                 raise ValueError("light_groups: a C-contiguous float32 array %s is expected" % (shape,))
             _check(self._L.tinsel_hip_render_light_groups(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), G,
                                                           _host_ptr(table), env, out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_light_groups")
+        return out
+
+    def depth_planes(self, camera, options, pass_begin, passes, depths=None, out=None, add=False, singly=False):
+        """Depth planes (tinsel_hip_render_depth_planes*): the beauty of passes [pass_begin, pass_begin + passes) at several path depths in
+        one trace -- float32 [n, H, W, 4], plane k the accumulator render() gives from zero with options.max_depth = depths[k] (bit for bit;
+        options.clamp applies per plane, the Russian-roulette setting applies).  `depths`: strictly ascending ints in 1 .. 64, at most 16;
+        None: 1 .. options.max_depth.  options.max_depth itself is not read by the call.  add: the passes are added to what `out` holds
+        instead of starting every plane from zero; singly: one accumulate launch per plane instead of one per batch (the same bits).
+        `out`: a contiguous float32 torch tensor [n, H, W, 4] on this renderer's device takes the device entry on torch's current stream,
+        not waited for; a numpy array of that shape is filled by the host entry.  Needs init() at the options' frame size; leaves the
+        accumulator, pass index, pass seeds and statistics as they were.  depth_contributions() turns the planes into per-bounce shares."""
+        if depths is None:
+            if int(options.max_depth) > abi.MAX_DEPTH_PLANES:
+                raise ValueError("depth_planes: options.max_depth = %d is more than %d planes: name the depths" % (int(options.max_depth), abi.MAX_DEPTH_PLANES))
+            depths = range(1, int(options.max_depth) + 1)
+        table = np.ascontiguousarray(np.asarray(list(depths)).reshape(-1), np.int32)
+        n = int(table.size)
+        flags = (abi.DEPTH_PLANES_ADD if add else 0) | (abi.DEPTH_PLANES_ACCUMULATE_SINGLY if singly else 0)
+        H, W = int(options.height), int(options.width)
+        shape = (max(n, 1), H, W, 4)
+        if _is_tensor(out):
+            import torch
+            if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError("depth_planes: a contiguous float32 tensor %s on the GPU is expected" % (shape,))
+            if out.device.index != self.device:
+                raise ValueError("depth_planes: the tensor is on %s, the renderer on device %d" % (out.device, self.device))
+            _check(self._L.tinsel_hip_render_depth_planes_device(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), n,
+                                                                 _host_ptr(table), flags, out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "tinsel_hip_render_depth_planes_device")
+        else:
+            if out is None:
+                if add:
+                    raise ValueError("depth_planes: add=True needs the planes to add to (out)")
+                out = np.zeros(shape, np.float32)
+            elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("depth_planes: a C-contiguous float32 array %s is expected" % (shape,))
+            _check(self._L.tinsel_hip_render_depth_planes(self._h, C.byref(camera), C.byref(options), int(pass_begin), int(passes), n,
+                                                          _host_ptr(table), flags, out.ctypes.data_as(C.c_void_p)), "tinsel_hip_render_depth_planes")
         return out
 
     def views(self, cameras, options, pass_begin=0, passes=1, out=None, add=False, singly=False):
