@@ -13,7 +13,9 @@
 // are decided by the compiler and nothing of the scene level is fetched or held in scalar registers.  What depends on the ray stays at run
 // time: a pair with both planes ahead, non-finite rays, the tie re-trace through the BVH walk (trace), pose_rotate's zero-component branch.
 // Only the closed FIT instance of k_bounce takes this path (SceneT::kBaked); the host launches it only for the scene whose key it was
-// compiled from (tn_host_bake.h).
+// compiled from (tn_host_bake.h).  tests/test_gpu_bake.py (cornell and its edits) and tests/test_gpu_closed_corpus.py (every form of the
+// light tables, no plane table, sixteen slots, a remainder slot, primitive 63, rotated and scaled poses) hold it to the library's instance
+// bit for bit.
 #pragma once
 
 #if TN_BAKED_SCENE

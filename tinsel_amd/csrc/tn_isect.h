@@ -497,7 +497,7 @@ TN_D unsigned long long wave_uniform64(unsigned long long v)
 
 // (TWIN: trace_flat_baked, tn_baked.h, states this scan's closed form -- kCompactSingles, no deferred walks, no any-hit stop -- over a baked
 // build's constants: a change to the pair block, the single planes, the scan loop or accept() here is made there too; tests/test_gpu_bake.py
-// compares the two bit for bit.)
+// (cornell and its edits) and tests/test_gpu_closed_corpus.py (other table shapes, light tables, poses) compare the two bit for bit.)
 template <class SC, class Stack, bool COUNT, bool ANYHIT = false>
 TN_D int trace_flat(const SC& sc, Stack& st, V3 o, V3 d, V3 rcp, float time, float& outT, V3& outN, bool& tie, TraceCounters& ctr, float tStop = 0.0f)
 {
