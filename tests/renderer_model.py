@@ -9,8 +9,12 @@ The LOGICAL STATE (class State) is what a caller may rely on: the scene (as a ke
 accumulator's contents -- the array given to write_accum, if any, and the renders since the last init, each with the settings it ran under --,
 the next pass index, the shard, the roulette start, the probe sampling mode, the arithmetic arm and whether a primitive was moved without a
 rebuild.  Everything else a renderer remembers is a cache.  LIVE_ONLY ops set what the project documents as bit-neutral: the fresh renderer
-never gets them.  THERE_AND_BACK and REFUSED ops leave the logical state as it was.  `replay(state)` is the shortest route that brings a
-fresh renderer to a state: a recipe, it launches nothing."""
+never gets them (set_bake, the bake mode of the closed fused kernel, among them).  THERE_AND_BACK and REFUSED ops leave the logical state
+as it was.  `replay(state)` is the shortest route that brings a fresh renderer to a state: a recipe, it launches nothing.
+
+The PLANE_OBSERVERS -- light groups, view batches, sample maps, depth planes, each through its host and its device entry -- need the frame
+but not its contents, keep renderer-lifetime buffers, seed tables and fences of their own, and refuse a sharded renderer and the
+tolerance arm: the builder sets the shard back in front of one."""
 import copy
 import os
 
@@ -23,7 +27,7 @@ ANIM_FRAMES = 4
 DEFAULT_SHARD = (0, 1, 32)
 SHARDS = ((1, 2, 16), (0, 2, 32), (2, 3, 16), (0, 1, 32))
 N_RAYS, N_STARTS, N_POINTS, N_SAMPLES = 4096, 2048, 256, 8
-MAX_OPS, MAX_SCHEDULES = 32, 16
+MAX_OPS, MAX_SCHEDULES = 44, 16
 MAX_REPLAY_RENDERS, MAX_REPLAY_PASSES = 4, 8
 SEED_TABLE_AHEAD = 1024                                             # render_impl's kSeedsAhead (tn_host_batch.h)
 
@@ -44,16 +48,20 @@ REFITS = ((0.05, None), (0.02, 7), (0.0, 0))                        # (displacem
 
 MUTATORS = ("init", "init_external", "set_pass_index", "render", "render_async", "write_accum", "set_shard", "set_russian_roulette",
             "set_probe_sampling", "update_scene", "refit_mesh")
-LIVE_ONLY = ("set_pipeline", "set_tuning", "set_batch_paths", "reserve", "set_lookahead", "set_counters")
+LIVE_ONLY = ("set_pipeline", "set_tuning", "set_batch_paths", "reserve", "set_lookahead", "set_counters", "set_bake")
 THERE_AND_BACK = ("bvh_there_and_back", "rebuild_there_and_back", "fast_there_and_back")
-REFUSED = ("refused_render_dirty", "refused_features_size", "refused_mattes_size", "refused_denoise_radius", "refused_tuning")
+REFUSED = ("refused_render_dirty", "refused_features_size", "refused_mattes_size", "refused_denoise_radius", "refused_tuning",
+           "refused_planes_sharded", "refused_planes_fast")
+# the four calls that give planes of the beauty, each with a host and a `_device` entry: they refuse a sharded renderer and the tolerance arm
+PLANE_FEATURES = ("light_groups", "views", "sample_map", "depth_planes")
+PLANE_OBSERVERS = tuple(f + e for f in PLANE_FEATURES for e in ("", "_device"))
 OBSERVERS = ("render_readback", "read_accum", "get_pass_index", "present", "present_image", "render_cost", "features", "features_device",
              "id_mattes", "id_mattes_device", "denoise_own", "denoise_images", "trace_rays", "trace_rays_device", "trace_camera",
-             "radiance", "gather", "gather_sh")
+             "radiance", "gather", "gather_sh") + PLANE_OBSERVERS
 ALL_KINDS = ("create",) + MUTATORS + LIVE_ONLY + THERE_AND_BACK + REFUSED + OBSERVERS
 # observers that only read the scene (a fresh renderer needs no frame), and those that need the frame and the shard but not its contents
 SCENE_OBSERVERS = ("trace_rays", "trace_rays_device", "trace_camera", "radiance", "gather", "gather_sh", "denoise_images")
-FRAME_OBSERVERS = ("render_cost", "features", "features_device", "id_mattes", "id_mattes_device")
+FRAME_OBSERVERS = ("render_cost", "features", "features_device", "id_mattes", "id_mattes_device") + PLANE_OBSERVERS
 # ops after which get_pass_index() is checked at once: they must change nothing
 CHANGES_NOTHING = tuple(k for k in OBSERVERS if k != "render_readback") + THERE_AND_BACK + REFUSED
 
@@ -61,7 +69,37 @@ PIPELINES = ("auto", "wavefront", "split", "paired", "megakernel")
 TUNINGS = ({"grid_mult": 4, "walk_lds_stack": 2}, {"shade_sorted": 1, "accumulate": 2}, {"overlap": 1, "walk_single": 0},
            {"repack": 1, "tail_split": 1, "tail_share": 0.4, "tail_divide": 8}, {"accumulate": 3, "overlap": 0, "repack": 0, "shade_sorted": 0},
            {"tail_split": 0, "grid_mult": 16, "accumulate": 1}, {})
-TUNING_FIELDS = ("grid_mult", "accumulate", "overlap", "shade_sorted", "repack", "tail_split", "walk_lds_stack", "walk_single")
+TUNING_FIELDS = ("grid_mult", "accumulate", "overlap", "shade_sorted", "repack", "tail_split", "walk_lds_stack", "walk_single", "bounce_share",
+                 "bounce_bake")
+# what the plane observers draw (tests/test_gpu_histories.py makes the tables, cameras and maps from these names)
+GROUP_TABLES = ("one", "parity", "eight")                           # -> (groups G, env_group): see group_table
+VIEW_COUNTS = (1, 3, 6)
+SAMPLE_MAPS = ("uniform", "random", "crop", "zeros")
+PLANE_DEPTHS = ((1,), (1, 2, 3, 4), (2, 6), tuple(range(1, 17)))
+PLANE_PASSES = {"light_groups": (0, 5, 1200), "views": (0, 7, 1300), "sample_map": (0, 3, 1400), "depth_planes": (0, 2, 1600)}
+BAKE_MODES, BAKE_SHARES = (1, 0, -1), (0, -1)
+# the call a refused_planes_* op makes, per feature
+REFUSED_PLANES = {"light_groups": dict(table="parity", pass_begin=0, passes=1),
+                  "views": dict(count=3, pass_begin=0, passes=1, add=False, singly=False, seed=1),
+                  "sample_map": dict(map="uniform", pass_begin=0, add=False, seed=1),
+                  "depth_planes": dict(depths=(1, 2, 3, 4), pass_begin=0, passes=1, add=False, singly=False, seed=1)}
+
+
+def feature_of(kind):
+    """the plane feature of an observer kind, or None"""
+    f = kind[:-len("_device")] if kind.endswith("_device") else kind
+    return f if f in PLANE_FEATURES else None
+
+
+def group_table(name, primitives):
+    """(group of every primitive, env_group, G) of a light-group table, from the scene's primitive count alone: "one" puts every primitive
+    in group 0; "parity" primitive i in group i % 2 and the environment in 1; "eight" primitive i in group i % 8, every seventh in none."""
+    if name == "one":
+        return [0]*primitives, 0, 1
+    if name == "parity":
+        return [i % 2 for i in range(primitives)], 1, 2
+    assert name == "eight", name
+    return [-1 if i % 7 == 6 else i % 8 for i in range(primitives)], -1, 8
 
 
 def supports(family, kind):
@@ -147,8 +185,10 @@ class Model:
             s.scene = ("refit", FAMILIES[s.family]["pack"], float(p["amount"]), p["normals"] if p["normals"] is not None else kept)
         else:
             # live-only settings, there-and-back operations, refused calls and the plain observers: the logical state stays
-            if kind in FRAME_OBSERVERS + ("read_accum", "present", "present_image", "denoise_own", "reserve") or kind in REFUSED[1:3]:
+            if kind in FRAME_OBSERVERS + ("read_accum", "present", "present_image", "denoise_own", "reserve") or kind in REFUSED[1:3] + REFUSED[5:7]:
                 assert s.size is not None, kind
+            if kind in PLANE_OBSERVERS:
+                assert s.shard[1] == 1 and s.arith == 0, "%s refuses a sharded renderer and the tolerance arm" % kind
             if kind in OBSERVERS and replay_level(kind) == "full":
                 assert all(r[0] == s.scene for r in s.renders), "one frame, one scene: init after the scene changes"
 
@@ -295,6 +335,7 @@ class _Builder:
         self.ops = []
         self.small_batches = False
         self.lookahead = 0
+        self.bake = None                                 # (mode, share) of the set_bake in force: a set_tuning drops it
         self.reserve = self._anchor_reserve()
         self.emit("create", scene=self.family)
 
@@ -311,8 +352,9 @@ class _Builder:
         self.ops.append(op)
         if kind == "set_batch_paths":
             self.small_batches = p["paths"] < (1 << 20)
-        if kind == "set_tuning":
+        if kind in ("set_tuning", "set_bake"):
             self.small_batches = False                   # (set_tuning takes the struct's batch_paths: the default)
+            self.bake = (p["mode"], p["share"]) if kind == "set_bake" else None
         if kind == "set_lookahead":
             self.lookahead = p["mode"]
 
@@ -404,6 +446,8 @@ class _Builder:
             self.emit(kind, mode=r.pick([m for m in (0, 1, 2) if m != self.lookahead]))
         elif kind == "set_counters":
             self.emit(kind, timing=bool(r.below(2)), detail=bool(r.below(2)))
+        elif kind == "set_bake":
+            self.emit(kind, mode=r.pick(BAKE_MODES), share=r.pick(BAKE_SHARES))
         else:
             raise AssertionError(kind)
 
@@ -411,6 +455,12 @@ class _Builder:
         """a there-and-back operation or a refused call"""
         if kind == "bvh_there_and_back":
             self.emit(kind, mode=self.rng.pick(("lbvh", "ploc")))
+        elif kind in ("refused_planes_sharded", "refused_planes_fast"):
+            self.frame()
+            p = dict(feature=self.rng.pick(PLANE_FEATURES), device=bool(self.rng.below(2)))
+            if p["device"]:
+                p["stream"] = self.side_stream
+            self.emit(kind, **p)
         elif kind in ("refused_features_size", "refused_mattes_size"):
             self.frame()
             self.emit(kind, device=bool(self.rng.below(2)))
@@ -427,6 +477,8 @@ class _Builder:
         if kind == "render_readback":
             self.render(kind, **over)
             return
+        if kind in PLANE_OBSERVERS and self.s.shard[1] > 1:              # (they refuse a sharded renderer)
+            self.emit("set_shard", rank=DEFAULT_SHARD[0], world=DEFAULT_SHARD[1], tile=DEFAULT_SHARD[2])
         if kind in ("read_accum", "present", "present_image", "denoise_own"):
             self.content()
         elif kind in FRAME_OBSERVERS:
@@ -453,6 +505,16 @@ class _Builder:
             p = dict(mode=r.pick(("cosine", "sphere")), depth=r.pick(DEPTHS[:3]), device=bool(r.below(2)))
         elif kind == "gather_sh":
             p = dict(order=r.below(3), mode=r.pick(("cosine", "sphere")), depth=r.pick(DEPTHS[:3]), device=bool(r.below(2)))
+        elif feature_of(kind) == "light_groups":
+            p = dict(table=r.pick(GROUP_TABLES), pass_begin=r.pick(PLANE_PASSES["light_groups"]), passes=1 + r.below(2))
+        elif feature_of(kind) == "views":
+            p = dict(count=r.pick(VIEW_COUNTS), pass_begin=r.pick(PLANE_PASSES["views"]), passes=1 + r.below(2), add=bool(r.below(2)),
+                     singly=bool(r.below(2)), seed=1 + r.below(3))
+        elif feature_of(kind) == "sample_map":
+            p = dict(map=r.pick(SAMPLE_MAPS), pass_begin=r.pick(PLANE_PASSES["sample_map"]), add=bool(r.below(2)), seed=1 + r.below(3))
+        elif feature_of(kind) == "depth_planes":
+            p = dict(depths=r.pick(PLANE_DEPTHS), pass_begin=r.pick(PLANE_PASSES["depth_planes"]), passes=1 + r.below(2), add=bool(r.below(2)),
+                     singly=bool(r.below(2)), seed=1 + r.below(3))
         else:
             p = {}
         p.update(over)
@@ -514,6 +576,71 @@ class _Builder:
         self.observe("present", nlm=self.rng.below(2))
         self.observe("render_readback", depth=2, passes=1)
 
+    def _entry(self, feature):
+        return feature + ("_device" if self.rng.below(2) else "")
+
+    def motif_planes_shrink_grow(self):
+        """record and output buffers that only grow: every plane feature at a big frame, a smaller one and a bigger one again"""
+        big, small, again = self.rng.pick(((96, 64), (50, 37))), self.rng.pick(((33, 17), (16, 16))), self.rng.pick(((96, 64), (48, 32)))
+        # (the last frame asks for more planes and passes than the first, so that it needs the largest buffers of the three whatever its size)
+        few = {"light_groups": dict(table="one", passes=1), "views": dict(count=1, passes=1),
+               "sample_map": dict(map="crop"), "depth_planes": dict(depths=self.rng.pick(PLANE_DEPTHS[:1] + PLANE_DEPTHS[2:3]), passes=1)}
+        many = {"light_groups": dict(table="eight", passes=2), "views": dict(count=6, passes=2), "sample_map": dict(map="uniform"),
+                "depth_planes": dict(depths=PLANE_DEPTHS[3], passes=2)}
+        for size, over in ((big, few), (small, few), (again, many)):
+            self.init(size)
+            self.render(passes=1)
+            for f in self.rng.shuffled(PLANE_FEATURES):
+                self.observe(self._entry(f), **over[f])
+        self.observe("render_readback", passes=1)
+
+    def motif_planes_between_renders(self):
+        """a plane call at a pass of its own between two renders of one frame: its seeds, records and fence, and the path buffers it borrows"""
+        self.init()
+        self.render(passes=1)
+        for k, f in enumerate(self.rng.shuffled(PLANE_FEATURES)):
+            if k == 2:
+                self.init(self.s.size)                   # (a fresh replay stays short)
+                self.render(passes=1)
+            self.observe(self._entry(f), pass_begin=self.rng.pick([b for b in PLANE_PASSES[f] if b != self.s.next_pass]))
+            self.render(passes=1)
+        self.observe("read_accum")
+
+    def motif_device_then_host(self):
+        """the device entry (on the side stream in a side-stream schedule) directly followed by the host entry of the same feature: the
+        fence and the stream it was recorded on"""
+        self.init()
+        self.render(passes=1)
+        for f in self.rng.shuffled(PLANE_FEATURES):
+            self.observe(f + "_device")
+            self.observe(f)
+        self.observe("render_readback", passes=1)
+
+    def motif_group_table_change(self):
+        """another table after the scene changed, at an unchanged frame size: what was uploaded last"""
+        self.init()
+        self.render(passes=1)
+        first = self.rng.pick(GROUP_TABLES)
+        self.observe(self._entry("light_groups"), table=first)
+        self.mutate("update_scene" if FAMILIES[self.family]["update"] else "refit_mesh")          # (and an init at the same size)
+        self.observe(self._entry("light_groups"), table=self.rng.pick([t for t in GROUP_TABLES if t != first]))
+        self.observe(self._entry("light_groups"), table=first)
+        self.observe("render_readback", passes=1)
+
+    def motif_bake_neutral(self):
+        """a baked instance across operations that leave the logical state: the installed code object and its key"""
+        self.init()
+        self.emit("set_bake", mode=1, share=0)
+        self.emit("reserve", passes=2, depth=4)          # (with mode 1 this is where the instance is compiled and installed)
+        self.render(depth=4, passes=1)
+        self.emit("rebuild_there_and_back")
+        self.render(depth=4, passes=1)
+        self.emit("fast_there_and_back")
+        self.observe("render_readback", depth=4, passes=1)
+        self.emit("set_tuning", fields=dict(self.rng.pick(TUNINGS)))                               # drops the mode
+        self.observe("render_readback", depth=4, passes=1)
+        self.emit("set_bake", mode=1, share=0)           # and back on: what the golden anchor may find in force
+
     def motif_scene_sweep(self):
         """the scene changes, then every observer kind looks"""
         self.init()
@@ -548,7 +675,10 @@ class _Builder:
         self.emit("render_readback", depth=depth, mode="pathtrace", passes=passes, golden=True)
 
 
-MOTIFS = ("shrink_grow", "depth_and_pipeline", "shared_buffers", "seed_table", "shard", "lookahead", "scene_sweep")
+MOTIFS = ("shrink_grow", "depth_and_pipeline", "shared_buffers", "seed_table", "shard", "lookahead", "planes_shrink_grow",
+          "planes_between_renders", "device_then_host", "group_table_change", "bake_neutral", "scene_sweep")
+ANYWHERE = MOTIFS[:9]                             # the motifs every scene family supports
+MOTIF_OPS = {"planes_shrink_grow": 20, "planes_between_renders": 14}             # the ops a motif takes where that is more than 14
 
 
 def schedule(seed):
@@ -558,12 +688,12 @@ def schedule(seed):
     r = b.rng
     scene_changes = FAMILIES[b.family]["update"] or FAMILIES[b.family]["refit"]
     first = MOTIFS[(seed//len(FAMILY_ORDER)) % len(MOTIFS)]
-    if first == "scene_sweep" and not scene_changes:
-        first = r.pick(MOTIFS[:-1])
+    if (first in ("scene_sweep", "group_table_change") and not scene_changes) or (first == "bake_neutral" and b.family != "cornell"):
+        first = r.pick(ANYWHERE)
     getattr(b, "motif_" + first)()
     if first != "scene_sweep" and r.below(2):
-        second = r.pick([m for m in MOTIFS[:-1] if m != first])
-        if b.room() >= 14:
+        second = r.pick([m for m in ANYWHERE if m != first])
+        if b.room() >= MOTIF_OPS.get(second, 14):
             getattr(b, "motif_" + second)()
     mutators = [k for k in MUTATORS if supports(b.family, k)]
     rare = [k for k in ("set_probe_sampling", "refit_mesh", "update_scene") if supports(b.family, k)]
@@ -698,12 +828,95 @@ def sequences(ops):
     for m in ("update_scene", "refit_mesh"):
         if m in kinds and set(OBSERVERS) <= set(kinds[kinds.index(m) + 1:]):
             found.add(m + "_then_every_observer")
+    found |= _plane_sequences(ops, rs)
+    return found
+
+
+def _planes_per_pixel(kind, p):
+    """what a plane call keeps per pixel of the frame, roughly: paths times planes (a sample map: its mean count)"""
+    f = feature_of(kind)
+    if f == "sample_map":
+        return {"zeros": 0.0, "crop": 0.25, "random": 1.5, "uniform": 2.0}[p["map"]]
+    return p["passes"]*{"light_groups": lambda: group_table(p["table"], 0)[2], "views": lambda: p["count"], "depth_planes": lambda: len(p["depths"])}[f]()
+
+
+def _plane_sequences(ops, rs):
+    """the sequences of the plane features (light groups, views, sample maps, depth planes) and of the bake mode"""
+    found = set()
+    # every feature at three successive frames, big, smaller, bigger again, with a render before the first look and after the last
+    frames = []                                          # [area, {feature: (first step, last step, paths of the largest call)}] per init
+    for k, (kind, p) in enumerate(ops):
+        if kind in INITS:
+            frames.append([p["size"][0]*p["size"][1], {}])
+        elif frames and feature_of(kind):
+            first, _, paths = frames[-1][1].get(feature_of(kind), (k, k, 0))
+            frames[-1][1][feature_of(kind)] = (first, k, max(paths, frames[-1][0]*_planes_per_pixel(kind, p)))
+    steps = [r[0] for r in rs]
+
+    def shrinks_then_grows(f):
+        # (and the last of the three asks for more than the first: buffers that kept their first size would be too small for it)
+        for a, b, c in zip(frames, frames[1:], frames[2:]):
+            if f in a[1] and f in b[1] and f in c[1] and a[0] > b[0] < c[0] and steps and min(steps) < a[1][f][0] and max(steps) > c[1][f][1] \
+                    and a[1][f][2] > b[1][f][2] < c[1][f][2] > a[1][f][2]:
+                return True
+        return False
+    if all(shrinks_then_grows(f) for f in PLANE_FEATURES):
+        found.add("planes_shrink_grow")
+    # a plane call at a pass of its own between two renders of one frame
+    for (a, oa, pa), (b, ob, _) in zip(rs, rs[1:]):
+        if _between(ops, a, b, INITS + ("set_pass_index",)):
+            continue
+        for k in _between(ops, a, b, PLANE_OBSERVERS):
+            if ops[k][1]["pass_begin"] != pa + oa[1]["passes"]:
+                found.add(feature_of(ops[k][0]) + "_between_renders")
+    # the device entry on a side stream, then at once the host entry of the same feature
+    for (ka, pa), (kb, _) in zip(ops, ops[1:]):
+        if ka.endswith("_device") and feature_of(ka) == kb and pa.get("stream"):
+            found.add(kb + "_device_then_host")
+    # two light-group tables, the second after the scene changed, no other frame size between them
+    last, changed, size = None, False, None
+    for kind, p in ops:
+        if kind in INITS:
+            if tuple(p["size"]) != size:
+                last = None
+            size = tuple(p["size"])
+        elif kind in ("update_scene", "refit_mesh"):
+            changed = last is not None
+        elif feature_of(kind) == "light_groups":
+            if last is not None and changed and p["table"] != last:
+                found.add("group_table_change")
+            last, changed = p["table"], False
+    # the bake mode across operations that leave the logical state, on the scene whose plan gives the closed fused kernel
+    if ops[0][1]["scene"] == "cornell":
+        want = [lambda k, p: k == "set_bake" and (p["mode"], p["share"]) == (1, 0), lambda k, p: k in ("render", "render_async"),
+                lambda k, p: k == "rebuild_there_and_back", lambda k, p: k in ("render", "render_async"),
+                lambda k, p: k == "fast_there_and_back", lambda k, p: k == "render_readback", lambda k, p: k == "set_tuning",
+                lambda k, p: k == "render_readback"]
+        for start in range(len(ops)):
+            at = 0
+            for kind, p in ops[start:]:
+                if want[at](kind, p):
+                    at += 1
+                    if at == len(want):
+                        break
+                elif at and kind not in INITS + ("reserve",):
+                    break
+            if at == len(want):
+                found.add("bake_across_neutral_ops")
+        force = None
+        for kind, p in ops:
+            if kind in ("set_tuning", "set_bake"):
+                force = (p["mode"], p["share"]) if kind == "set_bake" else None
+        if force == (1, 0) and ops[-1][1].get("golden"):
+            found.add("bake_in_force_at_the_anchor")
     return found
 
 
 SEQUENCES = ("shrink_grow", "depth_down_up", "pipeline_change_allocated", "query_between_renders", "side_pass_between_renders",
              "seed_table_exit_and_rewind", "shard_change_same_frame", "lookahead_miss", "lookahead_across_present",
-             "update_scene_then_every_observer", "refit_mesh_then_every_observer")
+             "update_scene_then_every_observer", "refit_mesh_then_every_observer", "planes_shrink_grow", "group_table_change",
+             "bake_across_neutral_ops", "bake_in_force_at_the_anchor") + \
+    tuple(f + s for f in PLANE_FEATURES for s in ("_between_renders", "_device_then_host"))
 
 
 # parameter values the schedules must draw somewhere: (kind prefix, parameter, value)
@@ -714,7 +927,15 @@ VALUES = tuple([("render", "mode", m) for m in ("pathtrace", "normals")] + [("re
                [("gather", "mode", m) for m in ("cosine", "sphere")] + [("trace_rays", "mode", m) for m in ("closest", "occluded")] +
                [("set_batch_paths", "paths", 1024), ("set_counters", "timing", True), ("set_counters", "detail", True),
                 ("denoise_own", "guides", True), ("denoise_own", "guides", False)] +
-               [(k, "device", d) for k in ("radiance", "gather", "gather_sh", "denoise_own", "denoise_images") for d in (False, True)])
+               [(k, "device", d) for k in ("radiance", "gather", "gather_sh", "denoise_own", "denoise_images") for d in (False, True)] +
+               [(f, "pass_begin", b) for f in PLANE_FEATURES for b in PLANE_PASSES[f]] +
+               [(f, "passes", n) for f in ("light_groups", "views", "depth_planes") for n in (1, 2)] +
+               [(f, name, x) for f in ("views", "depth_planes") for name in ("add", "singly") for x in (False, True)] +
+               [("sample_map", "add", x) for x in (False, True)] + [("light_groups", "table", t) for t in GROUP_TABLES] +
+               [("views", "count", n) for n in VIEW_COUNTS] + [("sample_map", "map", m) for m in SAMPLE_MAPS] +
+               [("depth_planes", "depths", d) for d in PLANE_DEPTHS] +
+               [("refused_planes", "feature", f) for f in PLANE_FEATURES] + [("refused_planes", "device", d) for d in (False, True)] +
+               [("set_bake", "mode", m) for m in BAKE_MODES] + [("set_bake", "share", n) for n in BAKE_SHARES])
 
 
 def requirements():
@@ -743,6 +964,8 @@ def tokens(ops):
     for kind, p in ops:
         if kind == "set_tuning":
             out.update(("tuning", f) for f in p["fields"] if f in TUNING_FIELDS)
+        if kind == "set_bake":
+            out.update((("tuning", "bounce_share"), ("tuning", "bounce_bake")))
         if kind == "set_pipeline":
             out.add(("pipeline", p["pipeline"]))
         if kind == "set_lookahead":
@@ -780,7 +1003,12 @@ def _greedy(need, have, chosen, limit):
 
 
 # choose_seeds(range(3000)): what meets requirements(), topped up to 16 with seeds that repeat sequences on other scenes
-SEEDS = (33, 37, 44, 322, 540, 725, 908, 948, 955, 1374, 1614, 1644, 1662, 1976, 2337, 2762)
+SEEDS = (3, 54, 65, 234, 392, 426, 715, 936, 1328, 1370, 1614, 1902, 2239, 2506, 2529, 2657)
+# The set chosen before the plane features and the bake mode joined the model (MAX_OPS 32).  The schedules these seeds give under the present
+# generator are run as well -- further histories that no requirement selected, each with at least 10 observations -- but nothing in
+# requirements() counts on them: what must be covered is covered by SEEDS alone.
+EARLIER_SEEDS = (33, 37, 44, 322, 540, 725, 908, 948, 955, 1374, 1614, 1644, 1662, 1976, 2337, 2762)
+ALL_SEEDS = SEEDS + tuple(s for s in EARLIER_SEEDS if s not in SEEDS)
 
 
 # -- groups -------------------------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,9 @@ tests/renderer_model.py draws seeded schedules of API calls and keeps the LOGICA
 the CPU what the committed schedules cover.  Here one live renderer runs a schedule in order.  At every observation a fresh renderer --
 default tuning, pipeline AUTO, no look-ahead, nothing reserved -- is brought to the model's state by the shortest route (renderer_model.replay),
 makes the same observation once and is closed, and the two results must agree bit for bit (compared as uint32 words: NaN payloads included).
-After every op that must change nothing the pass index is checked at once, and at the end the accumulator.  A schedule on a scene with a golden
+After every op that must change nothing the pass index is checked at once, and at the end the accumulator; around a light-group, view-batch,
+sample-map or depth-plane call the live renderer's statistics must stay as they were.  The bake mode (set_bake) is a live-only setting like
+the pipeline: the fresh renderers never get it, and the module's baked instances share one cache directory.  A schedule on a scene with a golden
 file ends on that file's own frame: the live renderer, after its whole history, is held to the reference's output, so that the fresh renderer
 cannot be wrong in the same way unseen.
 
@@ -23,6 +25,19 @@ from tests import renderer_model as rm
 pytestmark = pytest.mark.gpu
 
 SECONDS_PER_SCHEDULE = 120          # a schedule takes a few seconds; one that takes this long ends itself at its next step
+
+
+@pytest.fixture(scope="module", autouse=True)
+def bake_cache(tmp_path_factory):
+    """the baked instances the set_bake ops compile share one cache directory of the module's own: a scene level is compiled once"""
+    from tinsel_amd import build as hb
+    was = os.environ.get(hb.BAKE_CACHE_ENV)
+    os.environ[hb.BAKE_CACHE_ENV] = str(tmp_path_factory.mktemp("bake_cache"))
+    yield os.environ[hb.BAKE_CACHE_ENV]
+    if was is None:
+        del os.environ[hb.BAKE_CACHE_ENV]
+    else:
+        os.environ[hb.BAKE_CACHE_ENV] = was
 
 
 class Mismatch(AssertionError):
@@ -138,6 +153,74 @@ def _image(seed, size, weight=True):
     return _cached(("image", seed, tuple(size), weight), make)
 
 
+def _orbit(family, count):
+    """`count` cameras on a turntable about the point one unit in front of the family's camera (it looks along its local -z)"""
+    from tinsel_amd import orbit_cameras
+
+    def make():
+        cam = _frame(family)[0]
+        u, w = np.array(tuple(cam.rotation)[:3], np.float64), float(tuple(cam.rotation)[3])
+        ahead = np.array([0.0, 0.0, -1.0])
+        ahead = ahead + 2.0*np.cross(u, np.cross(u, ahead) + w*ahead)
+        return orbit_cameras(cam, np.array(tuple(cam.position), np.float64) + ahead, count)
+    return _cached(("orbit", family, count), make)
+
+
+def _sample_map(name, size):
+    """a uint16 pass count per pixel [H, W]: 2 everywhere, 0 .. 3 at random, a crop across column 16 and row 16, or 0 everywhere"""
+    from tinsel_amd import crop_sample_map
+
+    def make():
+        W, H = size
+        if name == "uniform":
+            return np.full((H, W), 2, np.uint16)
+        if name == "random":
+            return np.random.default_rng(3000 + 100*W + H).integers(0, 4, (H, W)).astype(np.uint16)
+        if name == "crop":
+            return crop_sample_map(W, H, 10, 9, 23, 21, 3)
+        assert name == "zeros", name
+        return np.zeros((H, W), np.uint16)
+    return _cached(("sample map", name, tuple(size)), make)
+
+
+def _plane_count(r, feature, p):
+    if feature == "light_groups":
+        return rm.group_table(p["table"], r.num_primitives)[2]
+    return {"views": p.get("count"), "sample_map": 1, "depth_planes": len(p.get("depths", ()))}[feature]
+
+
+def planes_out(r, feature, p, state, device, fill=None):
+    """The caller's `out` of a plane call: a numpy array (host entry) or a torch tensor (device entry, uploaded on torch's current stream)
+    of zeros, with add one _image per plane from the op's seed (the same for every renderer), or full of `fill`."""
+    import torch
+    n, size = _plane_count(r, feature, p), state.size
+    shape = (size[1], size[0], 4) if feature == "sample_map" else (n, size[1], size[0], 4)
+    if fill is not None:
+        out = np.full(shape, fill, np.float32)
+    elif p.get("add"):
+        out = np.stack([_image(p["seed"] + 10*k, size) for k in range(n)]).reshape(shape)
+    else:
+        out = np.zeros(shape, np.float32)
+    return torch.from_numpy(out).cuda() if device else out
+
+
+def plane_call(r, feature, p, state, device, out=None):
+    """One call of a plane feature -- light groups, views, a sample map, depth planes -- on renderer `r`, through the host or the device
+    entry (on torch's current stream): returns `out`"""
+    fam, size = state.family, state.size
+    cam, opt = _frame(fam)[0], _options(fam, size)
+    if out is None:
+        out = planes_out(r, feature, p, state, device)
+    if feature == "light_groups":
+        table, env, _ = rm.group_table(p["table"], r.num_primitives)
+        return r.light_groups(cam, opt, p["pass_begin"], p["passes"], table, env, out=out)
+    if feature == "views":
+        return r.views(_orbit(fam, p["count"]), opt, p["pass_begin"], p["passes"], out=out, add=p["add"], singly=p["singly"])
+    if feature == "sample_map":
+        return r.sample_map(cam, opt, _sample_map(p["map"], size), p["pass_begin"], out=out, add=p["add"])
+    return r.depth_planes(cam, opt, p["pass_begin"], p["passes"], p["depths"], out=out, add=p["add"], singly=p["singly"])
+
+
 @contextlib.contextmanager
 def _stream(side):
     """device entries run on torch's current stream: a non-default one where the schedule says so.  The result is read inside, in that
@@ -240,7 +323,21 @@ def observe(r, op, state, keep=None):
             with _stream(p["stream"]):
                 return [dev(getattr(r, kind)(_device(fam, "points"), *args))]
         return [getattr(r, kind)(_inputs(fam)["points"], *args)]
+    if kind in rm.PLANE_OBSERVERS:
+        if kind.endswith("_device"):
+            with _stream(p["stream"]):
+                return [dev(plane_call(r, rm.feature_of(kind), p, state, True))]
+        return [plane_call(r, rm.feature_of(kind), p, state, False)]
     raise AssertionError(kind)
+
+
+def _refused_planes(r, p, before):
+    """a plane call the renderer must refuse as it is now: TinselHipError, and `out` as it was"""
+    call = rm.REFUSED_PLANES[p["feature"]]
+    with _stream(p.get("stream", False)):
+        out = planes_out(r, p["feature"], call, before, p["device"], fill=7.0)
+        _refused(lambda: plane_call(r, p["feature"], call, before, p["device"], out))
+        assert bool((out == 7.0).all()), "a refused %s call wrote to its output" % p["feature"]
 
 
 def _refused(call):
@@ -326,6 +423,16 @@ def apply_live(r, op, before, keep):
         _refused(lambda: r.denoise(beauty=_image(1, (21, 35)), params=denoise_params(radius=9)))
     elif kind == "refused_tuning":
         _refused(lambda: r.set_tuning(abi.Tuning(walk_block=100)))
+    elif kind == "refused_planes_sharded":
+        r.set_shard(1, 2, 16)
+        _refused_planes(r, p, before)
+        r.set_shard(*before.shard)
+    elif kind == "refused_planes_fast":
+        r.set_arithmetic(abi.ARITH_FAST)
+        _refused_planes(r, p, before)
+        r.set_arithmetic(abi.ARITH_EXACT)
+    elif kind == "set_bake":
+        r.set_tuning(abi.Tuning(bounce_share=p["share"], bounce_bake=p["mode"]))
     else:
         raise AssertionError(kind)
 
@@ -350,10 +457,11 @@ def fresh(state, level="full"):
     return r
 
 
-def run_schedule(ops, seed=None, forget=None, report=None):
+def run_schedule(ops, seed=None, forget=None, report=None, at_end=None):
     """Runs a schedule on one live renderer and holds every observation to a fresh one; raises Mismatch at the first that differs.
     `forget`: the sabotage of renderer_model.Model -- what the fresh renderers are brought to is then the sabotaged model's belief, while the
-    live renderer is always given the schedule's own, valid calls.  Returns (observations, seconds)."""
+    live renderer is always given the schedule's own, valid calls.  `at_end`: called with the live renderer behind the last op, before it
+    is closed.  Returns (observations, seconds)."""
     import tinsel_amd
     truth, belief = rm.Model(), rm.Model(forget)
     live, keep, seen = None, {}, 0
@@ -369,7 +477,10 @@ def run_schedule(ops, seed=None, forget=None, report=None):
                 live = tinsel_amd.create_gpu_renderer(_scene(truth.state.scene))
                 continue
             if kind in rm.OBSERVERS:
+                counted = live.stats() if kind in rm.PLANE_OBSERVERS else None
                 got = observe(live, op, before, keep)
+                if counted is not None and live.stats() != counted:          # (the statistics of these calls are their own)
+                    raise Mismatch(step, op, "the statistics were %r and are %r" % (counted, live.stats()), ops, seed)
                 # (a render with read-back is held to the state it leads to; every other observer leaves the state as it was)
                 other = fresh(_without_last_render(belief.state) if kind == "render_readback" else belief.state, rm.replay_level(kind))
                 try:
@@ -398,6 +509,8 @@ def run_schedule(ops, seed=None, forget=None, report=None):
             what = _differ([live.read_accum(), np.array([live.get_pass_index()], np.uint32)], want)
             if what:
                 raise Mismatch(len(ops) - 1, ("read_accum at the end", {}), what, ops, seed)
+        if at_end is not None:
+            at_end(live)
     finally:
         if live is not None:
             live.close()
@@ -427,7 +540,7 @@ def _anchor(live, state, out, step, op, ops, seed):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("seed", rm.SEEDS)
+@pytest.mark.parametrize("seed", rm.ALL_SEEDS)         # (the chosen set, and the earlier set's seeds as further histories)
 def test_history_leaves_no_trace(seed):
     ops = rm.schedule(seed)
     seen, seconds = run_schedule(ops, seed, report="seed %d" % seed)
@@ -448,6 +561,19 @@ TEETH = {
     "that init changed the size": ([("create", {"scene": "cornell"}), ("init", {"size": (48, 32)}), RENDER(1), ("read_accum", {}),
                                     ("init", {"size": (16, 16)}), RENDER(1), ("read_accum", {}), ("present", {"nlm": 1})], (4, "size"), 6),
 }
+# the plane features: the model forgets an update_scene, and the first observation behind it is one of theirs
+_MOVED = [("create", {"scene": "anim_cornell"}), ("init", {"size": (33, 17)}), RENDER(1), ("read_accum", {}), ("update_scene", {"frame": 1}),
+          ("init", {"size": (33, 17)})]
+TEETH.update({
+    "an update_scene before light groups": (_MOVED + [("light_groups", {"table": "parity", "pass_begin": 5, "passes": 2}), ("get_pass_index", {})], (4, "op"), 6),
+    "an update_scene before views": (_MOVED + [("views_device", {"count": 3, "pass_begin": 7, "passes": 1, "add": True, "singly": False, "seed": 2,
+                                                                 "stream": True}), ("get_pass_index", {})], (4, "op"), 6),
+    "an update_scene before a sample map": (_MOVED + [("sample_map", {"map": "uniform", "pass_begin": 3, "add": False, "seed": 1}),
+                                                      ("get_pass_index", {})], (4, "op"), 6),
+    "an update_scene before depth planes": (_MOVED + [("depth_planes_device", {"depths": (1, 2, 3, 4), "pass_begin": 2, "passes": 2, "add": False,
+                                                                               "singly": True, "seed": 1, "stream": False}),
+                                                      ("get_pass_index", {})], (4, "op"), 6),
+})
 
 
 @pytest.mark.timeout(120)
@@ -460,6 +586,26 @@ def test_a_model_that_forgets_is_caught_at_the_first_observation_behind(what):
     print(caught.value)
     assert caught.value.step == expected
     run_schedule(ops)                                                # and the schedule itself is sound
+
+
+BAKED = [("create", {"scene": "cornell"}), ("set_bake", {"mode": 1, "share": 0}), ("init", {"size": (64, 64)}), RENDER(2), ("read_accum", {}),
+         ("views", {"count": 3, "pass_begin": 7, "passes": 1, "add": False, "singly": False, "seed": 1}), ("reserve", {"passes": 4, "depth": 4}),
+         ("init", {"size": (64, 64)}), ("set_pass_index", {"index": 0}),
+         ("render_readback", {"depth": 4, "mode": "pathtrace", "passes": 4, "golden": True})]
+
+
+@pytest.mark.timeout(120)
+def test_the_baked_instance_serves_a_schedule_that_asks_for_it():
+    """set_bake is never an error: where nothing compiles, every schedule with it would pass on the library's own instance.  So once, on the
+    scene whose plan gives the closed fused kernel, the baked instance must be installed and must have served launches -- and then its
+    frame is the golden file's, bit for bit (the anchor), and every observation a fresh, unbaked renderer's."""
+    from tinsel_amd import abi
+    status = []
+    seen, _ = run_schedule(BAKED, report="baked", at_end=lambda live: status.append(live.bake_status()))
+    assert seen == len(rm.observations(BAKED)) == 3
+    print(status[0])
+    assert status[0]["state"] in (abi.BAKE_COMPILED, abi.BAKE_FROM_CACHE), status[0]
+    assert status[0]["launches"] > 0, status[0]
 
 
 # -- groups -----------------------------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,9 @@ import pytest
 from tests import renderer_model as rm
 
 SCHEDULES = {seed: rm.schedule(seed) for seed in rm.SEEDS}
+# (with the earlier set's seeds, which are run too: what a schedule must be on its own is asked of them as well, what the SET must cover of
+# SCHEDULES alone)
+ALL = {seed: SCHEDULES[seed] if seed in SCHEDULES else rm.schedule(seed) for seed in rm.ALL_SEEDS}
 
 
 def test_the_set_is_small():
@@ -17,27 +20,27 @@ def test_the_set_is_small():
         assert ops[0][0] == "create" and all(k != "create" for k, _ in ops[1:]), seed
 
 
-@pytest.mark.parametrize("seed", rm.SEEDS)
+@pytest.mark.parametrize("seed", rm.ALL_SEEDS)
 def test_schedule_is_reproducible_and_a_literal(seed):
     again = rm.schedule(seed)
-    assert again == SCHEDULES[seed] and again is not SCHEDULES[seed]
+    assert again == ALL[seed] and again is not ALL[seed]
     assert eval(repr(again), {}) == again                    # what a failure message prints replays as it is
 
 
-@pytest.mark.parametrize("seed", rm.SEEDS)
+@pytest.mark.parametrize("seed", rm.ALL_SEEDS)
 def test_schedule_observes_at_least_ten_times(seed):
-    assert len(rm.observations(SCHEDULES[seed])) >= 10
+    assert len(rm.observations(ALL[seed])) >= 10
 
 
-@pytest.mark.parametrize("seed", rm.SEEDS)
+@pytest.mark.parametrize("seed", rm.ALL_SEEDS)
 def test_schedule_is_valid_for_its_scene_and_its_replays_stay_short(seed):
     """every op is one the scene supports (Model.apply asserts it), and at every step a fresh renderer gets there with at most 4 render
     calls and 8 passes"""
     m = rm.Model()
-    for k, op in enumerate(SCHEDULES[seed]):
+    for k, op in enumerate(ALL[seed]):
         m.apply(k, op)
         if any(r[0] != m.state.scene for r in m.state.renders):      # the scene changed under a frame: nothing looks before the next init
-            assert SCHEDULES[seed][k + 1][0] in ("init", "init_external", "set_shard", "set_russian_roulette", "set_batch_paths", "set_lookahead"), (seed, k)
+            assert ALL[seed][k + 1][0] in ("init", "init_external", "set_shard", "set_russian_roulette", "set_batch_paths", "set_lookahead"), (seed, k)
             continue
         renders = [s for s in rm.replay(m.state) if s[0] == "render"]
         assert len(renders) <= rm.MAX_REPLAY_RENDERS and sum(s[3] for s in renders if s[2] == "pathtrace") <= rm.MAX_REPLAY_PASSES, (seed, k)
@@ -94,6 +97,12 @@ def test_the_whole_requirement_table_holds_on_the_committed_seeds():
     assert not short, short
 
 
+def test_the_committed_seeds_are_what_choose_seeds_returns():
+    seeds, missing = rm.choose_seeds(range(3000))
+    assert not missing, missing
+    assert tuple(seeds) == rm.SEEDS
+
+
 def test_mutators_draw_what_the_issue_lists():
     ops = [op for s in SCHEDULES.values() for op in s]
     sizes = {p["size"] for k, p in ops if k in ("init", "init_external")}
@@ -115,6 +124,85 @@ def test_mutators_draw_what_the_issue_lists():
     host_next = lambda s: any(a[1].get("stream") and not ("stream" in b[1]) for a, b in zip(s, s[1:]))           # noqa: E731
     assert sum(host_next(s) for s in SCHEDULES.values()) >= 3
     assert {s[0][1]["scene"] for s in SCHEDULES.values()} == set(rm.FAMILIES)
+
+
+def test_plane_observers_draw_what_the_issue_lists():
+    """light groups, views, sample maps and depth planes, host and device entry: every listed value somewhere, frames the model's SIZES,
+    passes and counts 1 to 3, and never a sharded renderer in front of one"""
+    ops = [op for s in SCHEDULES.values() for op in s]
+    of = lambda f: [p for k, p in ops if rm.feature_of(k) == f]                                                  # noqa: E731
+    for kind in rm.PLANE_OBSERVERS:
+        assert kind in rm.FRAME_OBSERVERS and rm.replay_level(kind) == "frame"
+        assert sum(any(k == kind for k, _ in s) for s in SCHEDULES.values()) >= 2, kind
+    for f in rm.PLANE_FEATURES:
+        assert {p["pass_begin"] for p in of(f)} == set(rm.PLANE_PASSES[f]), f
+        assert all(("stream" in p) == k.endswith("_device") for k, p in ops if rm.feature_of(k) == f), f
+    for f in ("light_groups", "views", "depth_planes"):
+        assert {p["passes"] for p in of(f)} == {1, 2}, f
+    for f in ("views", "depth_planes"):
+        assert {(p["add"], p["singly"]) for p in of(f)} == {(a, s) for a in (False, True) for s in (False, True)}, f
+    assert {p["add"] for p in of("sample_map")} == {False, True}
+    assert {p["table"] for p in of("light_groups")} == set(rm.GROUP_TABLES) == {"one", "parity", "eight"}
+    assert {p["count"] for p in of("views")} == set(rm.VIEW_COUNTS) == {1, 3, 6}
+    assert {p["map"] for p in of("sample_map")} == set(rm.SAMPLE_MAPS) == {"uniform", "random", "crop", "zeros"}
+    assert {p["depths"] for p in of("depth_planes")} == set(rm.PLANE_DEPTHS) == {(1,), (1, 2, 3, 4), (2, 6), tuple(range(1, 17))}
+    assert all(p["seed"] in (1, 2, 3) for f in rm.PLANE_FEATURES[1:] for p in of(f))
+    for seed, s in SCHEDULES.items():
+        m = rm.Model()
+        for k, op in enumerate(s):
+            if op[0] in rm.PLANE_OBSERVERS:
+                assert m.state.shard[1] == 1 and m.state.arith == 0 and m.state.size in rm.SIZES, (seed, k)
+            m.apply(k, op)
+    # the refused calls: each feature, host and device entry
+    refused = [p for k, p in ops if k in ("refused_planes_sharded", "refused_planes_fast")]
+    assert {p["feature"] for p in refused} == set(rm.PLANE_FEATURES) and {p["device"] for p in refused} == {False, True}
+    assert set(rm.REFUSED_PLANES) == set(rm.PLANE_FEATURES)
+
+
+def test_group_tables_are_made_from_the_primitive_count_alone():
+    assert rm.group_table("one", 9) == ([0]*9, 0, 1)
+    assert rm.group_table("parity", 5) == ([0, 1, 0, 1, 0], 1, 2)
+    table, env, groups = rm.group_table("eight", 16)
+    assert (env, groups) == (-1, 8) and table == [0, 1, 2, 3, 4, 5, -1, 7, 0, 1, 2, 3, 4, -1, 6, 7]
+    assert rm.group_table("eight", 3) == ([0, 1, 2], -1, 8)              # G stays 8 where the scene has fewer primitives
+
+
+def test_the_bake_mode_is_live_only_and_a_set_tuning_drops_it():
+    assert "set_bake" in rm.LIVE_ONLY and {"bounce_share", "bounce_bake"} <= set(rm.TUNING_FIELDS)
+    ops = [op for s in SCHEDULES.values() for op in s]
+    assert {(p["mode"], p["share"]) for k, p in ops if k == "set_bake"} >= {(1, 0)}
+    assert {p["mode"] for k, p in ops if k == "set_bake"} == {1, 0, -1} and {p["share"] for k, p in ops if k == "set_bake"} == {0, -1}
+    m = rm.Model()
+    for k, op in enumerate([("create", {"scene": "cornell"}), ("init", {"size": (16, 16)}), ("set_bake", {"mode": 1, "share": 0})]):
+        m.apply(k, op)
+    assert rm.replay(m.state) == [("create", ("pack", "cornell")), ("init", 16, 16)]          # the fresh renderer never gets it
+    # the builder knows what is in force: a set_tuning drops the mode (and the small batches), as the library does
+    b = rm._Builder(5)
+    b.emit("set_batch_paths", paths=1024)
+    b.emit("set_bake", mode=1, share=0)
+    assert b.bake == (1, 0) and not b.small_batches
+    b.emit("set_tuning", fields={})
+    assert b.bake is None
+    # on cornell: the mode across a rebuild, the tolerance arm and a set_tuning; and a schedule whose golden anchor finds the mode in force
+    for name in ("bake_across_neutral_ops", "bake_in_force_at_the_anchor"):
+        assert [s for s, o in SCHEDULES.items() if name in rm.sequences(o) and o[0][1]["scene"] == "cornell"], name
+
+
+def test_the_teeth_bite_at_an_observation_of_the_kind_they_name():
+    from tests import test_gpu_histories as th
+    kinds = {}
+    for what, (ops, forget, expected) in th.TEETH.items():
+        m = rm.Model()
+        for k, op in enumerate(ops):
+            m.apply(k, op)                                               # a valid schedule
+        assert [k for k in rm.observations(ops) if k > forget[0]][0] == expected, what
+        kinds[rm.feature_of(ops[expected][0])] = ops[0][1]["scene"], ops[forget[0]][0]
+    assert all(kinds.get(f) == ("anim_cornell", "update_scene") for f in rm.PLANE_FEATURES), kinds
+    m = rm.Model()
+    for k, op in enumerate(th.BAKED):
+        m.apply(k, op)
+    assert th.BAKED[:3] == [("create", {"scene": "cornell"}), ("set_bake", {"mode": 1, "share": 0}), ("init", {"size": (64, 64)})]
+    assert th.BAKED[-1][1].get("golden") and rm.GOLDEN_FRAMES["cornell"] == (64, 64, 4, 4)
 
 
 def test_every_schedule_on_a_scene_with_a_golden_file_ends_on_it(golden_dir):
