@@ -1410,6 +1410,34 @@ void port_leaf_trace(void* h, int n, const float* in, int32_t* outPrim, float* o
     }
 }
 
+/* ProbeSample / ProbePdf / Sky::Eval (probe.h:128-236, scene.h:168-178), one row per seed: the direction, colour and pdf ProbeSample draws,
+ * then ProbePdf and Sky::Eval of that direction.  Without a probe the direction is UniformSampleSphere of the two draws and the rest zero
+ * but the sky. */
+void port_leaf_probe(void* h, int n, const uint32_t* seeds, float* outDir, float* outColor, float* outPdf, float* outPdfOfDir, float* outEvalOfDir)
+{
+    const scene_t* sc = (const scene_t*)h;
+    for (int i = 0; i < n; ++i)
+    {
+        rng_t rand = rng_seeded(seeds[i]);
+        vec3 dir = v3s(0.0f), color = v3s(0.0f);
+        float pdf = 0.0f;
+        if (sc->probeValid)
+            probe_sample(sc, &dir, &color, &pdf, &rand);
+        else
+        {
+            float u1 = rng_randf(&rand);
+            float u2 = rng_randf(&rand);
+            dir = uniform_sample_sphere(u1, u2);
+        }
+        outDir[i*3 + 0] = dir.x; outDir[i*3 + 1] = dir.y; outDir[i*3 + 2] = dir.z;
+        outColor[i*3 + 0] = color.x; outColor[i*3 + 1] = color.y; outColor[i*3 + 2] = color.z;
+        outPdf[i] = pdf;
+        outPdfOfDir[i] = sc->probeValid ? probe_pdf(sc, dir) : 0.0f;
+        vec3 e = sky_eval(sc, dir);
+        outEvalOfDir[i*3 + 0] = e.x; outEvalOfDir[i*3 + 1] = e.y; outEvalOfDir[i*3 + 2] = e.z;
+    }
+}
+
 /* ---------------------------------------------------------------------------------------------
  * Display stage: what main.cpp does with the accumulated pixels every frame (main.cpp:258-282)
  * and the 8-bit conversion of WritePng (png.cpp:323-343).  powf / expf are the host libm's.

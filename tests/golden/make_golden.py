@@ -91,6 +91,8 @@ def main():
     R.free(h)
 
     # cornell + probe (open box is lit by the probe through the camera side)
+    # (no path of this scene reaches the probe: its tests pin that the two draws are consumed, nothing more -- measured with the C oracle,
+    # whose accumulator is the same bits under five different probes; tests/test_probe_host.py keeps a check of it)
     h = R.load_tin(os.path.join(args.ref, "data/cornell.tin"))
     R.lib.ref_scene_set_procedural_probe(h, 64, 32)
     R.write_pack(h, os.path.join(HERE, "cornell_probe.pack"))

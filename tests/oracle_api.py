@@ -146,8 +146,6 @@ class RefOracle(_OracleBase):
         L.ref_leaf_primitive_intersect.restype = None
         L.ref_leaf_primitive_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ref_leaf_primitive_sample.restype = None
-        L.ref_leaf_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 5
-        L.ref_leaf_probe.restype = None
         L.ref_hardware_threads.restype = C.c_int
         if hasattr(L, "ref_add_sample_agrees"):
             L.ref_add_sample_agrees.restype = C.c_int
@@ -228,17 +226,6 @@ class RefOracle(_OracleBase):
         self.lib.ref_leaf_primitive_sample(h, prim, n, _fp(times), _fp(seeds), _fp(pos), _fp(nrm), _fp(st))
         return pos, nrm, st
 
-    def probe(self, h, seeds):
-        seeds = np.ascontiguousarray(seeds, np.uint32)
-        n = seeds.shape[0]
-        d = np.zeros((n, 3), np.float32)
-        c = np.zeros((n, 3), np.float32)
-        pdf = np.zeros(n, np.float32)
-        pdf2 = np.zeros(n, np.float32)
-        ev = np.zeros((n, 3), np.float32)
-        self.lib.ref_leaf_probe(h, n, _fp(seeds), _fp(d), _fp(c), _fp(pdf), _fp(pdf2), _fp(ev))
-        return d, c, pdf, pdf2, ev
-
 
 def _bounds_api():
     def primitive_bounds(self, h, prim):
@@ -253,6 +240,28 @@ def _bounds_api():
 
 
 _bounds_api()
+
+
+def _probe_api():
+    def probe(self, h, seeds):
+        """ProbeSample / ProbePdf / Sky::Eval (probe.h:128-236, scene.h:168-178) per seed, on both oracles -> (direction, colour, pdf,
+        ProbePdf(direction), Sky::Eval(direction))"""
+        fn = getattr(self.lib, self.prefix + "leaf_probe")
+        fn.restype = None
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p]*5
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        n = seeds.shape[0]
+        d = np.zeros((n, 3), np.float32)
+        c = np.zeros((n, 3), np.float32)
+        pdf = np.zeros(n, np.float32)
+        pdf2 = np.zeros(n, np.float32)
+        ev = np.zeros((n, 3), np.float32)
+        fn(h, n, _fp(seeds), _fp(d), _fp(c), _fp(pdf), _fp(pdf2), _fp(ev))
+        return d, c, pdf, pdf2, ev
+    _OracleBase.probe = probe
+
+
+_probe_api()
 
 
 def _trace_api():

@@ -1,6 +1,7 @@
 """k_bounce's FIT instances (tn_fused.h: the fused kernel compiled for a fixed set of scene and plan features) against the general kernel,
 forced through tinsel_hip_tuning::bounce_fit = 0.  Every comparison is bit for bit on the accumulator; the instance that ran is read back
-through tinsel_hip_bounce_plan."""
+through tinsel_hip_bounce_plan.  (The env_loft rows need tests/golden/large/; the probe coverage that needs no large pack is
+tests/test_gpu_probe_synthetic.py.)"""
 import os
 
 import numpy as np

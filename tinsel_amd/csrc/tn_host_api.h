@@ -631,7 +631,9 @@ int tinsel_hip_set_probe_sampling(tinsel_hip* r, int mode)
         for (int j = 0; j < H; ++j)
             for (int i = 0; i < W; ++i)
             {
-                const double p = (double)py[(size_t)j]*(double)px[(size_t)j*W + i];
+                // a row with pdfY == 0 has probability 0 whatever its pdfX holds: BuildCDF leaves 0*inf = NaN there for an all-black row,
+                // and 0*NaN would make the total NaN
+                const double p = (py[(size_t)j] == 0.0f) ? 0.0 : (double)py[(size_t)j]*(double)px[(size_t)j*W + i];
                 scaled[(size_t)j*W + i] = p;
                 total += p;
             }
